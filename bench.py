@@ -5,8 +5,15 @@ the torchdiffeq grid (step_size 0.02, the path the reference actually runs) + f8
 Synthetic data: seeded random-init weights of the real architectures (de-zeroed), seeded Gaussian latents; one "step" = one full batch
 through the hot path, INCLUDING the host-to-device copy of its latents (64 x 16 KiB from pinned memory) -- everything else is resident.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config 2|3|4|5|6]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config 2|3|4|5|6] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, warms up, times K steps and prints the line (images/sec and ms_per_step).  --full adds what the headline does not need:
+the check that the in-flight lanes agree, the solver / decode split of one step, every rank's sustained clock, the roofline of the dominant
+kernel and the DiT block (unless --no-roofline), and the CPU-oracle baseline of config 2 (unless --no-cpu-baseline).
+--dump-outputs DIR writes what the last timed step returned (rank 0's uint8 NHWC images) as DIR/images.npy in float32; inputs are seeded,
+so two builds run with the same arguments can be compared output for output.  An output beyond DUMP_BUDGET_BYTES is cut to a fixed, seeded
+sample of whole images (dump_outputs).
 
 --config selects another BASELINE.json configuration (same JSON contract, its own `roofline`):
   3  DiT-L/2 class-conditional, dopri5 rtol = atol = 1e-5, CFG 1.5, 64 live + 64 null rows, + decode
@@ -34,6 +41,7 @@ sys.path.insert(0, ROOT)
 MFMA_PEAK_TFLOPS = 2500.0  # MI355X dense fp16/bf16 (MI355X_MICROARCH.md)
 EDM_FFHQ_FLOP_PER_IMAGE = 73.053765632e9  # one DhariwalUNet evaluation at the ffhq_adm size: hook-counted on the reference module (tests/golden/edm_full.pt, oracle/make_golden.py::golden_edm_full)
 CONFIG3_FIELD_GAIN = 100.0  # output-layer scale of config 3's synthetic field (see --field-gain)
+DUMP_BUDGET_BYTES = 60 << 20  # --dump-outputs: all .npy files together stay below 64 MB
 
 # L2-miss traffic of the dominant GEMM of config 2 (fc1: M 16384 x N 4096 x K 1024, folded-LayerNorm + GELU epilogue) per launch comes from a TRACKED
 # measurement file, profiles/fc1_traffic.json, written by tools/profile_round.sh from separate rocprofv3 PMC passes of the shipped kernel IN SITU
@@ -71,10 +79,37 @@ def parse():
                         "job's batches are independent, test_flow_latent_ddp.py:128-146; while one lane's workgroups sit in their HBM-bound epilogues or run a "
                         "small-map kernel that cannot fill the chip, the other lane's kernels use it), 1 for config 3 (dopri5 reads a value back per step).  Rounds 1-4 reported one batch in "
                         "flight: --in-flight 1 reproduces that line")
-    p.add_argument("--no-cpu-baseline", action="store_true")
-    p.add_argument("--no-roofline", action="store_true")
+    p.add_argument("--full", action="store_true",
+                   help="also run what the headline does not need: lane agreement check, solver / decode split, sustained clocks, roofline, CPU baseline")
+    p.add_argument("--no-cpu-baseline", action="store_true", help="(with --full) skip the CPU-oracle baseline")
+    p.add_argument("--no-roofline", action="store_true", help="(with --full) skip the roofline measurements")
+    p.add_argument("--dump-outputs", metavar="DIR", default="",
+                   help="write what the last timed step returned as DIR/<name>.npy (float32, at most DUMP_BUDGET_BYTES in all)")
     p.add_argument("--stub", action="store_true", help="(tests) CPU / gloo rehearsal of the launcher + rank logic: a stub step instead of the HIP path")
-    return p.parse_args()
+    a = p.parse_args()
+    if a.steps < 1:
+        p.error("--steps must be at least 1")
+    return a
+
+
+def dump_outputs(d, arrays, budget=DUMP_BUDGET_BYTES):
+    """Write each tensor of `arrays` ({name: tensor}) as d/<name>.npy in float32.  A tensor larger than its share of `budget` keeps a fixed,
+    seeded sample of its leading-axis rows (whole images), in their original order: the same rows at every run with the same arguments.
+    -> {name: (rows written, rows computed)}."""
+    import numpy as np
+
+    os.makedirs(d, exist_ok=True)
+    share = budget // max(1, len(arrays))
+    kept = {}
+    for name, t in arrays.items():
+        n = t.shape[0]
+        k = min(n, max(1, share // (4 * max(1, t[0].numel()))))
+        if k < n:
+            rows = torch.randperm(n, generator=torch.Generator().manual_seed(0))[:k].sort().values
+            t = t[rows.to(t.device)]
+        np.save(os.path.join(d, name + ".npy"), t.detach().float().cpu().numpy())
+        kept[name] = (k, n)
+    return kept
 
 
 def self_launch(a, argv=None):
@@ -456,9 +491,11 @@ def main_stub(a, world, rank):
     got.clear()
     t0 = time.perf_counter()
     for _ in range(a.steps):
-        step()
+        out = step()
     fence()
     el = time.perf_counter() - t0
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, {"images": out})
     if world > 1:
         tt = torch.tensor([el], dtype=torch.float64)
         allt = [torch.zeros_like(tt) for _ in range(world)]
@@ -527,7 +564,8 @@ def main():
         torch.cuda.synchronize()
         # same latents through both lanes: the SAME images, bit for bit (the co-scheduling non-determinism of rounds 4 is root-caused and fixed:
         # profiles/r05_cosched_root_cause.txt; tests/test_gpu_cosched.py)
-        assert all(torch.equal(first[0], f) for f in first[1:]), "the lanes must produce identical images for the same latents"
+        if a.full:
+            assert all(torch.equal(first[0], f) for f in first[1:]), "the lanes must produce identical images for the same latents"
     nstep = [0]
 
     def step():
@@ -578,6 +616,9 @@ def main():
         el = max(float(t) for t in allt)
         rank_ips = [B * a.steps / float(t) for t in allt]
     assert out.shape == (B, S, S, 3) and float(out[:4].float().std()) > 0
+    if a.dump_outputs and rank == 0:  # before anything below runs a lane's solver again (its output buffers are reused)
+        for name, (k, n) in dump_outputs(a.dump_outputs, {"images": out}).items():
+            print(f"dumped {name}: {k} of {n} rows -> {os.path.join(a.dump_outputs, name + '.npy')}", file=sys.stderr, flush=True)
     ips = world * B * a.steps / el
 
     f_model = w["f_model"]
@@ -603,38 +644,39 @@ def main():
         "mfma_frac_whole_path": ips * f_img / (MFMA_PEAK_TFLOPS * 1e12 * world),
     }
 
-    # split of one step (outside the timed region): solver-only and decode-only
-    ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
-    ev[0].record()
-    lat = solve(x_dev)
-    ev[1].record()
-    images_to_uint8(vae.decode(lat / 0.18215).sample)
-    ev[2].record()
-    torch.cuda.synchronize()
-    res["split_ms"] = {"solver": ev[0].elapsed_time(ev[1]), "vae_decode_u8": ev[1].elapsed_time(ev[2])}
-    # what every rank ran at: the clock its GPU sustains under matrix load (boxes / GPUs differ by several percent under the power cap) and its own
-    # solve / decode times -- so that a multi-GPU line explains its own spread
-    from lfm_amd import hip as _hip
+    if a.full:  # everything below is outside the headline: --full only
+        # split of one step (outside the timed region): solver-only and decode-only
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
+        ev[0].record()
+        lat = solve(x_dev)
+        ev[1].record()
+        images_to_uint8(vae.decode(lat / 0.18215).sample)
+        ev[2].record()
+        torch.cuda.synchronize()
+        res["split_ms"] = {"solver": ev[0].elapsed_time(ev[1]), "vae_decode_u8": ev[1].elapsed_time(ev[2])}
+        # what every rank ran at: the clock its GPU sustains under matrix load (boxes / GPUs differ by several percent under the power cap) and its own
+        # solve / decode times -- so that a multi-GPU line explains its own spread
+        from lfm_amd import hip as _hip
 
-    mine = torch.tensor([_hip.effective_clock_mhz(dev), res["split_ms"]["solver"], res["split_ms"]["vae_decode_u8"], B * a.steps / el_local], device=dev,
-                        dtype=torch.float64)
-    per = [mine]
-    if world > 1:
-        per = [torch.zeros_like(mine) for _ in range(world)]
-        dist.all_gather(per, mine)
-    res["per_rank"] = [{"rank": r, "clock_mhz_under_mfma_load": round(float(v[0]), 1), "solver_ms": round(float(v[1]), 3), "vae_decode_u8_ms": round(float(v[2]), 3),
-                        "images_per_sec": round(float(v[3]), 3)} for r, v in enumerate(per)]
-    res["clock_mhz_under_mfma_load"] = res["per_rank"][0]["clock_mhz_under_mfma_load"]
+        mine = torch.tensor([_hip.effective_clock_mhz(dev), res["split_ms"]["solver"], res["split_ms"]["vae_decode_u8"], B * a.steps / el_local], device=dev,
+                            dtype=torch.float64)
+        per = [mine]
+        if world > 1:
+            per = [torch.zeros_like(mine) for _ in range(world)]
+            dist.all_gather(per, mine)
+        res["per_rank"] = [{"rank": r, "clock_mhz_under_mfma_load": round(float(v[0]), 1), "solver_ms": round(float(v[1]), 3), "vae_decode_u8_ms": round(float(v[2]), 3),
+                            "images_per_sec": round(float(v[3]), 3)} for r, v in enumerate(per)]
+        res["clock_mhz_under_mfma_load"] = res["per_rank"][0]["clock_mhz_under_mfma_load"]
 
-    if rank == 0 and not a.no_roofline:
-        if a.config == 5:
-            res["roofline"] = roofline_adm(B, dev)
-        elif a.config == 6:  # the 32x32 level (256 channels: 10 of the evaluation's 3x3 convolutions run at this shape or its 512-input variant)
-            res["roofline"] = roofline_adm(B, dev, side=32, ch=256)
-        else:
-            res["roofline"], res["roofline_block"] = roofline_dit(w["model"], lat, B if a.config == 2 else 2 * B, dev)
-    if rank == 0 and world == 1 and not a.no_cpu_baseline and a.config == 2:
-        res["cpu_baseline"] = cpu_baseline(w["name"], a.nfe)
+        if rank == 0 and not a.no_roofline:
+            if a.config == 5:
+                res["roofline"] = roofline_adm(B, dev)
+            elif a.config == 6:  # the 32x32 level (256 channels: 10 of the evaluation's 3x3 convolutions run at this shape or its 512-input variant)
+                res["roofline"] = roofline_adm(B, dev, side=32, ch=256)
+            else:
+                res["roofline"], res["roofline_block"] = roofline_dit(w["model"], lat, B if a.config == 2 else 2 * B, dev)
+        if rank == 0 and world == 1 and not a.no_cpu_baseline and a.config == 2:
+            res["cpu_baseline"] = cpu_baseline(w["name"], a.nfe)
     if rank == 0:
         print(json.dumps(res), flush=True)
     if world > 1:

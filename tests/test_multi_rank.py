@@ -212,6 +212,60 @@ def test_bench_refuses_a_mismatched_world():
     assert r.returncode != 0 and b"WORLD_SIZE=1" in r.stderr
 
 
+def test_bench_dump_outputs_is_the_last_step_and_repeatable(tmp_path):
+    """--dump-outputs DIR writes what the last timed step returned as DIR/images.npy (float32); the inputs are seeded, so two runs with the same
+    arguments write the same arrays.  --stub: the same code path around a CPU stub step."""
+    import json
+    import subprocess
+    import sys
+
+    import numpy as np
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    got = []
+    for run in ("a", "b"):
+        d = tmp_path / run
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--stub", "--dump-outputs", str(d)],
+                           env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=300)
+        assert r.returncode == 0, r.stderr.decode()[-2000:]
+        lines = [ln for ln in r.stdout.decode().splitlines() if ln.startswith("{")]
+        assert len(lines) == 1 and json.loads(lines[0])["steps"] == 2 and json.loads(lines[0])["ms_per_step"] > 0
+        assert sorted(os.listdir(d)) == ["images.npy"]
+        got.append(np.load(d / "images.npy"))
+    assert got[0].dtype == np.float32 and got[0].shape == (4, 8, 8, 4)  # the stub's "images": its 4-channel latents as uint8 NHWC
+    assert np.array_equal(got[0], got[1]) and got[0].std() > 0
+
+
+def test_bench_dump_outputs_keeps_a_fixed_sample_within_the_budget(tmp_path):
+    import sys
+
+    import numpy as np
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    sys.path.insert(0, root)
+    import bench
+
+    x = torch.arange(10 * 6, dtype=torch.uint8).reshape(10, 2, 3)  # 10 rows of 24 float32 bytes
+    kept = [bench.dump_outputs(str(tmp_path / d), {"images": x, "small": x[:2]}, budget=200) for d in ("a", "b")]
+    assert kept[0] == kept[1] == {"images": (4, 10), "small": (2, 2)}
+    a, b = np.load(tmp_path / "a" / "images.npy"), np.load(tmp_path / "b" / "images.npy")
+    assert a.dtype == np.float32 and a.shape == (4, 2, 3) and np.array_equal(a, b)
+    rows = a[:, 0, 0] / 6  # the rows kept, in their original order
+    assert list(rows) == sorted(rows) and all(np.array_equal(a[i], x[int(r)].float().numpy()) for i, r in enumerate(rows))
+    assert np.array_equal(np.load(tmp_path / "a" / "small.npy"), x[:2].float().numpy())
+    assert bench.dump_outputs(str(tmp_path / "c"), {"images": x}) == {"images": (10, 10)}  # the default budget holds it whole
+
+
+def test_bench_refuses_zero_steps():
+    import subprocess
+    import sys
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "0", "--stub"], stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=120)
+    assert r.returncode != 0 and b"--steps" in r.stderr
+
+
 def test_bench_flop_closed_forms_match_the_oracle():
     import sys
 

@@ -3,7 +3,7 @@
 # -ffast-math on the same box (LFM_FAST_MATH=1), same commands.  usage (on the GPU box): tools/fastmath_ab.sh <tag>
 TAG=${1:-r4fm}; R=${GRAFT_REPO_ROOT:-/root/repo}; O=$R/gpurun_out/$TAG; mkdir -p $O; cd $R
 run() {  # label
-  timeout 300 python bench.py --steps 5 --warmup 2 --no-cpu-baseline 2>/dev/null | grep '^{' > $O/bench_$1.json
+  timeout 300 python bench.py --full --steps 5 --warmup 2 --no-cpu-baseline 2>/dev/null | grep '^{' > $O/bench_$1.json
   timeout 900 python -m pytest tests/test_gpu_dit.py tests/test_gpu_vae.py tests/test_gpu_unet.py tests/test_gpu_sampler.py -q -m gpu -x 2>&1 | tail -3 > $O/tests_$1.txt
   timeout 200 python tools/fastmath_err.py > $O/err_$1.txt 2>&1
 }

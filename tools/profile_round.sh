@@ -7,11 +7,11 @@ R=${GRAFT_REPO_ROOT:-/root/repo}
 cd /tmp && export TMPDIR=/tmp
 O=$R/gpurun_out/$TAG; mkdir -p $O
 # ONE batch in flight: per-kernel durations that add up (comparable with rounds 1-4) -- the block sum the roofline fractions are computed from
-timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -o b -- python $R/bench.py --steps 1 --warmup 1 --no-cpu-baseline --in-flight 1 > $O/stats.log 2>&1
+timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -o b -- python $R/bench.py --full --steps 1 --warmup 1 --no-cpu-baseline --in-flight 1 > $O/stats.log 2>&1
 cp $(find $O/stats -name "*kernel_stats.csv" | head -1) $O/kernel_stats.csv 2>/dev/null; rm -rf $O/stats
 grep '^{' $O/stats.log > $O/bench_line_under_rocprof.json
 # the default (two batches in flight): kernels of the two lanes overlap, so per-kernel durations are NOT additive here -- kept to show what runs
-timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats2 -o b -- python $R/bench.py --steps 2 --warmup 2 --no-cpu-baseline > $O/stats2.log 2>&1
+timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats2 -o b -- python $R/bench.py --full --steps 2 --warmup 2 --no-cpu-baseline > $O/stats2.log 2>&1
 cp $(find $O/stats2 -name "*kernel_stats.csv" | head -1) $O/kernel_stats_two_lanes.csv 2>/dev/null; rm -rf $O/stats2
 grep '^{' $O/stats2.log > $O/bench_line_two_lanes_under_rocprof.json
 C0="GRBM_GUI_ACTIVE SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_INSTS_VALU_MFMA_MOPS_F16"
@@ -41,6 +41,6 @@ if len(vals) == 2:
                "source": "profiles/%s_pmc_in_situ.txt (EpiModGeluF16: fetch / write passes)" % tag}, open(o + "/fc1_traffic.json", "w"), indent=1)
     print("fc1 traffic", vals)
 PY
-timeout 300 python bench.py --steps 5 --warmup 2 2>/dev/null | grep '^{' > $O/bench_line.json
-timeout 200 python bench.py --steps 5 --warmup 2 --in-flight 1 --no-cpu-baseline 2>/dev/null | grep '^{' > $O/bench_line_one_lane.json
+timeout 300 python bench.py --full --steps 5 --warmup 2 2>/dev/null | grep '^{' > $O/bench_line.json
+timeout 200 python bench.py --full --steps 5 --warmup 2 --in-flight 1 --no-cpu-baseline 2>/dev/null | grep '^{' > $O/bench_line_one_lane.json
 head -c 600 $O/bench_line.json; echo; head -40 $O/pmc_summary.txt
