@@ -284,6 +284,20 @@ typedef struct lfm_vae_enc_weights {
 int lfm_vae_encode(const lfm_vae_enc_weights* w, void* workspace, size_t workspace_bytes, const float* x, float* moments, int N, int R,
                    int chunk, lfm_stream_t stream);
 
+/* Test entry points for the decoder's GroupNorm (32 groups, eps 1e-6), running the decoder's own host code.  Workspace (256-byte aligned):
+ * 256 B + n x 256 B (rounded up to 256) + the partial-statistics room in 8-byte pairs -- the decoder gives lfm_vae_workspace_bytes' share, and the
+ * statistics pass takes up to 512 slabs per image when n < 16 and that room allows it, else 64 (at least n x 64 x C / 4 pairs are required).
+ * lfm_vae_groupnorm_f16: y = silu?(GroupNorm(x) * gamma + beta), x, y fp16 NHWC [n, HW, C], C in {128, 256, 512}; statistics by their own pass. */
+int lfm_vae_groupnorm_f16(const void* x, void* y, const float* gamma, const float* beta, void* workspace, size_t workspace_bytes, int n, int HW, int C,
+                          int silu, lfm_stream_t stream);
+/* conv_out = conv3x3(in (nearest-2x upsampled when ups)) + bias (+ resid), then y = silu?(GroupNorm(conv_out) * gamma + beta), as a decoder resnet
+ * hands a convolution to its GroupNorm: w fp16 [Cout][9][Cin], H, W the output size.  Needs also n x 2 (H W / 256) x Cout / 4 pairs of room.
+ * *stat_slabs = the statistics slabs per image the convolution left (0: the GroupNorm ran its own pass); *stat_kernel = 1 (halo-tiled convolution),
+ * 2 (256-row implicit GEMM) or 0.  Either pointer may be NULL. */
+int lfm_vae_conv3x3_gn_f16(const void* in, const void* w, const float* bias, const void* resid, void* conv_out, void* y, const float* gamma,
+                           const float* beta, void* workspace, size_t workspace_bytes, int n, int H, int W, int Cin, int Cout, int ups, int silu,
+                           int* stat_slabs, int* stat_kernel, lfm_stream_t stream);
+
 /* u8 NHWC = trunc(clamp((x+1)/2, 0, 1) * 255) of fp32 NCHW images (test_flow_latent_ddp.py:131-135). */
 int lfm_images_to_uint8(const float* x, uint8_t* out, int N, int H, int W, lfm_stream_t stream);
 /* Same with rounding != 0: trunc(clamp((x+1)/2, 0, 1) * 255 + 0.5), the conversion of torchvision.utils.save_image that the

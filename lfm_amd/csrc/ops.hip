@@ -370,8 +370,11 @@ extern "C" int lfm_conv3x3_in_f32(const float* x_nchw, const float* w, const flo
 }
 
 // ------------------------------------------------------------------ general GroupNorm(32 groups) on NHWC fp16
-// 1) stats: one block per (image, pixel-slab) [fast path] or (group, image, pixel-slab) -> per-block PARTIAL {sum, sumsq} slots
-// 2) coef : per (n, c): folds the partials of its group in a FIXED order (deterministic: the reference is; atomics are not), then
+// 1) stats: one block per (image, pixel-slab) [fast path] or (group, image, pixel-slab) -> per-block PARTIAL {mean, M2} slots; the block's sums
+//           are of x - k, k = the slab's first value of the half-octet / group (read by every thread), so offset data (|mean| >> std) keeps its
+//           variance instead of losing it to the fp32 cancellation of sum(x^2) / n - mean^2
+// 2) coef : per (n, c): merges the partials of its group in a FIXED order (deterministic: the reference is; atomics are not), shifted by the
+//           group's first slot mean, then
 //           a = rstd*gamma*(1+scale),  b = (beta - mean*rstd*gamma)*(1+scale) + shift     (FiLM optional)
 // 3) apply: y = silu?(x*a + b), 8 channels per thread
 // GroupNorm input = the channel concat [a | b] of two NHWC tensors read in place (th.cat([h, hs.pop()], dim=1) feeding a ResBlock's first
@@ -396,6 +399,7 @@ __global__ __launch_bounds__(256) void gn_stats_general_kernel(GnIn in, float* _
   const int p0 = blockIdx.z * pix_per_block, p1 = min(p0 + pix_per_block, HW);
   const int vpp = cpg / VEC;  // vectors per pixel in this group
   const long total = (long)(p1 - p0) * vpp;
+  const float k = (float)*in.at((long)n * HW + p0, g * cpg);  // the shift: the slab's first value of the group
   float s = 0.f, q = 0.f;
   for (long e = threadIdx.x; e < total; e += 256) {
     const int p = p0 + (int)(e / vpp), v = (int)(e % vpp);
@@ -404,12 +408,12 @@ __global__ __launch_bounds__(256) void gn_stats_general_kernel(GnIn in, float* _
       const half4_t h = *(const half4_t*)ptr;
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
-        const float f = (float)h[j];
+        const float f = (float)h[j] - k;
         s += f;
         q += f * f;
       }
     } else {
-      const float f = (float)ptr[0];
+      const float f = (float)ptr[0] - k;
       s += f;
       q += f * f;
     }
@@ -422,10 +426,11 @@ __global__ __launch_bounds__(256) void gn_stats_general_kernel(GnIn in, float* _
     rq[threadIdx.x >> 6] = q;
   }
   __syncthreads();
-  if (threadIdx.x == 0) {  // slot [n][slab][g]
+  if (threadIdx.x == 0) {  // slot [n][slab][g] = {mean, M2}
     float* o = part + (((long)n * gridDim.z + blockIdx.z) * G + g) * 2;
-    o[0] = rs[0] + rs[1] + rs[2] + rs[3];
-    o[1] = rq[0] + rq[1] + rq[2] + rq[3];
+    const float ss = rs[0] + rs[1] + rs[2] + rs[3], qq = rq[0] + rq[1] + rq[2] + rq[3], rc = 1.f / (float)total / (float)VEC;
+    o[0] = k + ss * rc;
+    o[1] = fmaxf(qq - ss * ss * rc, 0.f);
   }
 }
 
@@ -439,13 +444,14 @@ __global__ __launch_bounds__(256) void gn_stats_rows_kernel(GnIn in, float* __re
   const int p0 = blockIdx.x * pix_per_block;
   const int p1 = min(p0 + pix_per_block, HW);
   float s[2] = {0.f, 0.f}, q[2] = {0.f, 0.f};
+  long XS;  // row stride of the tensor that holds this thread's octet
+  const half_t* base = in.column((long)n * HW, oct * 8, XS);
+  const float k[2] = {(float)base[(long)p0 * XS], (float)base[(long)p0 * XS + 4]};  // the shifts: pixel p0 of this slab, per half-octet
   if (prow < rows) {
-    long XS;  // row stride of the tensor that holds this thread's octet
-    const half_t* base = in.column((long)n * HW, oct * 8, XS);
     auto add = [&](const half8_t& v) {
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
-        const float f = (float)v[j];
+        const float f = (float)v[j] - k[j >> 2];
         s[j >> 2] += f;
         q[j >> 2] += f * f;
       }
@@ -473,41 +479,48 @@ __global__ __launch_bounds__(256) void gn_stats_rows_kernel(GnIn in, float* __re
       q[0] += red[2][tid + r * c8n];
       q[1] += red[3][tid + r * c8n];
     }
-    float* o = part + (((long)n * gridDim.x + blockIdx.x) * (C / 4) + tid * 2) * 2;
-    o[0] = s[0];
-    o[1] = q[0];
-    o[2] = s[1];
-    o[3] = q[1];
+    const float rc = 1.f / (float)((p1 - p0) * 4);
+    float* o = part + (((long)n * gridDim.x + blockIdx.x) * (C / 4) + tid * 2) * 2;  // {mean, M2} per half-octet
+    o[0] = k[0] + s[0] * rc;
+    o[1] = fmaxf(q[0] - s[0] * s[0] * rc, 0.f);
+    o[2] = k[1] + s[1] * rc;
+    o[3] = fmaxf(q[1] - s[1] * s[1] * rc, 0.f);
   }
 }
 
-// rows != 0: partials are [n][slab][C/4 half-octets] (fast path);  rows == 0: [n][slab][G]
+// rows != 0: partials are [n][slab][C/4 half-octets] (fast path);  rows == 0: [n][slab][G].  Slot {mean m, M2} of slab b holds
+// c = min(ppb, HW - b ppb) x (4 | cpg) values; merged shifted by the group's first slot mean K: sum (x - K) = sum c (m - K), sum (x - K)^2 = sum M2 + c (m - K)^2
 __global__ void gn_coef_kernel(const float* __restrict__ part, int slabs, int rows, const float* __restrict__ gamma, const float* __restrict__ beta,
-                               const float* __restrict__ film, long film_stride, float* __restrict__ ab, int N, int C, int cpg, float cnt,
+                               const float* __restrict__ film, long film_stride, float* __restrict__ ab, int N, int C, int cpg, int HW, int ppb,
                                float eps, int G) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= N * C) return;
   const int n = i / C, c = i - n * C, g = c / cpg;
-  float sum = 0.f, sq = 0.f;  // every channel of a group folds the same slots in the same order: identical, deterministic statistics
+  float sum = 0.f, sq = 0.f, K;  // every channel of a group folds the same slots in the same order: identical, deterministic statistics
   if (rows) {
     const int h0 = g * (cpg / 4), h1 = h0 + cpg / 4, Q = C / 4;
+    K = part[((long)n * slabs * Q + h0) * 2];
 #pragma unroll 4
     for (int b = 0; b < slabs; ++b) {
       const float* p = part + ((long)n * slabs + b) * Q * 2;
+      const float cb = (float)(4 * min(ppb, HW - b * ppb));
       for (int h = h0; h < h1; ++h) {
-        sum += p[2 * h];
-        sq += p[2 * h + 1];
+        const float d = p[2 * h] - K;
+        sum += cb * d;
+        sq += p[2 * h + 1] + cb * d * d;
       }
     }
   } else {
+    K = part[((long)n * slabs * G + g) * 2];
     for (int b = 0; b < slabs; ++b) {
       const float* p = part + (((long)n * slabs + b) * G + g) * 2;
-      sum += p[0];
-      sq += p[1];
+      const float cb = (float)(cpg * min(ppb, HW - b * ppb)), d = p[0] - K;
+      sum += cb * d;
+      sq += p[1] + cb * d * d;
     }
   }
-  const float mean = sum / cnt;
-  const float var = fmaxf(sq / cnt - mean * mean, 0.f);
+  const float cnt = (float)HW * (float)cpg, dl = sum / cnt, mean = K + dl;
+  const float var = fmaxf(sq / cnt - dl * dl, 0.f);
   const float rstd = rsqrtf(var + eps);
   float a = rstd * gamma[c], b = beta[c] - mean * rstd * gamma[c];
   if (film) {  // h = norm(h) * (1 + scale) + shift   (unet.py:229-232; film row = [scale(C) | shift(C)])
@@ -597,18 +610,23 @@ __global__ __launch_bounds__(256) void gn_fused_kernel(GnIn in, half_t* __restri
                                                        int C, int cpg, int gpb, float eps) {
   __shared__ float red[2][256];
   __shared__ float mr[2][32];
+  __shared__ float ks[32];  // the shift of every group of the block
   const int n = blockIdx.y, tid = threadIdx.x;
   const int CW = gpb * cpg, o8 = CW >> 3;          // channels / octets of this block
   const int oct = tid % o8, prow = tid / o8, rows = 256 / o8;
   const int c0 = blockIdx.x * CW + oct * 8;         // first channel of this thread's octet
   long XS;  // row stride of the tensor that holds this thread's octet
   const half_t* xb = in.column((long)n * HW, c0, XS);
+  const int gl = (oct * 8) / cpg;  // this thread's group within the block
+  // the shift: pixel 0, first channel of the group (every thread of the group reads the same value, so the partial sums below add linearly)
+  const float k = (float)*in.at((long)n * HW, blockIdx.x * CW + gl * cpg);
+  if (tid == gl * (cpg >> 3)) ks[gl] = k;  // (prow 0, the group's first octet)
   float s = 0.f, q = 0.f;
   if (prow < rows) {
     auto add = [&](const half8_t& v) {
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
-        const float f = (float)v[j];
+        const float f = (float)v[j] - k;
         s += f;
         q += f * f;
       }
@@ -635,13 +653,12 @@ __global__ __launch_bounds__(256) void gn_fused_kernel(GnIn in, half_t* __restri
         ss += red[0][r * o8 + o];
         qq += red[1][r * o8 + o];
       }
-    const float cnt = (float)HW * (float)cpg, mean = ss / cnt;
-    mr[0][tid] = mean;
-    mr[1][tid] = rsqrtf(fmaxf(qq / cnt - mean * mean, 0.f) + eps);
+    const float cnt = (float)HW * (float)cpg, dl = ss / cnt;
+    mr[0][tid] = ks[tid] + dl;  // the group's shift + the mean of x - shift
+    mr[1][tid] = rsqrtf(fmaxf(qq / cnt - dl * dl, 0.f) + eps);
   }
   __syncthreads();
   if (prow >= rows) return;
-  const int gl = (oct * 8) / cpg;
   const float mean = mr[0][gl], rstd = mr[1][gl];
   float a[8], b[8];
 #pragma unroll
@@ -705,15 +722,15 @@ static int groupnorm_impl(const GnIn& in, void* y, const float* gamma, const flo
   }
   float* part = (float*)scratch;
   float* ab = (float*)((char*)scratch + gn_part_bytes(N, C));
-  int slabs, rows;
+  int slabs, rows, ppb;
   if (cpg % 4 == 0 && C / 8 <= 256) {
-    int ppb = HW >= 4096 ? 256 : (HW >= 256 ? 64 : HW);  // (512 pixels per block at 64x64 maps left 256 blocks: one per CU; 128 made gn_coef's serial slab walk the longer kernel)
+    ppb = HW >= 4096 ? 256 : (HW >= 256 ? 64 : HW);  // (512 pixels per block at 64x64 maps left 256 blocks: one per CU; 128 made gn_coef's serial slab walk the longer kernel)
     if (cdiv(HW, ppb) > GN_MAX_SLABS) ppb = cdiv(HW, GN_MAX_SLABS);
     slabs = cdiv(HW, ppb);
     rows = 1;
     hipLaunchKernelGGL(gn_stats_rows_kernel, dim3(slabs, N), dim3(256), 0, st, in, part, HW, C, ppb);
   } else {
-    int ppb = 2048;
+    ppb = 2048;
     if (cdiv(HW, ppb) > GN_MAX_SLABS) ppb = cdiv(HW, GN_MAX_SLABS);
     slabs = cdiv(HW, ppb);
     rows = 0;
@@ -723,7 +740,7 @@ static int groupnorm_impl(const GnIn& in, void* y, const float* gamma, const flo
   }
   LFM_CHECK_LAUNCH();
   hipLaunchKernelGGL(gn_coef_kernel, dim3(cdiv((long)N * C, 256)), dim3(256), 0, st, part, slabs, rows, gamma, beta, film, film_stride, ab, N, C,
-                     cpg, (float)HW * (float)cpg, eps, G);
+                     cpg, HW, ppb, eps, G);
   LFM_CHECK_LAUNCH();
   if (C / 8 <= 256 && 256 % (C / 8) == 0) {  // a thread per channel octet
     const int pstride = 256 / (C / 8);

@@ -122,9 +122,11 @@ struct EpiConvF16 {  // out = acc + bias (+ residual)  -> fp16 NHWC
 
 // EpiConvF16 that also leaves the GroupNorm statistics of what it stores (round 3): the next layer of every resnet is a GroupNorm over exactly this
 // tensor, and its statistics pass (gn_stats_kernel) re-read it from HBM just to add it up.  In the row-major hand-over of the 256-row kernels a lane
-// owns the same eight output columns for all of its rows, so it keeps (sum, sum of squares) of the ROUNDED fp16 values per half-octet (a group is
-// >= 4 channels wide) in four registers, folds the eight lanes that share its columns at the end of the tile, and writes one fixed slot per
-// (image, 128-row slab, half-octet): part[n][slab][C / 4][2], the layout gn_finish_kernel folds in a fixed order -- deterministic, no atomics.
+// owns the same eight output columns for all of its rows, so it keeps shifted sums of the ROUNDED fp16 values per half-octet (a group is >= 4
+// channels wide) in registers, folds the eight lanes that share its columns at the end of the tile, and writes one fixed slot per (image, 128-row
+// slab, half-octet): part[n][slab][C / 4] = {mean, M2} of its 512 values, the layout gn_finish_kernel merges in a fixed order -- deterministic, no
+// atomics.  Shifted: a lane's sums are of x - k with k its own first value of the half-octet, so an offset group (|mean| >> std) keeps the
+// precision of its spread instead of cancelling sum(x^2) / n - mean^2; the finish re-shifts the eight lanes to one pivot before they are added.
 // Host-side preconditions (conv3): HW % 256 == 0 (a tile lies in one image), the 256x128 or 256x256 kernel, 16-byte-store path.
 struct EpiConvStatsF16 {
   half_t* C;
@@ -133,7 +135,8 @@ struct EpiConvStatsF16 {
   const half_t* resid;
   float* part;  // [n][slabs][ldc / 4][2]
   int HW, slabs;
-  mutable float s0, q0, s1, q1;
+  mutable float s0, q0, s1, q1;  // sums of (x - k0), (x - k0)^2 over half-octet 0, the same for half-octet 1 around k1
+  mutable float k0, k1, cnt;     // shifts (set by the first store8) and values per half-octet so far
   typedef EpiConvF16::Aux Aux;
   __device__ __forceinline__ Aux load(int m, int n) const {
     Aux a;
@@ -154,7 +157,13 @@ struct EpiConvStatsF16 {
     const half8_t h = {(half_t)(lo.x + (float)al.r.x), (half_t)(lo.y + (float)al.r.y), (half_t)(lo.z + (float)al.r.z), (half_t)(lo.w + (float)al.r.w),
                        (half_t)(hi.x + (float)ah.r.x), (half_t)(hi.y + (float)ah.r.y), (half_t)(hi.z + (float)ah.r.z), (half_t)(hi.w + (float)ah.r.w)};
     *(half8_t*)(C + (long)m * ldc + n) = h;
-    const float f0 = (float)h[0], f1 = (float)h[1], f2 = (float)h[2], f3 = (float)h[3], f4 = (float)h[4], f5 = (float)h[5], f6 = (float)h[6], f7 = (float)h[7];
+    if (cnt == 0.f) {
+      k0 = (float)h[0];
+      k1 = (float)h[4];
+    }
+    cnt += 4.f;
+    const float f0 = (float)h[0] - k0, f1 = (float)h[1] - k0, f2 = (float)h[2] - k0, f3 = (float)h[3] - k0;
+    const float f4 = (float)h[4] - k1, f5 = (float)h[5] - k1, f6 = (float)h[6] - k1, f7 = (float)h[7] - k1;
     s0 += (f0 + f1) + (f2 + f3);
     q0 += (f0 * f0 + f1 * f1) + (f2 * f2 + f3 * f3);
     s1 += (f4 + f5) + (f6 + f7);
@@ -162,17 +171,22 @@ struct EpiConvStatsF16 {
   }
   // fold the eight lanes that own the same columns and write the wave's slot: columns ncol0 + 8 (lane & 7) .. + 7 of slab `slab` of image `img`
   __device__ __forceinline__ void finish_slab(int img, int slab, int ncol0, int lane) const {
-    float a = s0, b = q0, c = s1, d = q1;
+    // re-shift every lane's sums to the shifts of lane (lane & 7): sum (x - p) = s + c d, sum (x - p)^2 = q + d (2 s + c d) with d = k - p
+    const float p0 = __shfl(k0, lane & 7, 64), p1 = __shfl(k1, lane & 7, 64);
+    const float d0 = k0 - p0, d1 = k1 - p1;
+    float a = s0 + cnt * d0, b = q0 + d0 * (2.f * s0 + cnt * d0), c = s1 + cnt * d1, d = q1 + d1 * (2.f * s1 + cnt * d1), t = cnt;
 #pragma unroll
     for (int o = 8; o < 64; o <<= 1) {  // the eight lanes lane & 7, + 8, .., + 56 own the same columns
       a += __shfl_xor(a, o, 64);
       b += __shfl_xor(b, o, 64);
       c += __shfl_xor(c, o, 64);
       d += __shfl_xor(d, o, 64);
+      t += __shfl_xor(t, o, 64);
     }
-    if (lane < 8) {
+    if (lane < 8) {  // {mean, M2} per half-octet
       float* o = part + (((long)img * slabs + slab) * (ldc >> 2) + ((ncol0 + lane * 8) >> 2)) * 2;
-      *(f32x4*)o = (f32x4){a, b, c, d};
+      const float r = 1.f / t;
+      *(f32x4*)o = (f32x4){p0 + a * r, fmaxf(b - a * a * r, 0.f), p1 + c * r, fmaxf(d - c * c * r, 0.f)};
     }
   }
   __device__ __forceinline__ void finish_tile(int m0, int n0, int g, int wn, int lane) const {
@@ -298,8 +312,11 @@ __global__ __launch_bounds__(256) void vae_conv_in_kernel(const float* __restric
 
 // ------------------------------------------------------------------ GroupNorm(32 groups, eps 1e-6) on NHWC fp16
 // Two-stage, deterministic statistics (the reference is deterministic; float atomics are not): every block folds its slab of pixels
-// into per-half-octet partial {sum, sumsq} slots part[n][slab][C/4], a small second kernel folds the slabs and the half-octets of a
-// group in a fixed order into stats[n][g]; apply fuses SiLU.
+// into per-half-octet partial {mean, M2} slots part[n][slab][C/4], a small second kernel merges the slabs and the half-octets of a
+// group in a fixed order into stats[n][g] = {mean, rstd}; apply fuses SiLU.
+// Offset data: a slab's sums are of x - k, k = the slab's first value of the half-octet (every thread of the octet reads the same k), and the
+// merge is shifted the same way, so a group whose mean is hundreds of standard deviations keeps its variance (the unshifted
+// sum(x^2) / n - mean^2 loses it to fp32 cancellation).
 // Block = 256 threads over a slab of pixels; thread t owns channel-octet (t % (C/8)) and strides over pixels.
 #define VGN_MAX_SLABS 64
 __global__ __launch_bounds__(256) void gn_stats_kernel(const half_t* __restrict__ x, float* __restrict__ part, int HW, int C,
@@ -311,11 +328,12 @@ __global__ __launch_bounds__(256) void gn_stats_kernel(const half_t* __restrict_
   const int p1 = min(p0 + pix_per_block, HW);
   float s[2] = {0.f, 0.f}, q[2] = {0.f, 0.f};  // per half-octet (4 channels): a group is >= 4 channels wide
   const half_t* base = x + (long)n * HW * C + oct * 8;
+  const float k[2] = {(float)base[(long)p0 * C], (float)base[(long)p0 * C + 4]};  // the shifts: pixel p0 of this slab
   for (int p = p0 + prow; p < p1; p += pstride) {
     const half8_t v = *(const half8_t*)(base + (long)p * C);
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
-      const float f = (float)v[j];
+      const float f = (float)v[j] - k[j >> 2];
       s[j >> 2] += f;
       q[j >> 2] += f * f;
     }
@@ -325,39 +343,47 @@ __global__ __launch_bounds__(256) void gn_stats_kernel(const half_t* __restrict_
   red[2][tid] = q[0];
   red[3][tid] = q[1];
   __syncthreads();
-  if (tid < c8n) {  // fold the pixel-rows of this channel octet, then one atomic pair per half-octet
+  if (tid < c8n) {  // fold the pixel-rows of this channel octet, then one {mean, M2} slot per half-octet
     for (int r = 1; r < pstride; ++r) {
       s[0] += red[0][tid + r * c8n];
       s[1] += red[1][tid + r * c8n];
       q[0] += red[2][tid + r * c8n];
       q[1] += red[3][tid + r * c8n];
     }
+    const float rc = 1.f / (float)((p1 - p0) * 4);
     float* o = part + (((long)n * gridDim.x + blockIdx.x) * (C / 4) + tid * 2) * 2;
-    o[0] = s[0];
-    o[1] = q[0];
-    o[2] = s[1];
-    o[3] = q[1];
+    o[0] = k[0] + s[0] * rc;
+    o[1] = fmaxf(q[0] - s[0] * s[0] * rc, 0.f);
+    o[2] = k[1] + s[1] * rc;
+    o[3] = fmaxf(q[1] - s[1] * s[1] * rc, 0.f);
   }
 }
 // one WAVE per (image, group): lane l folds slabs l, l + 64, ... in order, then a fixed-tree wave sum (deterministic).  (One thread per
 // (image, group) walking all slabs serially took 75 us once the convolution epilogues started to deliver 512 slabs per image.)
-__global__ __launch_bounds__(256) void gn_finish_kernel(const float* __restrict__ part, float* __restrict__ stats, int slabs, int C, int total) {
+// Slot {mean m, M2} of slab b holds c = 4 min(ppb, HW - b ppb) values; the merge is shifted by the group's first slot mean K:
+// sum (x - K) = sum c (m - K),  sum (x - K)^2 = sum M2 + c (m - K)^2 -- linear, so the lanes and the wave tree add as before.
+__global__ __launch_bounds__(256) void gn_finish_kernel(const float* __restrict__ part, float* __restrict__ stats, int slabs, int ppb, int HW, int C,
+                                                        int total) {
   const int i = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;  // (n, g)
   if (i >= total) return;
   const int n = i >> 5, g = i & 31, hpg = C / 128;  // half-octets per group = (C/32)/4
+  const float K = part[((long)n * slabs * (C / 4) + g * hpg) * 2];
   float sum = 0.f, sq = 0.f;
   for (int b = lane; b < slabs; b += 64) {
     const float* p = part + (((long)n * slabs + b) * (C / 4) + g * hpg) * 2;
+    const float c = (float)(4 * min(ppb, HW - b * ppb));
     for (int h = 0; h < hpg; ++h) {
-      sum += p[2 * h];
-      sq += p[2 * h + 1];
+      const float d = p[2 * h] - K;
+      sum += c * d;
+      sq += p[2 * h + 1] + c * d * d;
     }
   }
   sum = wave_sum(sum);
   sq = wave_sum(sq);
   if (lane == 0) {
-    stats[(long)i * 2] = sum;
-    stats[(long)i * 2 + 1] = sq;
+    const float cnt = (float)HW * (float)(C / 32), dl = sum / cnt;
+    stats[(long)i * 2] = K + dl;
+    stats[(long)i * 2 + 1] = rsqrtf(fmaxf(sq / cnt - dl * dl, 0.f) + 1e-6f);
   }
 }
 
@@ -371,14 +397,12 @@ __global__ __launch_bounds__(256) void gn_apply_kernel(const half_t* __restrict_
                                                        int pix_per_block) {
   const int n = blockIdx.y, c8n = C / 8, cpg = C / 32, tid = threadIdx.x;
   const int oct = tid % c8n, prow = tid / c8n, pstride = 256 / c8n;
-  const float cnt = (float)HW * (float)cpg;
   float mean[2], rstd[2];
 #pragma unroll
-  for (int hh = 0; hh < 2; ++hh) {
+  for (int hh = 0; hh < 2; ++hh) {  // stats[n][g] = {mean, rstd} (gn_finish_kernel)
     const int g = (oct * 8 + hh * 4) / cpg;
-    mean[hh] = stats[((long)n * 32 + g) * 2] / cnt;
-    const float var = fmaxf(stats[((long)n * 32 + g) * 2 + 1] / cnt - mean[hh] * mean[hh], 0.f);
-    rstd[hh] = rsqrtf(var + 1e-6f);
+    mean[hh] = stats[((long)n * 32 + g) * 2];
+    rstd[hh] = stats[((long)n * 32 + g) * 2 + 1];
   }
   const f32x4 g0 = *(const f32x4*)(gamma + oct * 8), g1 = *(const f32x4*)(gamma + oct * 8 + 4);
   const f32x4 b0 = *(const f32x4*)(beta + oct * 8), b1 = *(const f32x4*)(beta + oct * 8 + 4);
@@ -427,11 +451,11 @@ static inline size_t a256(size_t v) { return (v + 255) / 256 * 256; }
 
 struct VaeWs {
   half_t *b0, *b1, *b2, *b3;  // four ping-pong activation buffers of the largest size
-  float* stats;               // [chunk, 32, 2]
-  float* part;                // [chunk, VGN_MAX_SLABS, 128, 2] partial sums of the two-stage GroupNorm statistics
+  float* stats;               // [chunk, 32, 2] {mean, rstd}
+  float* part;                // [chunk, VGN_MAX_SLABS, 128, 2] partial {mean, M2} of the two-stage GroupNorm statistics
   half_t* zeros;              // 256 B
   float* S;                   // [chunk, T, T] scores
-  size_t part_pairs;          // capacity of `part` in (sum, sum of squares) pairs
+  size_t part_pairs;          // capacity of `part` in {mean, M2} pairs
   size_t total;
 };
 
@@ -479,7 +503,7 @@ extern "C" size_t lfm_vae_workspace_bytes(int R, int chunk) {
 static int gn(const half_t* x, half_t* y, float* stats, float* part, const float* g, const float* b, int n, int HW, int C, bool silu,
               hipStream_t st, int ready_slabs = 0, size_t part_pairs = 0) {
   if (C % 128 || 256 % (C / 8) || C > 512) return LFM_ERR_SHAPE;  // groups of >= 4 channels, octet-per-thread mapping
-  int slabs = ready_slabs;
+  int slabs = ready_slabs, ppb = ready_slabs ? HW / ready_slabs : 0;  // pixels per slab (the convolution epilogues: 128)
   if (!ready_slabs) {
     // slabs per image: VGN_MAX_SLABS when the images fill the chip; a FEW images (--measure_time decodes ONE) get up to 512 -- 64 blocks walked a 256x256x128 map in
     // 64 dependent 16-byte loads per thread, 68 us per GroupNorm and 38 % of the batch-1 decode (profiles/r06_latency_mode.txt) -- as far as `part` has room
@@ -492,14 +516,14 @@ static int gn(const half_t* x, half_t* y, float* stats, float* part, const float
       if (cap > 512) cap = 512;
       if (cap < VGN_MAX_SLABS) cap = VGN_MAX_SLABS;
     }
-    int ppb = 1024;
+    ppb = 1024;
     if (cap > VGN_MAX_SLABS) ppb = cdiv(HW, cap) > 64 ? cdiv(HW, cap) : 64;  // >= 64 pixels per block: at least a few loads per thread
     if (cdiv(HW, ppb) > cap) ppb = cdiv(HW, cap);
     slabs = cdiv(HW, ppb);
     hipLaunchKernelGGL(gn_stats_kernel, dim3(slabs, n), dim3(256), 0, st, x, part, HW, C, ppb);
     LFM_CHECK_LAUNCH();
   }
-  hipLaunchKernelGGL(gn_finish_kernel, dim3(cdiv(n * 32, 4)), dim3(256), 0, st, part, stats, slabs, C, n * 32);
+  hipLaunchKernelGGL(gn_finish_kernel, dim3(cdiv(n * 32, 4)), dim3(256), 0, st, part, stats, slabs, ppb, HW, C, n * 32);
   LFM_CHECK_LAUNCH();
   const int app = HW >= 4096 ? 256 : (HW >= 256 ? 64 : HW);  // pixels per block: 16 .. 4 chunks per thread at 128 .. 512 channels
   if (silu) hipLaunchKernelGGL(gn_apply_kernel<true>, dim3(cdiv(HW, app), n), dim3(256), 0, st, x, y, stats, g, b, HW, C, app);
@@ -509,21 +533,26 @@ static int gn(const half_t* x, half_t* y, float* stats, float* part, const float
 }
 
 // out[n,H,W,Cout] = conv3x3(in (optionally nearest-2x upsampled)) + bias (+ resid)
-// *stat_slabs (optional): set to the number of partial-sum slabs per image this convolution left in `part` for the GroupNorm that follows, or 0
+// *stat_slabs (optional): set to the number of partial-sum slabs per image this convolution left in `part` for the GroupNorm that follows, or 0;
+// *stat_kernel (optional): which kernel left them -- 1 the halo-tiled convolution, 2 a 256-row implicit GEMM, 0 none
 static int conv3(const half_t* in, const half_t* w, const float* b, const half_t* resid, half_t* out, const half_t* zeros, int n, int H, int W,
-                 int Cin, int Cout, bool ups, hipStream_t st, float* part = nullptr, int* stat_slabs = nullptr) {
+                 int Cin, int Cout, bool ups, hipStream_t st, float* part = nullptr, int* stat_slabs = nullptr, int* stat_kernel = nullptr) {
   if (Cin % 64 || Cout % 4) return LFM_ERR_SHAPE;
   const int M = n * H * W;
   if (stat_slabs) *stat_slabs = 0;
+  if (stat_kernel) *stat_kernel = 0;
   const int HW = H * W, kern = gemm_auto_choice(M, Cout, 9 * Cin);
   // every 3x3 convolution on a 16-aligned map: the halo-tiled direct kernel (conv_halo_kernel.h; 1.1-1.2 PFLOP/s where the implicit GEMM reaches
   // 0.65-1.05, profiles/r03_halo_conv_probe.txt); flag 8388608: the implicit GEMM instead (A/B)
   if (lfm_gemm_selected() == 0 && !(((uintptr_t)out | (uintptr_t)resid) & 15) && !(lfm_gemm_debug_flags() & 8388608)) {
     int rc;
     if (part && stat_slabs && (HW % 256) == 0 && !(lfm_gemm_debug_flags() & 4194304)) {
-      EpiConvStatsF16 es{out, Cout, b, resid, part, HW, 2 * (HW / 256), 0.f, 0.f, 0.f, 0.f};
+      EpiConvStatsF16 es{out, Cout, b, resid, part, HW, 2 * (HW / 256), 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
       rc = ups ? launch_conv3x3_halo<1>(in, zeros, w, n, H, W, Cin, Cout, es, st) : launch_conv3x3_halo<0>(in, zeros, w, n, H, W, Cin, Cout, es, st);
-      if (rc == 0) *stat_slabs = es.slabs;
+      if (rc == 0) {
+        *stat_slabs = es.slabs;
+        if (stat_kernel) *stat_kernel = 1;
+      }
     } else {
       EpiConvF16 ep{out, Cout, b, resid};
       rc = ups ? launch_conv3x3_halo<1>(in, zeros, w, n, H, W, Cin, Cout, ep, st) : launch_conv3x3_halo<0>(in, zeros, w, n, H, W, Cin, Cout, ep, st);
@@ -533,13 +562,64 @@ static int conv3(const half_t* in, const half_t* w, const float* b, const half_t
   if (part && stat_slabs && (HW % 256) == 0 && (kern == 4 || kern == 5) && (Cout % (kern == 4 ? 128 : 256)) == 0 && (Cout % 128) == 0 &&
       !(((uintptr_t)out | (uintptr_t)resid) & 15) && !(lfm_gemm_debug_flags() & (1024 | 4194304))) {  // flag 4194304: the separate statistics pass (A/B)
     *stat_slabs = 2 * (HW / 256);
-    EpiConvStatsF16 es{out, Cout, b, resid, part, HW, *stat_slabs, 0.f, 0.f, 0.f, 0.f};
+    if (stat_kernel) *stat_kernel = 2;
+    EpiConvStatsF16 es{out, Cout, b, resid, part, HW, *stat_slabs, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     if (ups) return launch_gemm_auto(ASrcConv3x3<1>{in, zeros, H, W, Cin, M, 0, 0}, w, 9L * Cin, M, Cout, 9 * Cin, es, st);
     return launch_gemm_auto(ASrcConv3x3<0>{in, zeros, H, W, Cin, M, 0, 0}, w, 9L * Cin, M, Cout, 9 * Cin, es, st);
   }
   EpiConvF16 epi{out, Cout, b, resid};
   if (ups) return launch_gemm_auto(ASrcConv3x3<1>{in, zeros, H, W, Cin, M, 0, 0}, w, 9L * Cin, M, Cout, 9 * Cin, epi, st);
   return launch_gemm_auto(ASrcConv3x3<0>{in, zeros, H, W, Cin, M, 0, 0}, w, 9L * Cin, M, Cout, 9 * Cin, epi, st);
+}
+
+// ---- test entry points: the decoder's GroupNorm (gn, its own statistics pass) and the conv3 -> gn hand-over, on the decoder's host code.
+// Workspace: [zeros 256 B][stats n x 32 x {mean, rstd}][part: the rest, in {mean, M2} pairs] (the decoder sizes part by lfm_vae_workspace_bytes;
+// gn takes as many statistics slabs as part has room for, as in the decoder).
+static int vae_test_carve(void* workspace, size_t bytes, int n, half_t*& zeros, float*& stats, float*& part, size_t& part_pairs) {
+  if ((uintptr_t)workspace & 255) return LFM_ERR_ALIGN;
+  const size_t head = 256 + a256((size_t)n * 64 * 4);
+  if (bytes < head) return LFM_ERR_WORKSPACE;
+  zeros = (half_t*)workspace;
+  stats = (float*)((char*)workspace + 256);
+  part = (float*)((char*)workspace + head);
+  part_pairs = (bytes - head) / 8;
+  return LFM_OK;
+}
+
+extern "C" int lfm_vae_groupnorm_f16(const void* x, void* y, const float* gamma, const float* beta, void* workspace, size_t workspace_bytes, int n,
+                                     int HW, int C, int silu, lfm_stream_t stream) {
+  if (!x || !y || !gamma || !beta || !workspace) return LFM_ERR_ARG;
+  if (n <= 0 || HW <= 0 || C <= 0) return LFM_ERR_SHAPE;
+  if (((uintptr_t)x | (uintptr_t)y) & 15) return LFM_ERR_ALIGN;
+  half_t* zeros;
+  float *stats, *part;
+  size_t pairs;
+  RC(vae_test_carve(workspace, workspace_bytes, n, zeros, stats, part, pairs));
+  if (pairs < (size_t)n * VGN_MAX_SLABS * (C / 4)) return LFM_ERR_WORKSPACE;
+  return gn((const half_t*)x, (half_t*)y, stats, part, gamma, beta, n, HW, C, silu != 0, (hipStream_t)stream, 0, pairs);
+}
+
+extern "C" int lfm_vae_conv3x3_gn_f16(const void* in, const void* w, const float* bias, const void* resid, void* conv_out, void* y, const float* gamma,
+                                      const float* beta, void* workspace, size_t workspace_bytes, int n, int H, int W, int Cin, int Cout, int ups,
+                                      int silu, int* stat_slabs, int* stat_kernel, lfm_stream_t stream) {
+  if (!in || !w || !bias || !conv_out || !y || !gamma || !beta || !workspace) return LFM_ERR_ARG;
+  if (n <= 0 || H <= 0 || W <= 0 || (ups && ((H | W) & 1))) return LFM_ERR_SHAPE;
+  if (((uintptr_t)in | (uintptr_t)w | (uintptr_t)resid | (uintptr_t)conv_out | (uintptr_t)y) & 15) return LFM_ERR_ALIGN;
+  half_t* zeros;
+  float *stats, *part;
+  size_t pairs;
+  RC(vae_test_carve(workspace, workspace_bytes, n, zeros, stats, part, pairs));
+  const size_t conv_pairs = (size_t)n * 2 * (H * W / 256) * (Cout / 4), stat_pairs = (size_t)n * VGN_MAX_SLABS * (Cout / 4);
+  if (pairs < (conv_pairs > stat_pairs ? conv_pairs : stat_pairs)) return LFM_ERR_WORKSPACE;
+  hipStream_t st = (hipStream_t)stream;
+  if (lfm_zero_async(zeros, 256, st)) return LFM_ERR_LAUNCH;
+  int slabs = 0, kern = 0;
+  RC(conv3((const half_t*)in, (const half_t*)w, bias, (const half_t*)resid, (half_t*)conv_out, zeros, n, H, W, Cin, Cout, ups != 0, st, part, &slabs,
+           &kern));
+  RC(gn((const half_t*)conv_out, (half_t*)y, stats, part, gamma, beta, n, H * W, Cout, silu != 0, st, slabs, pairs));
+  if (stat_slabs) *stat_slabs = slabs;
+  if (stat_kernel) *stat_kernel = kern;
+  return LFM_OK;
 }
 
 // x_slabs: in = partial-sum slabs per image already in ws.part for x (0 = none), out = the same for the result

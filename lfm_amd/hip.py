@@ -163,6 +163,10 @@ def lib():
     L.lfm_attention_small_f16.argtypes = [V, V, I, I, I, I, V]
     L.lfm_time_embed.restype = I
     L.lfm_time_embed.argtypes = [V, I, V, V, V, V, V, V, I, V, V, V, I, I, I, V]
+    L.lfm_vae_groupnorm_f16.restype = I
+    L.lfm_vae_groupnorm_f16.argtypes = [V, V, V, V, V, C.c_size_t, I, I, I, I, V]
+    L.lfm_vae_conv3x3_gn_f16.restype = I
+    L.lfm_vae_conv3x3_gn_f16.argtypes = [V, V, V, V, V, V, V, V, V, C.c_size_t, I, I, I, I, I, I, I, C.POINTER(C.c_int), C.POINTER(C.c_int), V]
     _lib = L
     return L
 
