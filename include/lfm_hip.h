@@ -160,8 +160,12 @@ int lfm_gemm_qkv_f16(const void* A, long lda, const void* W, long ldw, void* Q, 
  * 128x128, 4 = force 256x128, 5 = force 256x256 with eight waves, 6 = force 256x256 with one wave per SIMD (128x128 wave tiles; row-major A
  * operands, K % 64 == 0 -- other cases take kernel 5); 7 / 8 = lfm_gemm_f16 (epilogues 0-2, <= 256 rows) on the latency-mode kernels -- 64x64 tiles /
  * all rows x 16 columns -- which refuse other shapes, every other entry point treats them as 1 (other values are refused); | flags << 4 =
- * ablation / A-B switches.  For measurement and parity tests. */
+ * ablation / A-B switches (LFM_DBG_*, named one by one in lfm_amd/csrc/debug_flags.h).  For measurement and parity tests. */
 int lfm_gemm_select(int which);
+/* Which kernel (1, 4, 5 or 6) a GEMM of this shape runs on under the calling thread's current selection.  caps: bit 0 = the caller's instantiation can
+ * take kernel 6 (row-major A operand, an epilogue without per-lane tile accumulators), bit 1 = the operands fit the 32-bit buffer offsets of the 256x256
+ * kernels (below 2^31 elements).  No launch; usable without a GPU. */
+int lfm_gemm_plan(int M, int N, int K, int batch, int caps);
 
 /* Measurement only: when enabled, every eager lfm_dit_forward records a HIP event pair around each block's fc1 GEMM (the
  * dominant kernel); lfm_profile_fc1_read synchronises and returns the per-launch durations in ms (bench.py roofline row).  One stream at a time:
@@ -205,10 +209,10 @@ int lfm_clock_probe(int blocks, int iters, unsigned long long* ticks_out, lfm_st
 
 /* ---- measurement-only entry points: exported by LFM_MEASURE builds of the library only (LFM_MEASURE=1 python -m lfm_amd._build; tools/README.md) */
 #ifdef LFM_MEASURE
-/* Measurement only: s_memtime stamps written by the quadrant-phased GEMM (select flag 2) after every barrier of block 0,
+/* Measurement only: s_memtime stamps written by the quadrant-phased GEMM (select flag LFM_DBG_TRACE_GEMM, csrc/debug_flags.h) after every barrier of block 0,
  * wave groups 0 and 1; host_out receives 2 x n_per_group values. */
 int lfm_gemm_trace_read(unsigned long long* host_out, int n_per_group);
-/* Measurement only: s_memtime stamps of the attention kernel's trace build (select flags 33554432 | 67108864; slot map in csrc/attention_kernel.h). */
+/* Measurement only: s_memtime stamps of the attention kernel's trace build (select field LFM_DBG_ATT_MODE = 3, csrc/debug_flags.h; slot map in csrc/attention_kernel.h). */
 int lfm_attention_trace_read(unsigned long long* host_out, int n);
 /* Measurement only (LFM_MEASURE builds, same trace build): per attention workgroup {HW_ID | XCC_ID << 32, start, loads landed, end} -- which CU it ran on
  * and when; host_out receives 4 x n_wg values (n_wg <= 2048). */

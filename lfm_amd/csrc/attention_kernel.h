@@ -19,8 +19,6 @@
 #include "gemm_kernel.h"
 #include "attention_stream_kernel.h"
 
-int lfm_gemm_debug_flags();
-int lfm_attention_stream_enabled();  // LFM_OPT_ATTENTION_STREAM (dit.hip)
 
 // MODE 3 (measurement only): s_memtime stamps of wave 0 of the first workgroup (slots 0..31) and of the last one (32..63), read back with
 // lfm_attention_trace_read.  Slots: 0 start, 1 all DMAs / Q loads issued, 2 K and Q landed (first barrier), 3 + 4 k + {0: S(next) issued,
@@ -398,15 +396,15 @@ static int attention_launch(const half_t* Q, const half_t* K, const half_t* Vt, 
   dim3 grid(heads, batch);
   // Rounds 1-3: 8 waves x 32 queries (4 waves/SIMD) measured 44.3 us vs 40.2 us for 4 waves x 64 queries (two 8-byte V^T reads per fragment then).
   // Round 4: with the V^T operand a single conflict-free ds_read_b128 (vt_pos) the balance flipped -- 8 waves x 32 queries (126 VGPRs: four waves per
-  // SIMD) 35.7 us, 4 waves x 64 queries (228 VGPRs: two) 38.9 us -- so the narrow shape is the default; flag 256 selects the wide one (A/B)
-  const bool narrow = T == 256 && !(lfm_gemm_debug_flags() & 256);
-  [[maybe_unused]] const int mode = (lfm_gemm_debug_flags() >> 25) & 3;  // flags 33554432 / 67108864 / both: the measurement-only variants MODE 1 / 2 / 3 (hd 64, 256 tokens)
+  // SIMD) 35.7 us, 4 waves x 64 queries (228 VGPRs: two) 38.9 us -- so the narrow shape is the default; flag ATT_WIDE selects the wide one (A/B)
+  const bool narrow = T == 256 && !(lfm_gemm_debug_flags() & LFM_DBG_ATT_WIDE);
+  [[maybe_unused]] const int mode = (lfm_gemm_debug_flags() >> LFM_DBG_ATT_MODE_SHIFT) & LFM_DBG_ATT_MODE_MASK;  // the measurement-only variants MODE 1 / 2 / 3 (hd 64, 256 tokens)
 #ifdef LFM_MEASURE
   if (mode && hd == 64 && T == 256 && narrow && lfm_attention_stream_enabled() && batch * heads > 64) {  // the streamed kernel's phase split
     const int rc = attention_stream_launch(Q, K, Vt, O, batch, heads, st, mode);
     if (rc <= 0) return rc;
   }
-  if (mode && hd == 64 && T == 256 && narrow) {  // the shipped shape (8 waves x 32 queries); flag 256 + mode = the wide one below
+  if (mode && hd == 64 && T == 256 && narrow) {  // the shipped shape (8 waves x 32 queries); ATT_WIDE + mode = the wide one below
     static bool set = false;
     if (!set) {
       (void)hipFuncSetAttribute((const void*)dit_attention_kernel<256, 1, 64, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 256 * 64 * 4);

@@ -104,7 +104,7 @@ __device__ __forceinline__ void att_softmax_block(const f32x16& S, bool first, f
 static __device__ unsigned long long att_trace[ATT_TRACE_SLOTS];
 static __device__ unsigned long long att_wg_trace[ATT_WG_TRACE][4];
 #endif
-// MODE (measurement builds only, flags 33554432 / 67108864 like the per-item kernel): 1 = memory only (LDS-DMA ring, waits, barriers, Q loads, O stores; no MFMA / softmax),
+// MODE (measurement builds only, the ATT_MODE field of the flags, like the per-item kernel): 1 = memory only (LDS-DMA ring, waits, barriers, Q loads, O stores; no MFMA / softmax),
 // 2 = compute only (every LDS-DMA and Q load out of range: no operand traffic), 3 = s_memtime trace (attention_kernel.h: att_trace = wave 0 of the first / last
 // workgroup: slot 0 start, 1 prologue issued, 2 + 14 i + 3 j + {0 before the wait, 1 after the wait, 2 after the barrier} for stage j of the workgroup's item i < 2,
 // 14 + 14 i key loop done, 15 + 14 i stores issued; att_wg_trace = {HW_ID | XCC_ID << 32, start, first barrier passed, end} per workgroup)

@@ -235,7 +235,7 @@ static inline int launch_conv3x3_halo(const half_t* in, const half_t* zeros, con
   if ((long)n * H * W >= (1L << 31) || (long)H * W * Cin >= (1L << 31)) return 1;
   const int tiles_x = W / 16, tiles_per_img = tiles_x * (H / 16), nb = Cout / 128;
   const long total = (long)n * tiles_per_img * nb;
-  if ((total < 256 && !(lfm_gemm_debug_flags() & 16777216)) || total >= (1L << 31)) return 1;  // flag 16777216: small problems too (parity tests)
+  if ((total < 256 && !(lfm_gemm_debug_flags() & LFM_DBG_CONV_HALO_SMALL)) || total >= (1L << 31)) return 1;  // flag: small problems too (parity tests)
   if (((uintptr_t)in | (uintptr_t)Wt | (uintptr_t)zeros) & 15) return LFM_ERR_ALIGN;
   static lfm_device_mask attr_set{0};  // one bit per device: the attribute is per (function, device)
   const unsigned long long dbit = lfm_device_bit();
@@ -352,7 +352,7 @@ static inline int launch_conv3x3_halo_out(const half_t* in, const half_t* zeros,
   if ((long)n * H * W >= (1L << 31) || (long)H * W * Cin >= (1L << 31)) return 1;
   const int tiles_x = W / 16, tiles_per_img = tiles_x * (H / 16);
   const long total = (long)n * tiles_per_img;
-  if ((total < 256 && !(lfm_gemm_debug_flags() & 16777216)) || total >= (1L << 31)) return 1;
+  if ((total < 256 && !(lfm_gemm_debug_flags() & LFM_DBG_CONV_HALO_SMALL)) || total >= (1L << 31)) return 1;
   if (((uintptr_t)in | (uintptr_t)w4 | (uintptr_t)zeros) & 15) return LFM_ERR_ALIGN;
   static lfm_device_mask attr_set{0};
   const unsigned long long dbit = lfm_device_bit();

@@ -11,34 +11,42 @@
 // Library-wide switches = process-wide DEFAULTS (lfm_gemm_select, lfm_set_option); a call that carries its own values (lfm_dit_call.fold_ln /
 // .gemm_select, ABI 4) overrides them in THREAD-LOCAL state for the duration of lfm_dit_forward: every launcher reads the effective value on the
 // calling thread while it enqueues, so two host threads (or two lanes in flight with different settings) never see each other's choice.
-static int g_gemm_sel_default = 0, g_gemm_dbg_default = 0;
-static int g_opt_fold_ln_default = 1;
+// The defaults are written by one thread while others enqueue: relaxed atomics, each value stands on its own (as lfm_device_mask, common.h).
+typedef std::atomic<int> Opt;
+static inline int opt_get(const Opt& o) { return o.load(std::memory_order_relaxed); }
+static inline void opt_set(Opt& o, int v) { o.store(v, std::memory_order_relaxed); }
+static struct {
+  Opt gemm_sel{0}, gemm_dbg{0};  // lfm_gemm_select: kernel, ablation flags (debug_flags.h)
+  Opt fold_ln{1};                // LFM_OPT_FOLD_LN
+  Opt v6{0};                     // LFM_OPT_GEMM_V6
+  Opt skinny{1};  // LFM_OPT_SKINNY_GEMM: the batch-1 DiT linears on their own kernels (1: 64x64 tiles where the image has whole 64-token tiles,
+                  // gemm_sq64_kernel.h, else all rows x 16 columns, gemm_skinny_kernel.h; 2: always the latter; 0: the rounds 2-4 split-K path)
+  Opt stagger{0};     // measurement builds, lfm_set_option key 3
+  Opt att_stream{1};  // LFM_OPT_ATTENTION_STREAM: 256 tokens x head_dim 64 with more than 64 (image, head) items on the persistent streamed kernel
+  Opt fused_qkv{1};   // LFM_OPT_FUSED_QKV_ATTENTION: folded path at 256 tokens x head_dim 64: QKV projection + attention in one kernel (qkv_attention_kernel.h)
+} g_def;
 static thread_local int tl_sel_set = 0, tl_gemm_sel = 0, tl_gemm_dbg = 0;  // per-call kernel selection active on this thread
 static thread_local int tl_fold = 0;                                       // 0: default, LFM_CALL_OFF, LFM_CALL_ON
-#define g_gemm_sel (tl_sel_set ? tl_gemm_sel : g_gemm_sel_default)
-#define g_gemm_dbg (tl_sel_set ? tl_gemm_dbg : g_gemm_dbg_default)
-#define g_opt_fold_ln (tl_fold ? (tl_fold == LFM_CALL_ON ? 1 : 0) : g_opt_fold_ln_default)
-int lfm_gemm_selected() { return g_gemm_sel; }
-int lfm_gemm_debug_flags() { return g_gemm_dbg; }
-int lfm_gemm_selected_v1_ok() { return g_gemm_sel < 2 && !(g_gemm_dbg & 512); }  // flag 512: split-K off (A/B)
-// flag 4096: never pick v4 for 256-wide-capable shapes; flag 8192: always (A/B of the automatic choice)
-int lfm_gemm_prefers_v4(int M, int N, int K) {
+static inline int gemm_sel() { return tl_sel_set ? tl_gemm_sel : opt_get(g_def.gemm_sel); }
+static inline int gemm_dbg() { return tl_sel_set ? tl_gemm_dbg : opt_get(g_def.gemm_dbg); }
+static inline int opt_fold_ln() { return tl_fold ? (tl_fold == LFM_CALL_ON ? 1 : 0) : opt_get(g_def.fold_ln); }
+int lfm_gemm_selected() { return gemm_sel(); }
+int lfm_gemm_debug_flags() { return gemm_dbg(); }
+int lfm_gemm_selected_v1_ok() { return gemm_sel() < 2 && !(gemm_dbg() & LFM_DBG_GEMM_NO_SPLITK); }
+int lfm_gemm_prefers_v4(int M, int N, int K) {  // no shape today: only the A/B flags of the automatic choice
   (void)M;
   (void)N;
   (void)K;
-  if (g_gemm_dbg & 4096) return 0;
-  if (g_gemm_dbg & 8192) return 1;
+  if (gemm_dbg() & LFM_DBG_GEMM_NEVER_V4) return 0;
+  if (gemm_dbg() & LFM_DBG_GEMM_ALWAYS_V4) return 1;
   return 0;
 }
-static int g_opt_v6 = 0;
-int lfm_gemm_v6_default() { return g_opt_v6; }
-static int g_opt_skinny = 1;  // LFM_OPT_SKINNY_GEMM: the batch-1 DiT linears on their own kernels (1: 64x64 tiles where the image has whole 64-token tiles,
-                               // gemm_sq64_kernel.h, else all rows x 16 columns, gemm_skinny_kernel.h; 2: always the latter; 0: the rounds 2-4 split-K path)
-static int g_stagger = 0;
-int lfm_stagger_ticks() { return g_stagger; }
-static int g_opt_att_stream = 1;  // LFM_OPT_ATTENTION_STREAM: 256 tokens x head_dim 64 with more than 64 (image, head) items on the persistent streamed kernel
-int lfm_attention_stream_enabled() { return g_opt_att_stream; }
-static int g_opt_fused_qkv = 1;  // LFM_OPT_FUSED_QKV_ATTENTION: folded path at 256 tokens x head_dim 64: QKV projection + attention in one kernel (qkv_attention_kernel.h)
+int lfm_gemm_v6_default() { return opt_get(g_def.v6); }
+int lfm_stagger_ticks() { return opt_get(g_def.stagger); }
+int lfm_attention_stream_enabled() { return opt_get(g_def.att_stream); }
+// Which kernel launch_gemm_auto runs for a shape under the calling thread's selection (host only, no GPU needed): caps bit 0 = the instantiation can take
+// kernel 6 (row-major A, no per-lane tile accumulators in the epilogue), bit 1 = the operands fit 32-bit buffer offsets.
+extern "C" int lfm_gemm_plan(int M, int N, int K, int batch, int caps) { return gemm_choose(M, N, K, batch, caps); }
 static inline bool gemm_select_valid(int which) {
   const int k = which & 15;
   return which >= 0 && (k == 0 || k == 1 || k == 4 || k == 5 || k == 6 || k == 7 || k == 8);  // 7, 8: the latency-mode kernels through lfm_gemm_f16 (tests)
@@ -72,35 +80,35 @@ extern "C" int lfm_dit_call_settings(const lfm_dit_call* call, int* gemm_select_
   CallScope scope;
   const int rc = call_scope_enter(call);
   if (rc) return rc;
-  *gemm_select_out = g_gemm_sel | (g_gemm_dbg << 4);
-  *fold_ln_out = g_opt_fold_ln;
+  *gemm_select_out = gemm_sel() | (gemm_dbg() << 4);
+  *fold_ln_out = opt_fold_ln();
   return LFM_OK;
 }
 
 extern "C" int lfm_set_option(int key, int value) {  // key 1 (LFM_OPT_FOLD_LN): adaLN LayerNorm-modulate folded into the GEMM epilogues (default 1)
   if (key == 1) {
-    g_opt_fold_ln_default = value != 0;
+    opt_set(g_def.fold_ln, value != 0);
     return LFM_OK;
   }
   if (key == 2) {  // LFM_OPT_GEMM_V6: the one-wave-per-SIMD 256x256 kernel for the chip-filling row-major GEMMs
-    g_opt_v6 = value != 0;
+    opt_set(g_def.v6, value != 0);
     return LFM_OK;
   }
   if (key == 4) {  // LFM_OPT_SKINNY_GEMM: 0 = the split-K 128x128 path of rounds 2-4 for M <= 256 (A/B, parity)
-    g_opt_skinny = value < 0 || value > 2 ? 1 : value;
+    opt_set(g_def.skinny, value < 0 || value > 2 ? 1 : value);
     return LFM_OK;
   }
   if (key == 5) {  // LFM_OPT_ATTENTION_STREAM: 0 = one workgroup per (image, head) item (the rounds 1-5 kernel; A/B and the bit-equality test)
-    g_opt_att_stream = value != 0;
+    opt_set(g_def.att_stream, value != 0);
     return LFM_OK;
   }
   if (key == 6) {  // LFM_OPT_FUSED_QKV_ATTENTION: 0 = the QKV GEMM and the attention kernel as two launches (A/B and the bit-equality test)
-    g_opt_fused_qkv = value != 0;
+    opt_set(g_def.fused_qkv, value != 0);
     return LFM_OK;
   }
 #ifdef LFM_MEASURE
   if (key == 3) {  // measurement: start offset (s_memtime ticks) of the second resident workgroups of the two-per-CU kernels (gemm256_common.h)
-    g_stagger = value > 0 ? value : 0;
+    opt_set(g_def.stagger, value > 0 ? value : 0);
     return LFM_OK;
   }
 #endif
@@ -108,8 +116,8 @@ extern "C" int lfm_set_option(int key, int value) {  // key 1 (LFM_OPT_FOLD_LN):
 }
 extern "C" int lfm_gemm_select(int which) {  // low 4 bits: kernel choice (0 auto, 1, 4, 5, 6; 7, 8 for lfm_gemm_f16 only); bits 4+: ablation flags (measurement only)
   if (!gemm_select_valid(which)) return LFM_ERR_ARG;
-  g_gemm_sel_default = which & 15;
-  g_gemm_dbg_default = which >> 4;
+  opt_set(g_def.gemm_sel, which & 15);
+  opt_set(g_def.gemm_dbg, which >> 4);
   return LFM_OK;
 }
 
@@ -984,14 +992,14 @@ extern "C" int lfm_dit_attention(const void* Q, const void* K, const void* Vt, v
 static int ln_modulate_launch(const float* X, half_t* A, int M, int D, int tokens, const float* shift, const float* scale, long stride,
                               hipStream_t st) {
   if (D % 4 || D > 256 * LN_MAXV) return LFM_ERR_SHAPE;
-  if (D % 8 == 0 && !(((uintptr_t)A | (uintptr_t)X) & 15) && !(lfm_gemm_debug_flags() & 32768)) {  // flag 32768: the 8-byte-store kernel (A/B)
+  if (D % 8 == 0 && !(((uintptr_t)A | (uintptr_t)X) & 15) && !(gemm_dbg() & LFM_DBG_LN_STORE8)) {  // flag: the 8-byte-store kernel (A/B)
     // ONE row per wave and the two row sums on the DPP network (r02_probe3: 17.0-17.2 us = 5.9 TB/s at M 16384 x D 1024; two rows per wave with
-    // ds_bpermute sums -- the round-1 choice -- 20.4-20.9 us, one row with ds_bpermute 17.5-17.8 us, four rows 23.3-24.0 us).  A/B flags: 65536 =
-    // one row + ds_bpermute sums, 524288 = two rows, 262144 = four rows.
-    const int f = lfm_gemm_debug_flags();
-    if (f & 65536) hipLaunchKernelGGL(ln_modulate8_kernel<1>, dim3(cdiv(M, 4)), dim3(256), 0, st, X, A, M, D, tokens, shift, scale, stride);
-    else if (f & 524288) hipLaunchKernelGGL(ln_modulate8_kernel<2>, dim3(cdiv(M, 8)), dim3(256), 0, st, X, A, M, D, tokens, shift, scale, stride);
-    else if (f & 262144) hipLaunchKernelGGL(ln_modulate8_kernel<4>, dim3(cdiv(M, 16)), dim3(256), 0, st, X, A, M, D, tokens, shift, scale, stride);
+    // ds_bpermute sums -- the round-1 choice -- 20.4-20.9 us, one row with ds_bpermute 17.5-17.8 us, four rows 23.3-24.0 us).  A/B flags:
+    // LN_BPERMUTE = one row + ds_bpermute sums, LN_TWO_ROWS, LN_FOUR_ROWS.
+    const int f = gemm_dbg();
+    if (f & LFM_DBG_LN_BPERMUTE) hipLaunchKernelGGL(ln_modulate8_kernel<1>, dim3(cdiv(M, 4)), dim3(256), 0, st, X, A, M, D, tokens, shift, scale, stride);
+    else if (f & LFM_DBG_LN_TWO_ROWS) hipLaunchKernelGGL(ln_modulate8_kernel<2>, dim3(cdiv(M, 8)), dim3(256), 0, st, X, A, M, D, tokens, shift, scale, stride);
+    else if (f & LFM_DBG_LN_FOUR_ROWS) hipLaunchKernelGGL(ln_modulate8_kernel<4>, dim3(cdiv(M, 16)), dim3(256), 0, st, X, A, M, D, tokens, shift, scale, stride);
     else hipLaunchKernelGGL((ln_modulate8_kernel<1, true>), dim3(cdiv(M, 4)), dim3(256), 0, st, X, A, M, D, tokens, shift, scale, stride);
     LFM_CHECK_LAUNCH();
     return LFM_OK;
@@ -1008,14 +1016,56 @@ extern "C" int lfm_ln_modulate(const float* X, void* A, int M, int D, int tokens
   return ln_modulate_launch(X, (half_t*)A, M, D, tokens, shift, scale, mod_stride, (hipStream_t)stream);
 }
 
+// lfm_gemm_f16 / lfm_gemm_qkv_f16: the automatic choice; in a measurement build, first the variants that a forced kernel 5 / 6 plus flags ask for.
+// The main-loop-ablation and OPT variants exist for the GELU epilogue only (every further epilogue would multiply the measurement build's kernels).
+template <class Epi>
+static int gemm_f16_launch(const ASrcRowMajor& a, const half_t* W, long ldw, int M, int N, int K, const Epi& e, hipStream_t st) {
+#ifdef LFM_MEASURE
+  const int sel = gemm_sel(), dbg = gemm_dbg();
+  if (K % G256Q_BK == 0 && sel == 5 && (dbg & LFM_DBG_TRACE_GEMM)) return launch_gemm256h_tn<ASrcRowMajor, Epi, true>(a, W, ldw, M, N, K, e, st);  // the epilogue-stamped build
+  if constexpr (std::is_same<Epi, EpiBiasGeluF16>::value) {
+    const int abl = (dbg >> LFM_DBG_GEMM_ABL_SHIFT) & LFM_DBG_GEMM_ABL_MASK, opt = (dbg >> LFM_DBG_GEMM_OPT_SHIFT) & LFM_DBG_GEMM_OPT_MASK;
+    if (K % G256Q_BK == 0 && sel == 5 && (abl & 7)) {  // kernel 5, main-loop ablations: the field's low three bits, its top bit turns variant 7 into 8
+      switch (abl & 7) {
+        case 1: return launch_gemm256h_tn<ASrcRowMajor, Epi, false, 1>(a, W, ldw, M, N, K, e, st);
+        case 2: return launch_gemm256h_tn<ASrcRowMajor, Epi, false, 2>(a, W, ldw, M, N, K, e, st);
+        case 3: return launch_gemm256h_tn<ASrcRowMajor, Epi, false, 3>(a, W, ldw, M, N, K, e, st);
+        case 4: return launch_gemm256h_tn<ASrcRowMajor, Epi, false, 4>(a, W, ldw, M, N, K, e, st);
+        case 5: return launch_gemm256h_tn<ASrcRowMajor, Epi, false, 5>(a, W, ldw, M, N, K, e, st);
+        case 6: return launch_gemm256h_tn<ASrcRowMajor, Epi, false, 6>(a, W, ldw, M, N, K, e, st);
+        default: return (abl & 8) ? launch_gemm256h_tn<ASrcRowMajor, Epi, false, 8>(a, W, ldw, M, N, K, e, st)
+                                  : launch_gemm256h_tn<ASrcRowMajor, Epi, false, 7>(a, W, ldw, M, N, K, e, st);
+      }
+    }
+    if (K % G256Q_BK == 0 && (sel == 5 || sel == 6) && opt) {  // OPT variants
+      if (sel == 6) return launch_gemm256w_tn<ASrcRowMajor, Epi, 0, 0, 1>(a, W, ldw, M, N, K, e, st);
+      if (opt == 1) return launch_gemm256h_tn<ASrcRowMajor, Epi, false, 0, 1>(a, W, ldw, M, N, K, e, st);
+      if (opt == 2) return launch_gemm256h_tn<ASrcRowMajor, Epi, false, 0, 2>(a, W, ldw, M, N, K, e, st);
+      return launch_gemm256h_tn<ASrcRowMajor, Epi, false, 0, 3>(a, W, ldw, M, N, K, e, st);
+    }
+    if (K % G256Q_BK == 0 && sel == 6 && abl) {  // kernel 6: main-loop ablations 1..4, DMA placement 8
+      switch (abl) {
+        case 1: return launch_gemm256w_tn<ASrcRowMajor, Epi, 1>(a, W, ldw, M, N, K, e, st);
+        case 2: return launch_gemm256w_tn<ASrcRowMajor, Epi, 2>(a, W, ldw, M, N, K, e, st);
+        case 3: return launch_gemm256w_tn<ASrcRowMajor, Epi, 3>(a, W, ldw, M, N, K, e, st);
+        case 4: return launch_gemm256w_tn<ASrcRowMajor, Epi, 4>(a, W, ldw, M, N, K, e, st);
+        case 8: return launch_gemm256w_tn<ASrcRowMajor, Epi, 0, 1>(a, W, ldw, M, N, K, e, st);
+        default: return LFM_ERR_ARG;
+      }
+    }
+  }
+#endif
+  return launch_gemm_auto(a, W, ldw, M, N, K, e, st);
+}
+
 extern "C" int lfm_gemm_f16(const void* A, long lda, const void* W, long ldw, void* C, long ldc, int M, int N, int K, const float* bias,
                             int epilogue, const float* gate, long gate_stride, int tokens, lfm_stream_t stream) {
   if (!A || !W || !C) return LFM_ERR_ARG;
   if ((lda % 8) || ((uintptr_t)A & 15)) return LFM_ERR_ALIGN;
   hipStream_t st = (hipStream_t)stream;
   ASrcRowMajor a{(const half_t*)A, lda, M, 0};
-  if (g_gemm_sel == 7 || g_gemm_sel == 8) {  // the latency-mode kernels on their own (parity tests): 7 = 64x64 tiles, 8 = all rows x 16 columns; <= 256 rows
-    const int which = g_gemm_sel;
+  if (gemm_sel() == 7 || gemm_sel() == 8) {  // the latency-mode kernels on their own (parity tests): 7 = 64x64 tiles, 8 = all rows x 16 columns; <= 256 rows
+    const int which = gemm_sel();
     auto lat = [&](const auto& e) {
       return which == 7 ? launch_gemm_sq64((const half_t*)A, lda, (const half_t*)W, ldw, M, N, K, e, 1, st)
                         : launch_gemm_skinny((const half_t*)A, lda, (const half_t*)W, ldw, M, N, K, e, 1, st);
@@ -1028,60 +1078,12 @@ extern "C" int lfm_gemm_f16(const void* A, long lda, const void* W, long ldw, vo
     }
   }
   switch (epilogue) {
-    case 0:
-#ifdef LFM_MEASURE
-      if (g_gemm_sel == 5 && (g_gemm_dbg & 2) && K % G256Q_BK == 0)  // measurement: the epilogue-stamped build of the 16x16x32 kernel
-        return launch_gemm256h_tn<ASrcRowMajor, EpiBiasF16, true>(a, (const half_t*)W, ldw, M, N, K, EpiBiasF16{(half_t*)C, ldc, bias}, st);
-#endif
-      return launch_gemm_auto(a, (const half_t*)W, ldw, M, N, K, EpiBiasF16{(half_t*)C, ldc, bias}, st);
-    case 1:
-      if (!bias) return LFM_ERR_ARG;
-#ifdef LFM_MEASURE
-      if (g_gemm_sel == 5 && (g_gemm_dbg & 2) && K % G256Q_BK == 0)  // measurement: the epilogue-stamped build of the 16x16x32 kernel
-        return launch_gemm256h_tn<ASrcRowMajor, EpiBiasGeluF16, true>(a, (const half_t*)W, ldw, M, N, K, EpiBiasGeluF16{(half_t*)C, ldc, bias}, st);
-      if (g_gemm_sel == 5 && ((g_gemm_dbg >> 21) & 7) && K % G256Q_BK == 0) {  // measurement: main-loop ablations (flags 1..7 << 21)
-        const EpiBiasGeluF16 e{(half_t*)C, ldc, bias};
-        switch ((g_gemm_dbg >> 21) & 7) {
-          case 1: return launch_gemm256h_tn<ASrcRowMajor, EpiBiasGeluF16, false, 1>(a, (const half_t*)W, ldw, M, N, K, e, st);
-          case 2: return launch_gemm256h_tn<ASrcRowMajor, EpiBiasGeluF16, false, 2>(a, (const half_t*)W, ldw, M, N, K, e, st);
-          case 3: return launch_gemm256h_tn<ASrcRowMajor, EpiBiasGeluF16, false, 3>(a, (const half_t*)W, ldw, M, N, K, e, st);
-          case 4: return launch_gemm256h_tn<ASrcRowMajor, EpiBiasGeluF16, false, 4>(a, (const half_t*)W, ldw, M, N, K, e, st);
-          case 5: return launch_gemm256h_tn<ASrcRowMajor, EpiBiasGeluF16, false, 5>(a, (const half_t*)W, ldw, M, N, K, e, st);
-          case 6: return launch_gemm256h_tn<ASrcRowMajor, EpiBiasGeluF16, false, 6>(a, (const half_t*)W, ldw, M, N, K, e, st);
-          default: return (g_gemm_dbg & (1 << 24)) ? launch_gemm256h_tn<ASrcRowMajor, EpiBiasGeluF16, false, 8>(a, (const half_t*)W, ldw, M, N, K, e, st)
-                                                   : launch_gemm256h_tn<ASrcRowMajor, EpiBiasGeluF16, false, 7>(a, (const half_t*)W, ldw, M, N, K, e, st);
-        }
-      }
-      if ((g_gemm_sel == 5 || g_gemm_sel == 6) && ((g_gemm_dbg >> 25) & 3) && K % G256Q_BK == 0) {  // measurement: OPT variants (1..3 << 25)
-        const EpiBiasGeluF16 e{(half_t*)C, ldc, bias};
-        const int o = (g_gemm_dbg >> 25) & 3;
-        if (g_gemm_sel == 6) return launch_gemm256w_tn<ASrcRowMajor, EpiBiasGeluF16, 0, 0, 1>(a, (const half_t*)W, ldw, M, N, K, e, st);
-        if (o == 1) return launch_gemm256h_tn<ASrcRowMajor, EpiBiasGeluF16, false, 0, 1>(a, (const half_t*)W, ldw, M, N, K, e, st);
-        if (o == 2) return launch_gemm256h_tn<ASrcRowMajor, EpiBiasGeluF16, false, 0, 2>(a, (const half_t*)W, ldw, M, N, K, e, st);
-        return launch_gemm256h_tn<ASrcRowMajor, EpiBiasGeluF16, false, 0, 3>(a, (const half_t*)W, ldw, M, N, K, e, st);
-      }
-      if (g_gemm_sel == 6 && ((g_gemm_dbg >> 21) & 15) && K % G256Q_BK == 0) {  // measurement: v6 main-loop ablations (1..3 << 21) and DMA placement (8 << 21)
-        const EpiBiasGeluF16 e{(half_t*)C, ldc, bias};
-        switch ((g_gemm_dbg >> 21) & 15) {
-          case 1: return launch_gemm256w_tn<ASrcRowMajor, EpiBiasGeluF16, 1>(a, (const half_t*)W, ldw, M, N, K, e, st);
-          case 2: return launch_gemm256w_tn<ASrcRowMajor, EpiBiasGeluF16, 2>(a, (const half_t*)W, ldw, M, N, K, e, st);
-          case 3: return launch_gemm256w_tn<ASrcRowMajor, EpiBiasGeluF16, 3>(a, (const half_t*)W, ldw, M, N, K, e, st);
-          case 4: return launch_gemm256w_tn<ASrcRowMajor, EpiBiasGeluF16, 4>(a, (const half_t*)W, ldw, M, N, K, e, st);
-          case 8: return launch_gemm256w_tn<ASrcRowMajor, EpiBiasGeluF16, 0, 1>(a, (const half_t*)W, ldw, M, N, K, e, st);
-          default: return LFM_ERR_ARG;
-        }
-      }
-#endif
-      return launch_gemm_auto(a, (const half_t*)W, ldw, M, N, K, EpiBiasGeluF16{(half_t*)C, ldc, bias}, st);
-    case 2: return launch_gemm_auto(a, (const half_t*)W, ldw, M, N, K, EpiBiasF32{(float*)C, ldc, bias}, st);
+    case 0: return gemm_f16_launch(a, (const half_t*)W, ldw, M, N, K, EpiBiasF16{(half_t*)C, ldc, bias}, st);
+    case 1: return bias ? gemm_f16_launch(a, (const half_t*)W, ldw, M, N, K, EpiBiasGeluF16{(half_t*)C, ldc, bias}, st) : LFM_ERR_ARG;
+    case 2: return launch_gemm_auto(a, (const half_t*)W, ldw, M, N, K, EpiBiasF32{(float*)C, ldc, bias}, st);  // (no stamped build of this epilogue)
     case 3:
       if (!bias || !gate || tokens <= 0) return LFM_ERR_ARG;
-#ifdef LFM_MEASURE
-      if (g_gemm_sel == 5 && (g_gemm_dbg & 2) && K % G256Q_BK == 0)
-        return launch_gemm256h_tn<ASrcRowMajor, EpiGateResidF32, true>(a, (const half_t*)W, ldw, M, N, K,
-                                                                       EpiGateResidF32{(float*)C, ldc, bias, gate, gate_stride, tokens}, st);
-#endif
-      return launch_gemm_auto(a, (const half_t*)W, ldw, M, N, K, EpiGateResidF32{(float*)C, ldc, bias, gate, gate_stride, tokens}, st);
+      return gemm_f16_launch(a, (const half_t*)W, ldw, M, N, K, EpiGateResidF32{(float*)C, ldc, bias, gate, gate_stride, tokens}, st);
   }
   return LFM_ERR_ARG;
 }
@@ -1164,14 +1166,8 @@ extern "C" int lfm_gemm_qkv_f16(const void* A, long lda, const void* W, long ldw
   if (!A || !W || !Q || !Kout || !Vt || !bias) return LFM_ERR_ARG;
   if ((lda % 8) || ((uintptr_t)A & 15)) return LFM_ERR_ALIGN;
   if (head_dim <= 0 || tokens <= 0 || (D % head_dim) || (head_dim % 8) || (tokens % 16) || (M % tokens)) return LFM_ERR_SHAPE;  // 16: the V^T token groups (vt_pos)
-#ifdef LFM_MEASURE
-  if (g_gemm_sel == 5 && (g_gemm_dbg & 2) && K % G256Q_BK == 0)
-    return launch_gemm256h_tn<ASrcRowMajor, EpiQKV, true>(ASrcRowMajor{(const half_t*)A, lda, M, 0}, (const half_t*)W, ldw, M, 3 * D, K,
-                                                          EpiQKV::make((half_t*)Q, (half_t*)Kout, (half_t*)Vt, bias, D, head_dim, tokens),
-                                                          (hipStream_t)stream);
-#endif
-  return launch_gemm_auto(ASrcRowMajor{(const half_t*)A, lda, M, 0}, (const half_t*)W, ldw, M, 3 * D, K,
-                          EpiQKV::make((half_t*)Q, (half_t*)Kout, (half_t*)Vt, bias, D, head_dim, tokens), (hipStream_t)stream);
+  return gemm_f16_launch(ASrcRowMajor{(const half_t*)A, lda, M, 0}, (const half_t*)W, ldw, M, 3 * D, K,
+                         EpiQKV::make((half_t*)Q, (half_t*)Kout, (half_t*)Vt, bias, D, head_dim, tokens), (hipStream_t)stream);
 }
 
 #ifdef LFM_MEASURE  // s_memtime trace readers: measurement builds only (include/lfm_hip.h)
@@ -1349,12 +1345,12 @@ static DitPlan dit_plan(const lfm_dit_shape* s, int B, int rows) {
   DitPlan p;
   // folded LayerNorm-modulate: only where its preconditions hold -- whole 256-row tiles of ONE image each (or one shared modulation row), row partials in D / 256
   // slots, all four GEMMs chip-filling on the 16x16x32 kernel
-  p.fold = g_opt_fold_ln && (D % 256 == 0) && (M % 256 == 0) && (rows == 1 || T % 256 == 0) && (long)(M / 256) * tiles_p >= 192 &&
-           (g_gemm_sel == 0 || g_gemm_sel == 6) && (H % 64 == 0) && s->depth >= 1;
-  p.w6 = g_gemm_sel == 6 || (g_gemm_sel == 0 && g_opt_v6);  // the block GEMMs of the folded path on the one-wave-per-SIMD kernel
+  p.fold = opt_fold_ln() && (D % 256 == 0) && (M % 256 == 0) && (rows == 1 || T % 256 == 0) && (long)(M / 256) * tiles_p >= 192 &&
+           (gemm_sel() == 0 || gemm_sel() == 6) && (H % 64 == 0) && s->depth >= 1;
+  p.w6 = gemm_sel() == 6 || (gemm_sel() == 0 && opt_get(g_def.v6));  // the block GEMMs of the folded path on the one-wave-per-SIMD kernel
   // QKV projection + attention in one kernel (qkv_attention_kernel.h): one (image, head) per work item -- images of exactly one 256-token tile, head_dim 64,
   // operands inside the unsigned 32-bit byte offsets of its LDS-DMAs
-  p.fused = p.fold && g_opt_fused_qkv && !p.w6 && T == 256 && D == s->heads * 64 && (long)M * D < (1L << 31) && (long)3 * D * D < (1L << 31);
+  p.fused = p.fold && opt_get(g_def.fused_qkv) && !p.w6 && T == 256 && D == s->heads * 64 && (long)M * D < (1L << 31) && (long)3 * D * D < (1L << 31);
   return p;
 }
 // The plan of an evaluation without launching it (tests; a caller that sizes its expectations): *plan_out = LFM_PLAN_* bits.  Same scope code as the forward.
@@ -1403,7 +1399,7 @@ extern "C" int lfm_dit_forward(const lfm_dit_shape* s, const lfm_dit_weights* w,
   const int tiles_p = D / 256;
   const DitPlan plan = dit_plan(s, B, rows);
   const bool fold = plan.fold, w6 = plan.w6;
-  const bool pe_mfma = s->patch == 2 && s->in_ch == 4 && (D % 256 == 0) && D <= 1280 && (s->res % 2 == 0) && !(g_gemm_dbg & 2097152);  // flag: round-1 kernel
+  const bool pe_mfma = s->patch == 2 && s->in_ch == 4 && (D % 256 == 0) && D <= 1280 && (s->res % 2 == 0) && !(gemm_dbg() & LFM_DBG_DIT_PATCH_ROUND1);  // flag: round-1 kernel
   if (tab) {
     rc = dit_cond_select(s, ws, (const float*)c->cond_table, c->cond_step, c->cond_offset, c->cond_rows, st);
   } else {
@@ -1530,10 +1526,10 @@ extern "C" int lfm_dit_forward(const lfm_dit_shape* s, const lfm_dit_weights* w,
     while ((N_ / SQ_T) * (M / SQ_T) * (sl * 2) <= 256 && (K_ % (sl * 2 * SQ_BK)) == 0 && K_ / (sl * 2) >= 2 * SQ_BK && (size_t)(sl * 2) * M * N_ * 4 <= ws.slab_bytes) sl *= 2;
     return sl;
   };
-  const bool sq64 = g_opt_skinny == 1 && M >= SQ_T && (M % SQ_T) == 0 && gemm_sq64_ok(ws.A, D, w->qkv_w, D, M, 3 * D, D, 1) && gemm_sq64_ok(ws.A, D, w->fc1_w, D, M, H, D, 1) &&
+  const bool sq64 = opt_get(g_def.skinny) == 1 && M >= SQ_T && (M % SQ_T) == 0 && gemm_sq64_ok(ws.A, D, w->qkv_w, D, M, 3 * D, D, 1) && gemm_sq64_ok(ws.A, D, w->fc1_w, D, M, H, D, 1) &&
                     gemm_sq64_ok(ws.A, D, w->proj_w, D, M, D, D, sq_slices(D, D)) && gemm_sq64_ok(ws.QKVH, H, w->fc2_w, H, M, D, H, sq_slices(D, H));
   const int sk_s_proj = sq64 ? sq_slices(D, D) : sk_slices(D, D), sk_s_fc2 = sq64 ? sq_slices(D, H) : sk_slices(D, H);
-  const bool skinny = !fold && g_opt_skinny && g_gemm_sel == 0 && M <= SK_ROWS && ws.slab && D <= 1024 * SPLITK_LN_MAXJ && (D % 4) == 0 &&
+  const bool skinny = !fold && opt_get(g_def.skinny) && gemm_sel() == 0 && M <= SK_ROWS && ws.slab && D <= 1024 * SPLITK_LN_MAXJ && (D % 4) == 0 &&
                       gemm_skinny_ok(ws.A, D, w->qkv_w, D, M, 3 * D, D, 1) && gemm_skinny_ok(ws.A, D, w->fc1_w, D, M, H, D, 1) &&
                       gemm_skinny_ok(ws.A, D, w->proj_w, D, M, D, D, sk_s_proj) && gemm_skinny_ok(ws.QKVH, H, w->fc2_w, H, M, D, H, sk_s_fc2);
   auto lat_gemm = [&](const half_t* A_, long lda_, const half_t* W_, int N_, int K_, const auto& epi_, int S_) {  // the latency-mode linear: lda == ldw == K
@@ -1603,7 +1599,7 @@ extern "C" int lfm_dit_forward(const lfm_dit_shape* s, const lfm_dit_weights* w,
   const int Mh = cfg ? M / 2 : M;
   // skinny MFMA GEMM (16 rows per wave) when the shape allows it: whole 16-row tiles inside one image half, 16-column output tiles, D % 32 == 0
   const int NO = s->in_ch * s->patch * s->patch;
-  const bool fin_mfma = (NO == 16 || NO == 64) && (D % 32 == 0) && (T % 16 == 0) && (M % 16 == 0) && !(g_gemm_dbg & 1048576);  // flag 1048576: the round-1 kernel (A/B)
+  const bool fin_mfma = (NO == 16 || NO == 64) && (D % 32 == 0) && (T % 16 == 0) && (M % 16 == 0) && !(gemm_dbg() & LFM_DBG_DIT_FINAL_ROUND1);  // flag: the round-1 kernel (A/B)
   if (fin_mfma) {
     const long ntiles = cfg ? Mh / 8 : M / 16;
 #define FIN_LAUNCH(CF, NTT)                                                                                                                 \

@@ -7,9 +7,6 @@
 #pragma once
 #include "gemm_kernel.h"
 
-int lfm_gemm_selected();     // 0 auto, 1 force the 128x128 kernel, 4 the 256x128 one, 5 the 256x256 one (set by lfm_gemm_select)
-int lfm_gemm_debug_flags();  // ablation switches, measurement only
-int lfm_stagger_ticks();  // measurement builds (lfm_set_option key 3): s_memtime ticks by which workgroups 256..511 of a co-resident-pair kernel start late; else 0
 #ifdef LFM_MEASURE
 // Two workgroups share a CU in the 256x128 GEMM and the halo convolution; dispatched together they run in lockstep (both in their main loops, then both in
 // their epilogues).  The experiment: delay the second resident of every CU in the FIRST wave of workgroups (ids 256..511: consecutive ids go round the
@@ -21,7 +18,6 @@ __device__ __forceinline__ void lfm_stagger_start(int ticks) {
   }
 }
 #endif
-int lfm_gemm_prefers_v4(int M, int N, int K);  // shapes where the 256x128 two-workgroups-per-CU kernel measured faster than the 256x256 one
 
 #define G256_BM 256
 #define G256_BN 256
@@ -30,9 +26,9 @@ int lfm_gemm_prefers_v4(int M, int N, int K);  // shapes where the 256x128 two-w
 // GM = 4 M-panels column-major, so the ~32 tiles an XCD runs concurrently form a 4 x 8 patch (12 operand panels in its
 // L2) instead of a 1 x 32 / 2 x 16 strip (33 / 18 panels).
 __device__ __forceinline__ void g256_tile_order(int bid, int nb, int tiles_n, int dbg, int& tile_m, int& tile_n) {
-  if ((nb & 7) == 0 && !(dbg & 128)) bid = (bid & 7) * (nb >> 3) + (bid >> 3);
+  if ((nb & 7) == 0 && !(dbg & LFM_DBG_GEMM_NO_XCD_REMAP)) bid = (bid & 7) * (nb >> 3) + (bid >> 3);
   // GM x tiles_n should be a multiple of the ~32 tiles an XCD runs at once: 8 for 12 tile columns (QKV, measured -3 %), else 4
-  const int tiles_m = nb / tiles_n, GM = (dbg & 32) ? 8 : ((dbg & 64) ? 2 : ((dbg & 256) ? 4 : ((tiles_n & 7) && tiles_n > 8 ? 8 : 4)));
+  const int tiles_m = nb / tiles_n, GM = (dbg & LFM_DBG_GEMM_GM8) ? 8 : ((dbg & LFM_DBG_GEMM_GM2) ? 2 : ((dbg & LFM_DBG_GEMM_GM4) ? 4 : ((tiles_n & 7) && tiles_n > 8 ? 8 : 4)));
   const int grp = bid / (GM * tiles_n), within = bid - grp * (GM * tiles_n);
   const int gm = (tiles_m - grp * GM) < GM ? (tiles_m - grp * GM) : GM;  // last group may be short
   tile_m = grp * GM + within % gm;
@@ -167,12 +163,12 @@ __device__ __forceinline__ void g256_epilogue(f32x16 (&acc)[4][2], char* smem, E
   // 272 B: conflict-free ds_write_b128) and re-reads it row-major: 16 lanes cover one 256-B row, so a global access
   // instruction touches 4 rows x full lines.  Epilogues that want the fragment layout (V^T scatter) opt out.
   epi_batch(epi, bz, bsC, 0);
-  if (dbg & 4) return;  // ablation: no epilogue
+  if (dbg & LFM_DBG_GEMM_NO_EPILOGUE) return;  // ablation: no epilogue
   if constexpr (epi_has_transposed<Epi>::value) {
     // The K loop ran this tile with the MFMA operands swapped: lane (n = lane&31, h) holds FOUR CONSECUTIVE m per register
     // group.  Same scratch, roles exchanged: rows = 32 columns n of block j, columns = 64 rows m of blocks 2*ih, 2*ih+1; read
     // back row-major, 16 lanes cover 64 consecutive m of one n -> epi.store_t(n, m, C[m..m+3][n]).
-    if (swapped && !(dbg & 1024) && epi.wide_t_ok()) {  // 16-byte stores: lane = (column n = lane>>3 of 8 per pass, 8 consecutive rows m)
+    if (swapped && !(dbg & LFM_DBG_GEMM_STORE8) && epi.wide_t_ok()) {  // 16-byte stores: lane = (column n = lane>>3 of 8 per pass, 8 consecutive rows m)
       char* scr = smem + wave * (32 * 272);
       const int rrow = lane >> 3;
       const int ml = 16 * ((lane & 7) >> 1) + 4 * (lane & 1);  // tokens ml .. ml + 3 and ml + 8 .. ml + 11: one 16-byte chunk of the permuted V^T row (vt_pos)
@@ -266,11 +262,11 @@ __device__ __forceinline__ void g256_epilogue(f32x16 (&acc)[4][2], char* smem, E
   if constexpr (epi_has_plain<Epi>::value) {
     if (epi.plain_tile(n0, BN)) {
       auto pe = epi.plain(n0);
-      g256_epilogue_rows<BN>(acc, smem, pe, m0, n0, M, N, g, wn, lane, wave, (dbg & 1024) != 0);
+      g256_epilogue_rows<BN>(acc, smem, pe, m0, n0, M, N, g, wn, lane, wave, (dbg & LFM_DBG_GEMM_STORE8) != 0);
       return;
     }
   }
-  g256_epilogue_rows<BN>(acc, smem, epi, m0, n0, M, N, g, wn, lane, wave, (dbg & 1024) != 0);  // flag 1024: the 8-byte-store epilogue (A/B)
+  g256_epilogue_rows<BN>(acc, smem, epi, m0, n0, M, N, g, wn, lane, wave, (dbg & LFM_DBG_GEMM_STORE8) != 0);  // the 8-byte-store epilogue (A/B)
   if constexpr (epi_has_finish_tile<Epi>::value) epi.finish_tile(m0, n0, g, wn, lane);
 }
 
@@ -294,7 +290,7 @@ __device__ __forceinline__ void g256_epilogue(f32x16 (&acc)[4][2], char* smem, E
 #define G256Q_BUF_BYTES (4 * G256Q_PIECE)
 #define G256Q_LDS_BYTES (2 * G256Q_BUF_BYTES)
 
-// Measurement only (lfm_gemm_select flag 2 with kernel 5): s_memtime stamps of the epilogue, parked here and read back with lfm_gemm_trace_read().
+// Measurement only (lfm_gemm_select flag TRACE_GEMM with kernel 5): s_memtime stamps of the epilogue, parked here and read back with lfm_gemm_trace_read().
 // One copy per translation unit; dit.hip's is read back.
 #define G256Q_TRACE_MAX 2048
 static __device__ unsigned long long g256q_trace[2][G256Q_TRACE_MAX];

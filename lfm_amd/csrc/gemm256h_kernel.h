@@ -19,7 +19,7 @@ typedef float f32x4_t __attribute__((ext_vector_type(4)));
 
 // ---- epilogue for the 16x16 accumulator map.  acc[i][j]: tile i (16 rows) x j (16 columns) of the wave's 128 x 64 block.
 // fill32(I, scr): rows 32 I .. 32 I + 31 of the block -> scratch [32][64 + pad] fp32, row stride 272 B (as g256_epilogue_rows)
-// Measurement only (lfm_gemm_select flag 2 with kernel 5): waves 0 and 4 of the tile at row 0, column (flags >> 21) & 15 stamp s_memtime at the end of the K loop and after the
+// Measurement only (lfm_gemm_select flag TRACE_GEMM with kernel 5): waves 0 and 4 of the tile at row 0, column TRACE_COL stamp s_memtime at the end of the K loop and after the
 // scratch fill / read-back / store issue of each of the four 32-row blocks of the row-major epilogue (g256q_trace, lfm_gemm_trace_read).
 template <bool TRACE>
 __device__ __forceinline__ void g256h_stamp(bool tr, int g, int wn, int lane, int slot) {
@@ -303,7 +303,7 @@ __device__ __forceinline__ void g256h_epilogue_body(f32x4_t (&acc)[8][4], char* 
     // a lane gets 8 (or 4) consecutive m of one n -> epi.store_t8 / store_t.
     if (swapped) {
       char* scr = smem + wave * (32 * 272);
-      const bool wide = !(dbg & 1024) && epi.wide_t_ok();
+      const bool wide = !(dbg & LFM_DBG_GEMM_STORE8) && epi.wide_t_ok();
       // the per-column bias of every pass, loaded ahead of the first store (a load issued after stores waits for them: vmcnt is in order)
       typedef decltype(epi.load_t(0)) AuxT;  // float (a bias) or (u, v) of the folded path
       AuxT bt[2][4];
@@ -342,7 +342,7 @@ __device__ __forceinline__ void g256h_epilogue_body(f32x4_t (&acc)[8][4], char* 
               asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
               g256h_stamp<TRACE>(tr, g, wn, lane, 2 + 4 * (2 * J + ih));
             }
-            if (!(TRACE && (dbg & 131072))) {  // (trace build, flag 131072: the pass without its stores)
+            if (!(TRACE && (dbg & LFM_DBG_TRACE_NO_STORES))) {  // (trace build: the pass without its stores)
 #pragma unroll
               for (int ps = 0; ps < 4; ++ps) epi.store_t8(nb + ps * 8, m, lo[ps], hi[ps], bt[J][ps]);
             }
@@ -399,11 +399,11 @@ __device__ __forceinline__ void g256h_epilogue_body(f32x4_t (&acc)[8][4], char* 
   if constexpr (epi_has_plain<Epi>::value) {
     if (epi.plain_tile(n0, BN)) {
       auto pe = epi.plain(n0);
-      g256h_epilogue_rows<BN, TRACE>(acc, smem, pe, m0, n0, M, N, g, wn, lane, wave, (dbg & 1024) != 0, tr);
+      g256h_epilogue_rows<BN, TRACE>(acc, smem, pe, m0, n0, M, N, g, wn, lane, wave, (dbg & LFM_DBG_GEMM_STORE8) != 0, tr);
       return;
     }
   }
-  g256h_epilogue_rows<BN, TRACE>(acc, smem, epi, m0, n0, M, N, g, wn, lane, wave, (dbg & 1024) != 0, tr);
+  g256h_epilogue_rows<BN, TRACE>(acc, smem, epi, m0, n0, M, N, g, wn, lane, wave, (dbg & LFM_DBG_GEMM_STORE8) != 0, tr);
   if constexpr (epi_has_finish_tile<Epi>::value) epi.finish_tile(m0, n0, g, wn, lane);
   g256h_stamp<TRACE>(tr, g, wn, lane, 17);
 }
@@ -411,10 +411,10 @@ __device__ __forceinline__ void g256h_epilogue_body(f32x4_t (&acc)[8][4], char* 
 template <int BN, bool TRACE = false, class Epi>
 __device__ __forceinline__ void g256h_epilogue(f32x4_t (&acc)[8][4], char* smem, Epi& epi, int m0, int n0, int M, int N, int g, int wn, int lane,
                                                int wave, int bz, long bsC, int dbg, bool swapped) {
-  const bool tr = TRACE && m0 == 0 && n0 == ((dbg >> 21) & 15) * BN && bz == 0;  // the stamped tile: row 0, column (flags >> 21) & 15
+  const bool tr = TRACE && m0 == 0 && n0 == ((dbg >> LFM_DBG_TRACE_COL_SHIFT) & LFM_DBG_TRACE_COL_MASK) * BN && bz == 0;  // the stamped tile: row 0, column TRACE_COL
   epi_batch(epi, bz, bsC, 0);
   g256h_stamp<TRACE>(tr, g, wn, lane, 0);
-  if (dbg & 4) return;  // ablation: no epilogue
+  if (dbg & LFM_DBG_GEMM_NO_EPILOGUE) return;  // ablation: no epilogue
   if constexpr (epi_is_producer_mod<Epi>::value) {
     g256h_epilogue_mod(acc, smem, epi, m0, n0, n0 / BN, N, g, wn, lane, wave);
     return;

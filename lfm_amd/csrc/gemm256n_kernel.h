@@ -12,7 +12,7 @@
 //   * one workgroup in its epilogue: the other one has the whole matrix pipe.  To use more than half of it alone, a wave overlaps
 //     its own LDS reads with its own MFMAs (fragments of k16-step s+1 are in flight while step s multiplies; counted lgkmcnt);
 //   * age-ordered arbitration lets the older workgroup of a CU run ahead, so the two drift out of phase by themselves and their
-//     epilogues do not coincide (flag 2048: static s_setprio by block parity instead, A/B).
+//     epilogues do not coincide (flag GEMM_PARITY_PRIO: static s_setprio by block parity instead, A/B).
 // It is also the kernel for N = 128 problems (the 128-channel 256^2 convolutions of the VAE), which the 256-wide tiles waste.
 //
 // K is consumed in 32-deep tiles through a three-stage LDS ring (3 x 24 KiB: A 256 x 32 + W 128 x 32 fp16): tile t+2 is issued
@@ -47,14 +47,14 @@ __global__ __launch_bounds__(256, 2) void gemm256n_tn_kernel(ASrc asrc, const ha
 #endif
 
   int tile_m, tile_n;
-  g256_tile_order(blockIdx.x, gridDim.x, tiles_n, dbg | 32, tile_m, tile_n);  // GM = 8: an XCD runs ~64 of these tiles at a time
+  g256_tile_order(blockIdx.x, gridDim.x, tiles_n, dbg | LFM_DBG_GEMM_GM8, tile_m, tile_n);  // GM = 8: an XCD runs ~64 of these tiles at a time
   const int m0 = tile_m * G256_BM, n0 = tile_n * G256N_BN;
   bool swapped = false;
   if constexpr (epi_has_transposed<Epi>::value) swapped = epi.transposed(n0);
   const int bz = blockIdx.y;
   asrc.init(bz, bsA);
   W += (long)bz * bsW;
-  if (dbg & 2048) {  // A/B: static priority by block parity instead of the pipe's age order
+  if (dbg & LFM_DBG_GEMM_PARITY_PRIO) {  // A/B: static priority by block parity instead of the pipe's age order
     if (__builtin_amdgcn_readfirstlane(blockIdx.x) & 1) __builtin_amdgcn_s_setprio(1);
   }
 
@@ -120,7 +120,7 @@ __global__ __launch_bounds__(256, 2) void gemm256n_tn_kernel(ASrc asrc, const ha
 #define G256N_LGKM(n) asm volatile("s_waitcnt lgkmcnt(" #n ")" ::: "memory")
   auto mfma_tile = [&](auto SWC) {
     constexpr bool SW = decltype(SWC)::value != 0;
-    if (dbg & 8) __builtin_amdgcn_s_setprio(1);  // A/B: raise the priority around the MFMA cluster (T5)
+    if (dbg & LFM_DBG_GEMM_SETPRIO) __builtin_amdgcn_s_setprio(1);  // A/B: raise the priority around the MFMA cluster (T5)
 #pragma unroll
     for (int ks = 0; ks < 2; ++ks)
 #pragma unroll
@@ -145,7 +145,7 @@ __global__ __launch_bounds__(256, 2) void gemm256n_tn_kernel(ASrc asrc, const ha
         }
         __builtin_amdgcn_sched_barrier(0);
       }
-    if (dbg & 8) __builtin_amdgcn_s_setprio(0);
+    if (dbg & LFM_DBG_GEMM_SETPRIO) __builtin_amdgcn_s_setprio(0);
   };
 #undef G256N_LGKM
 

@@ -307,7 +307,7 @@ __global__ __launch_bounds__(256) void gemm256w_tn_kernel(ASrc asrc, const half_
   G256_BARRIER();  // every wave's last fragment reads are retired: the K-tile buffers are free for the epilogue scratch
 
   epi_batch(epi, bz, bsC, 0);
-  if (dbg & 4) return;  // ablation: no epilogue
+  if (dbg & LFM_DBG_GEMM_NO_EPILOGUE) return;  // ablation: no epilogue
   if constexpr (epi_is_producer_mod<Epi>::value) {
     g256w_epilogue_mod(acc, smem, epi, m0, n0, n0 / G256_BN, N, wm, wn, lane, wave);
   } else {

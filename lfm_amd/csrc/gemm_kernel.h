@@ -18,8 +18,7 @@
 // the epilogue sees (m, n..n+3, float4) and can do 8/16-byte stores and per-n vector loads.
 #pragma once
 #include "common.h"
-
-int lfm_gemm_selected_v1_ok();  // 1 unless a 256x256 kernel is being forced (lfm_gemm_select 2 / 3): split-K runs on the 128x128 kernel
+#include "debug_flags.h"
 
 #define GEMM_BM 128
 #define GEMM_BN 128
@@ -831,9 +830,8 @@ static inline int splitk_slices(int M, int N, int K, size_t slab_bytes, int max_
 // 256x256 eight-wave kernel instead of the 128x128 one: its main loop runs at ~1.3 PFLOP/s where the 128x128 loop reaches 0.45-0.75
 // (profiles/r04_conv_small_maps_probe.txt), and a slice that is >= 24 K-tiles deep amortises its longer prologue / epilogue.  S = the largest divisor
 // of the K-tile count that keeps tiles x S <= 256 workgroups (one per CU) with slices >= `min_tiles_k` K-tiles.  0 = does not apply.
-int lfm_gemm_debug_flags();
 static inline int splitk256_slices(int M, int N, int K, size_t slab_bytes, int min_tiles_k = 24) {
-  if (M < 2048 || N < 256 || (N % 256) != 0 || (K % 64) != 0 || (lfm_gemm_debug_flags() & 65536)) return 0;  // flag 65536: the 128x128 slices (A/B)
+  if (M < 2048 || N < 256 || (N % 256) != 0 || (K % 64) != 0 || (lfm_gemm_debug_flags() & LFM_DBG_GEMM_SPLITK128)) return 0;  // the 128x128 slices (A/B)
   const long tiles = (long)cdiv(M, 256) * (N / 256);
   if (tiles > 128) return 0;
   const int kt = K / 64;

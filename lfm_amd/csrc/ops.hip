@@ -166,8 +166,8 @@ extern "C" int lfm_conv3x3_f16_ws(const void* in, const void* w, const float* bi
   const half_t* xi = (const half_t*)in;
   float* ws = (float*)workspace;
   // plain and upsample-fused 3x3 convolutions on 16-aligned maps that fill the chip: the halo-tiled direct kernel (conv_halo_kernel.h);
-  // flag 8388608: the implicit GEMM instead (A/B and parity tests)
-  if (mode != 2 && lfm_gemm_selected() == 0 && !(lfm_gemm_debug_flags() & 8388608) && !(((uintptr_t)out | (uintptr_t)resid) & 15)) {
+  // CONV_IMPLICIT_GEMM: the implicit GEMM instead (A/B and parity tests)
+  if (mode != 2 && lfm_gemm_selected() == 0 && !(lfm_gemm_debug_flags() & LFM_DBG_CONV_IMPLICIT_GEMM) && !(((uintptr_t)out | (uintptr_t)resid) & 15)) {
     const int rc = mode == 1 ? launch_conv3x3_halo<1>(xi, z, wi, N, H, W, Cin, Cout, epi, st) : launch_conv3x3_halo<0>(xi, z, wi, N, H, W, Cin, Cout, epi, st);
     if (rc != 1) return rc;
   }
@@ -189,7 +189,7 @@ extern "C" int lfm_conv3x3_out_f32(const void* in, const void* w4, const float* 
   if (!z) return LFM_ERR_LAUNCH;
   const int M = N * H * W;
   const EpiNCHWF32 eo{out_nchw, bias4, H * W, nch};
-  if (lfm_gemm_selected() == 0 && !(lfm_gemm_debug_flags() & 8388608)) {  // flag 8388608: the implicit GEMM (A/B)
+  if (lfm_gemm_selected() == 0 && !(lfm_gemm_debug_flags() & LFM_DBG_CONV_IMPLICIT_GEMM)) {  // flag: the implicit GEMM (A/B)
     const int rc = launch_conv3x3_halo_out((const half_t*)in, z, (const half_t*)w4, N, H, W, Cin, eo, (hipStream_t)stream);
     if (rc != 1) return rc;
   }
@@ -347,7 +347,7 @@ extern "C" int lfm_conv3x3_in_f32(const float* x_nchw, const float* w, const flo
   if (!x_nchw || !w || !bias || !out_nhwc) return LFM_ERR_ARG;
   if (N <= 0 || Cin <= 0 || Cin > 16 || Cout % 8 || Cout / 8 > 256) return LFM_ERR_SHAPE;
   if ((Cout == 64 || Cout == 128 || Cout == 192 || Cout == 256) && !((uintptr_t)out_nhwc & 7) && !((uintptr_t)bias & 15) &&
-      !(lfm_gemm_debug_flags() & 1)) {  // flag 1: the scalar kernel (A/B)
+      !(lfm_gemm_debug_flags() & LFM_DBG_UNET_CONV_IN_SCALAR)) {  // flag: the scalar kernel (A/B)
     int rc;
     if (Cout == 64) rc = launch_conv_in_mfma<1>(x_nchw, w, bias, (half_t*)out_nhwc, N, H, W, Cin, Cout, (hipStream_t)stream);
     else if (Cout == 128) rc = launch_conv_in_mfma<2>(x_nchw, w, bias, (half_t*)out_nhwc, N, H, W, Cin, Cout, (hipStream_t)stream);
@@ -711,7 +711,7 @@ static int groupnorm_impl(const GnIn& in, void* y, const float* gamma, const flo
   // (measured on the celeb512 UNet: at 64x64 maps the fused kernel's 256 blocks are too few -- 300 us vs ~35 us for the three kernels)
   // fused path: one block's 256 threads cover the gpb * cpg / 8 eight-channel columns of its groups, so a single group may be at most 2048
   // channels wide (wider groups -- e.g. groups = 1 on 4096 channels -- take the three-kernel path below instead of shrinking gpb to zero)
-  if (cpg % 8 == 0 && cpg <= 2048 && HW <= 1024 && !(lfm_gemm_debug_flags() & 16384)) {  // flag 16384: the three-kernel path (A/B)
+  if (cpg % 8 == 0 && cpg <= 2048 && HW <= 1024 && !(lfm_gemm_debug_flags() & LFM_DBG_UNET_GN_ROWS)) {  // flag: the three-kernel path (A/B)
     int gpb = 1;
     while (gpb * 2 <= G && G % (gpb * 2) == 0 && (long)N * (G / (gpb * 2)) >= 256 && gpb * 2 * cpg <= 2048) gpb *= 2;
     dim3 grid(G / gpb, N);
@@ -1020,7 +1020,7 @@ static int launch_attention_unet_mfma(const half_t* qkv, half_t* out, int N, int
 extern "C" int lfm_attention_small_f16(const void* qkv, void* out, int N, int T, int heads, int ch, lfm_stream_t stream) {
   if (!qkv || !out) return LFM_ERR_ARG;
   if (N <= 0 || T <= 0 || heads <= 0 || ch <= 0) return LFM_ERR_SHAPE;
-  if (!(((uintptr_t)qkv | (uintptr_t)out) & 15) && !(lfm_gemm_debug_flags() & 16)) {  // flag 16: the VALU kernel (A/B)
+  if (!(((uintptr_t)qkv | (uintptr_t)out) & 15) && !(lfm_gemm_debug_flags() & LFM_DBG_UNET_ATT_VALU)) {  // flag: the VALU kernel (A/B)
     const half_t* qi = (const half_t*)qkv;
     half_t* oi = (half_t*)out;
     hipStream_t st = (hipStream_t)stream;

@@ -80,8 +80,8 @@ __global__ __launch_bounds__(512) void qkv_attention_kernel(const half_t* __rest
     wvoff1 = ((unsigned)(2 * D + head_ * 64 + (tid >> 3)) * (unsigned)ldw + (unsigned)cswz) * 2u;  // B1: LDS row = V dim
   };
   set_item(m0, head);
-#ifdef LFM_MEASURE  // phase split (tools/fused_qkv_phases.py; results are garbage): flag 67108864 = two K-tiles only, 33554432 = no key loop
-  const int nk = (dbg & 67108864) ? 2 : K / G256Q_BK;
+#ifdef LFM_MEASURE  // phase split (tools/fused_qkv_phases.py; results are garbage): QKV_TWO_KTILES, QKV_NO_KEY_LOOP
+  const int nk = (dbg & LFM_DBG_QKV_TWO_KTILES) ? 2 : K / G256Q_BK;
 #else
   const int nk = K / G256Q_BK;
 #endif
@@ -308,12 +308,12 @@ __global__ __launch_bounds__(512) void qkv_attention_kernel(const half_t* __rest
 
   const float scale_log2e = ep.scale_log2e;
   bool first = true;
-  // (measurement builds, flag 2: s_memtime stamps of waves 0 and 4 of workgroup 0 -> att_trace[0..31] / [32..63], read with lfm_attention_trace_read; per item k, slot
+  // (measurement builds, flag QKV_TRACE: s_memtime stamps of waves 0 and 4 of workgroup 0 -> att_trace[0..31] / [32..63], read with lfm_attention_trace_read; per item k, slot
   // 7 k + {0 loop top, 1 operands landed (barrier), 2 K loop done, 3 hand-over done (barrier), 4 next item requested, 5 key loop done, 6 stores issued})
   [[maybe_unused]] int tr_k = 0;
   auto stamp = [&](int slot) {
 #ifdef LFM_MEASURE
-    if ((dbg & 2) && blockIdx.x == 0 && (wave & 3) == 0 && tr_k < 4) {
+    if ((dbg & LFM_DBG_QKV_TRACE) && blockIdx.x == 0 && (wave & 3) == 0 && tr_k < 4) {
       unsigned long long t;
       asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory");
       if (lane == 0) att_trace[(wave >> 2) * 32 + 7 * tr_k + slot] = t;
@@ -367,8 +367,8 @@ __global__ __launch_bounds__(512) void qkv_attention_kernel(const half_t* __rest
           // tiles 0 and 1 of the wave are the two halves of EIGHT consecutive dims of one matrix (the W rows were gathered that way): one 16-byte write per row
           const f32x4 lo = row_affine4(ab[ii].x, ab[ii].y, acc[i][0], uq, vq);
           const f32x4 hi = row_affine4(ab[ii].x, ab[ii].y, acc[i][1], uk, vk);
-#ifdef LFM_MEASURE  // (hand-over ablation: flag 524288 = no Q / K writes, 262144 = no V^T writes)
-          if (!(dbg & 524288))
+#ifdef LFM_MEASURE  // (hand-over ablation: QKV_NO_QK_WRITES, QKV_NO_VT_WRITES)
+          if (!(dbg & LFM_DBG_QKV_NO_QK_WRITES))
 #endif
             *(half8_t*)(QKs + m * 128 + (((4 * (wn & 1) + l4) ^ ((m >> 1) & 7)) << 4)) =
                 (half8_t){(half_t)lo.x, (half_t)lo.y, (half_t)lo.z, (half_t)lo.w, (half_t)hi.x, (half_t)hi.y, (half_t)hi.z, (half_t)hi.w};
@@ -393,7 +393,7 @@ __global__ __launch_bounds__(512) void qkv_attention_kernel(const half_t* __rest
           const u32x4 chunk = {s0[0], s1[0], s0[1], s1[1]};  // positions 0-3 (tokens 0-3 / 4-7 of the group), then 4-7 (tokens 8-11 / 12-15)
           const int G2 = 8 * g + ih * 4 + ip * 2 + (l4 >> 1);  // the group this lane writes
 #ifdef LFM_MEASURE
-          if (!(dbg & 262144))
+          if (!(dbg & LFM_DBG_QKV_NO_VT_WRITES))
 #endif
             *(u32x4*)(Vs + d * 512 + (((2 * G2 + (l4 & 1)) ^ (d & 15)) << 4)) = chunk;
         }
@@ -498,7 +498,7 @@ __global__ __launch_bounds__(512) void qkv_attention_kernel(const half_t* __rest
     };
     f32x16 Sa, Sb;
 #ifdef LFM_MEASURE
-    if (!(dbg & 33554432))
+    if (!(dbg & LFM_DBG_QKV_NO_KEY_LOOP))
 #endif
     {
       qk(Sa, 0);
@@ -587,7 +587,7 @@ static inline int launch_qkv_attention(const half_t* A, long lda, const half_t* 
   }
   const int items = (M / G256_BM) * heads, ncu = cus[devid & 63].load(std::memory_order_relaxed);
   const int dbg = lfm_gemm_debug_flags();
-  const int grid = (items <= ncu || (dbg & 4194304)) ? items : ncu;  // one persistent workgroup per CU (flag 4194304: one workgroup per item, A/B)
+  const int grid = (items <= ncu || (dbg & LFM_DBG_QKV_PER_ITEM)) ? items : ncu;  // one persistent workgroup per CU (flag: one workgroup per item, A/B)
   hipLaunchKernelGGL(qkv_attention_kernel, dim3(grid), dim3(512), QKVA_LDS_BYTES, stream, A, lda, W, ldw, M, K, ep, items, dbg);
   LFM_CHECK_LAUNCH();
   return LFM_OK;

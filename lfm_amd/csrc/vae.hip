@@ -541,12 +541,12 @@ static int conv3(const half_t* in, const half_t* w, const float* b, const half_t
   const int M = n * H * W;
   if (stat_slabs) *stat_slabs = 0;
   if (stat_kernel) *stat_kernel = 0;
-  const int HW = H * W, kern = gemm_auto_choice(M, Cout, 9 * Cin);
+  const int HW = H * W;
   // every 3x3 convolution on a 16-aligned map: the halo-tiled direct kernel (conv_halo_kernel.h; 1.1-1.2 PFLOP/s where the implicit GEMM reaches
-  // 0.65-1.05, profiles/r03_halo_conv_probe.txt); flag 8388608: the implicit GEMM instead (A/B)
-  if (lfm_gemm_selected() == 0 && !(((uintptr_t)out | (uintptr_t)resid) & 15) && !(lfm_gemm_debug_flags() & 8388608)) {
+  // 0.65-1.05, profiles/r03_halo_conv_probe.txt); CONV_IMPLICIT_GEMM: the implicit GEMM instead (A/B)
+  if (lfm_gemm_selected() == 0 && !(((uintptr_t)out | (uintptr_t)resid) & 15) && !(lfm_gemm_debug_flags() & LFM_DBG_CONV_IMPLICIT_GEMM)) {
     int rc;
-    if (part && stat_slabs && (HW % 256) == 0 && !(lfm_gemm_debug_flags() & 4194304)) {
+    if (part && stat_slabs && (HW % 256) == 0 && !(lfm_gemm_debug_flags() & LFM_DBG_VAE_SEPARATE_STATS)) {
       EpiConvStatsF16 es{out, Cout, b, resid, part, HW, 2 * (HW / 256), 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
       rc = ups ? launch_conv3x3_halo<1>(in, zeros, w, n, H, W, Cin, Cout, es, st) : launch_conv3x3_halo<0>(in, zeros, w, n, H, W, Cin, Cout, es, st);
       if (rc == 0) {
@@ -559,17 +559,20 @@ static int conv3(const half_t* in, const half_t* w, const float* b, const half_t
     }
     if (rc != 1) return rc;
   }
-  if (part && stat_slabs && (HW % 256) == 0 && (kern == 4 || kern == 5) && (Cout % (kern == 4 ? 128 : 256)) == 0 && (Cout % 128) == 0 &&
-      !(((uintptr_t)out | (uintptr_t)resid) & 15) && !(lfm_gemm_debug_flags() & (1024 | 4194304))) {  // flag 4194304: the separate statistics pass (A/B)
-    *stat_slabs = 2 * (HW / 256);
-    if (stat_kernel) *stat_kernel = 2;
-    EpiConvStatsF16 es{out, Cout, b, resid, part, HW, *stat_slabs, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    if (ups) return launch_gemm_auto(ASrcConv3x3<1>{in, zeros, H, W, Cin, M, 0, 0}, w, 9L * Cin, M, Cout, 9 * Cin, es, st);
-    return launch_gemm_auto(ASrcConv3x3<0>{in, zeros, H, W, Cin, M, 0, 0}, w, 9L * Cin, M, Cout, 9 * Cin, es, st);
-  }
-  EpiConvF16 epi{out, Cout, b, resid};
-  if (ups) return launch_gemm_auto(ASrcConv3x3<1>{in, zeros, H, W, Cin, M, 0, 0}, w, 9L * Cin, M, Cout, 9 * Cin, epi, st);
-  return launch_gemm_auto(ASrcConv3x3<0>{in, zeros, H, W, Cin, M, 0, 0}, w, 9L * Cin, M, Cout, 9 * Cin, epi, st);
+  // the implicit GEMM.  The statistics epilogue leaves its partials in the slot layout of the 256-row kernels' tiles: ask which kernel runs for the types
+  // about to be launched, take the epilogue only if that is one of them, and launch THAT kernel (one decision for the layout and the launch).
+  auto gemm = [&](const auto& a) {
+    const int kern = gemm_choose(M, Cout, 9 * Cin, 1, gemm_caps<std::decay_t<decltype(a)>, EpiConvStatsF16>(a, Cout, 9L * Cin));
+    if (part && stat_slabs && (HW % 256) == 0 && (kern == 4 || kern == 5) && (Cout % (kern == 4 ? 128 : 256)) == 0 && (Cout % 128) == 0 &&
+        !(((uintptr_t)out | (uintptr_t)resid) & 15) && !(lfm_gemm_debug_flags() & (LFM_DBG_GEMM_STORE8 | LFM_DBG_VAE_SEPARATE_STATS))) {
+      *stat_slabs = 2 * (HW / 256);
+      if (stat_kernel) *stat_kernel = 2;
+      return launch_gemm_kernel(kern, a, w, 9L * Cin, M, Cout, 9 * Cin, EpiConvStatsF16{out, Cout, b, resid, part, HW, *stat_slabs, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, st);
+    }
+    return launch_gemm_auto(a, w, 9L * Cin, M, Cout, 9 * Cin, EpiConvF16{out, Cout, b, resid}, st);
+  };
+  if (ups) return gemm(ASrcConv3x3<1>{in, zeros, H, W, Cin, M, 0, 0});
+  return gemm(ASrcConv3x3<0>{in, zeros, H, W, Cin, M, 0, 0});
 }
 
 // ---- test entry points: the decoder's GroupNorm (gn, its own statistics pass) and the conv3 -> gn hand-over, on the decoder's host code.
@@ -719,8 +722,8 @@ extern "C" int lfm_vae_decode(const lfm_vae_weights* w, void* workspace, size_t 
     const int M = n * H * H;
     {
       const EpiConvOutNCHW eo{out + (long)n0 * 3 * H * H, w->cout_b, H * H};
-      int rc = 1;  // flag 8388608: the implicit GEMM (A/B)
-      if (lfm_gemm_selected() == 0 && !(lfm_gemm_debug_flags() & 8388608)) rc = launch_conv3x3_halo_out(t1, ws.zeros, (const half_t*)w->cout_w, n, H, H, 128, eo, st);
+      int rc = 1;  // CONV_IMPLICIT_GEMM: the implicit GEMM (A/B)
+      if (lfm_gemm_selected() == 0 && !(lfm_gemm_debug_flags() & LFM_DBG_CONV_IMPLICIT_GEMM)) rc = launch_conv3x3_halo_out(t1, ws.zeros, (const half_t*)w->cout_w, n, H, H, 128, eo, st);
       if (rc == 1) rc = launch_gemm_tn(ASrcConv3x3<0>{t1, ws.zeros, H, H, 128, M, 0, 0}, (const half_t*)w->cout_w, 9L * 128, M, 4, 9 * 128, eo, st);
       RC(rc);
     }

@@ -111,6 +111,8 @@ def lib():
     L.lfm_dit_call_settings.argtypes = [C.POINTER(DitCall), C.POINTER(C.c_int), C.POINTER(C.c_int)]
     L.lfm_dit_plan.restype = C.c_int
     L.lfm_dit_plan.argtypes = [C.POINTER(DitShape), C.POINTER(DitCall), C.POINTER(C.c_int)]
+    L.lfm_gemm_plan.restype = C.c_int
+    L.lfm_gemm_plan.argtypes = [C.c_int] * 5
     L.lfm_dit_attention_hd.restype = C.c_int
     L.lfm_dit_attention_hd.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]
     L.lfm_grid_advance.restype = C.c_int
@@ -252,6 +254,50 @@ def ln_modulate(X, shift, scale, tokens, mod_stride):
     return A
 
 
+# Ablation flags of gemm_select (`kernel | flags << 4`) and lfm_dit_call.gemm_select: the names, values and meanings of csrc/debug_flags.h (the single
+# definition; tests/test_host_logic.py compares the two).  NAME_SHIFT / NAME_MASK: a multi-bit field, value << NAME_SHIFT.  Several flags share bits.
+DBG_GEMM_NO_EPILOGUE = 4
+DBG_GEMM_SETPRIO = 8
+DBG_GEMM_GM8 = 32
+DBG_GEMM_GM2 = 64
+DBG_GEMM_NO_XCD_REMAP = 128
+DBG_GEMM_GM4 = 256
+DBG_GEMM_NO_SPLITK = 512
+DBG_GEMM_STORE8 = 1024
+DBG_GEMM_PARITY_PRIO = 2048
+DBG_GEMM_NEVER_V4 = 4096
+DBG_GEMM_ALWAYS_V4 = 8192
+DBG_GEMM_SPLITK128 = 65536
+DBG_GEMM_ABL_SHIFT = 21
+DBG_GEMM_ABL_MASK = 15
+DBG_GEMM_OPT_SHIFT = 25
+DBG_GEMM_OPT_MASK = 3
+DBG_TRACE_GEMM = 2
+DBG_TRACE_NO_STORES = 131072
+DBG_TRACE_COL_SHIFT = 21
+DBG_TRACE_COL_MASK = 15
+DBG_ATT_WIDE = 256
+DBG_ATT_MODE_SHIFT = 25
+DBG_ATT_MODE_MASK = 3
+DBG_QKV_TRACE = 2
+DBG_QKV_NO_VT_WRITES = 262144
+DBG_QKV_NO_QK_WRITES = 524288
+DBG_QKV_PER_ITEM = 4194304
+DBG_QKV_NO_KEY_LOOP = 33554432
+DBG_QKV_TWO_KTILES = 67108864
+DBG_LN_STORE8 = 32768
+DBG_LN_BPERMUTE = 65536
+DBG_LN_FOUR_ROWS = 262144
+DBG_LN_TWO_ROWS = 524288
+DBG_DIT_FINAL_ROUND1 = 1048576
+DBG_DIT_PATCH_ROUND1 = 2097152
+DBG_CONV_IMPLICIT_GEMM = 8388608
+DBG_CONV_HALO_SMALL = 16777216
+DBG_VAE_SEPARATE_STATS = 4194304
+DBG_UNET_CONV_IN_SCALAR = 1
+DBG_UNET_ATT_VALU = 16
+DBG_UNET_GN_ROWS = 16384
+
 OPT_FOLD_LN = 1  # adaLN LayerNorm-modulate folded into the GEMM epilogues, default on (include/lfm_hip.h)
 OPT_SKINNY_GEMM = 4  # batch-1 DiT linears on the latency-mode kernels (1, default: csrc/gemm_sq64_kernel.h where rows % 64 == 0, else csrc/gemm_skinny_kernel.h; 2: always the latter; 0: split-K path)
 OPT_ATTENTION_STREAM = 5  # 256-token hd-64 attention on persistent workgroups with an LDS ring of K / V^T stages (csrc/attention_stream_kernel.h), default on; 0: one workgroup per item
@@ -289,6 +335,14 @@ def dit_plan(shape, batch, t_len=1, labels=False, fold_ln=0, gemm_select=0):
     plan = C.c_int(-1)
     check(lib().lfm_dit_plan(C.byref(shape), C.byref(call), C.byref(plan)), "lfm_dit_plan")
     return plan.value
+
+
+GEMM_CAP_V6, GEMM_CAP_FITS = 1, 2  # lfm_gemm_plan caps: row-major A and an epilogue the one-wave-per-SIMD kernel serves; operands within 32-bit buffer offsets
+
+
+def gemm_plan(M, N, K, batch=1, caps=GEMM_CAP_V6 | GEMM_CAP_FITS):
+    """The GEMM kernel (1 / 4 / 5 / 6) the library runs for this shape under the calling thread's current selection (no launch, no GPU needed)."""
+    return lib().lfm_gemm_plan(int(M), int(N), int(K), int(batch), int(caps))
 
 
 def set_option(key, value):

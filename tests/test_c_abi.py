@@ -167,10 +167,10 @@ def test_per_call_settings_are_scoped_to_the_call_and_the_thread(lib):
 
     def a():
         call = hip.DitCall()
-        call.gemm_select = hip.call_gemm_select(6 | (256 << 4))
+        call.gemm_select = hip.call_gemm_select(6 | (hip.DBG_GEMM_GM4 << 4))
         call.fold_ln = hip.CALL_OFF
         for _ in range(20000):
-            if settings(call) != (0, 6 | (256 << 4), 0):
+            if settings(call) != (0, 6 | (hip.DBG_GEMM_GM4 << 4), 0):
                 errors.append(("per-call", settings(call)))
                 break
         stop.set()

@@ -11,6 +11,7 @@ import torch
 
 pytestmark = pytest.mark.gpu
 
+from lfm_amd import hip
 from oracle import dit_ref  # checker only
 
 
@@ -125,9 +126,9 @@ def _gemm_case(M, N, K, epi):
                                    (512, 256, 192), (256, 512, 320), (768, 512, 576), (512, 128, 96), (384, 132, 160), (256, 128, 32),
                                    (65536, 128, 1152)])
 @pytest.mark.parametrize("epi", [0, 1, 2, 3])
-@pytest.mark.parametrize("kernel", [4, 4 | (1024 << 4), 5, 5 | (1024 << 4), 6, 6 | (1024 << 4)])
+@pytest.mark.parametrize("kernel", [4, 4 | (hip.DBG_GEMM_STORE8 << 4), 5, 5 | (hip.DBG_GEMM_STORE8 << 4), 6, 6 | (hip.DBG_GEMM_STORE8 << 4)])
 def test_gemm256_kernels(dev, M, N, K, epi, kernel):
-    """Same checks with a 256-row kernel forced (lfm_gemm_select: 4 = the 256x128 two-workgroups-per-CU kernel, 4 | 1024<<4 = with the 8-byte-store
+    """Same checks with a 256-row kernel forced (lfm_gemm_select: 4 = the 256x128 two-workgroups-per-CU kernel, 4 | GEMM_STORE8<<4 = with the 8-byte-store
     epilogue, 5 = the quadrant-phased 256x256 kernel on 16x16x32 MFMAs, the default for chip-filling shapes, 6 = the one-wave-per-SIMD 256x256
     kernel with 128x128 wave tiles, gemm256w_kernel.h); K covers 1, 2, 3, 5, odd and even
     numbers of 64-deep (and, for the 256x128 kernel, 32-deep) K-tiles, i.e. every prologue / tail path; N = 128 / 132 the narrow shapes; repeated
@@ -180,7 +181,7 @@ def _qkv_case(batch, tokens, D):
     return A, W, bias, A.float() @ W.float().t() + bias
 
 
-@pytest.mark.parametrize("kernel", [1, 4, 5, 5 | (1024 << 4), 6, 6 | (1024 << 4)])
+@pytest.mark.parametrize("kernel", [1, 4, 5, 5 | (hip.DBG_GEMM_STORE8 << 4), 6, 6 | (hip.DBG_GEMM_STORE8 << 4)])
 @pytest.mark.parametrize("batch,tokens,D,hd", [(3, 256, 384, 64), (8, 64, 512, 64), (2, 256, 1024, 64), (2, 256, 1152, 72), (3, 64, 576, 72)])
 def test_gemm_qkv_split(dev, batch, tokens, D, hd, kernel):
     """Fused QKV projection: Q, K row-major, V transposed per head (timm Attention's qkv + reshape + permute, DiT.py:120), with

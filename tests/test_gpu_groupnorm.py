@@ -15,6 +15,8 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from lfm_amd import hip
+
 pytestmark = pytest.mark.gpu
 
 FAMILIES = ["centred", "offset30", "offset100", "offset300", "channel_offsets", "spike3000", "constant", "near_constant"]
@@ -85,14 +87,14 @@ def with_flags(flags, fn):
 
 
 # ------------------------------------------------------------------ lfm_groupnorm_f16 (UNets)
-# (N, HW, C, groups, film, flags, path): fused = HW <= 1024 and cpg % 8 == 0; rows = cpg % 4 == 0 with HW > 1024 or flag 16384; groups = the rest
+# (N, HW, C, groups, film, flags, path): fused = HW <= 1024 and cpg % 8 == 0; rows = cpg % 4 == 0 with HW > 1024 or flag UNET_GN_ROWS; groups = the rest
 UNET_CASES = [
     (8, 1024, 256, 32, True, 0, "fused, ADM 32x32 level (boundary HW = 1024)"),
     (3, 100, 512, 32, False, 0, "fused, ragged 10x10"),
     (2, 64, 2048, 32, True, 0, "fused, 64-wide groups"),
     (2, 4096, 128, 32, True, 0, "rows, ADM 64x64 level"),
     (3, 1025, 256, 32, False, 0, "rows, ragged (boundary HW = 1025)"),
-    (4, 256, 512, 32, True, 16384 << 4, "rows via flag 16384"),
+    (4, 256, 512, 32, True, hip.DBG_UNET_GN_ROWS << 4, "rows via flag 16384"),
     (2, 300, 96, 32, False, 0, "groups layout, cpg 3"),
     (2, 4100, 96, 32, True, 0, "groups layout, ragged slabs"),
     (1, 2048, 4096, 32, False, 0, "groups layout, cpg 128 (C / 8 > 256)"),
@@ -246,18 +248,18 @@ def conv_family(name, Cout, seed):
     raise ValueError(name)
 
 
-# (source, gemm_select value, n, H, Cin, Cout, ups, resid): statistics from the halo convolution (flag 16777216: at any size), the 256x128 / 256x256
-# implicit GEMMs (kernel selections 4 / 5), or the separate pass (flag 4194304); H = W the output size, n >= 2 so that slabs cross image boundaries
+# (source, gemm_select value, n, H, Cin, Cout, ups, resid): statistics from the halo convolution (flag CONV_HALO_SMALL: at any size), the 256x128 / 256x256
+# implicit GEMMs (kernel selections 4 / 5 with CONV_IMPLICIT_GEMM), or the separate pass (flag VAE_SEPARATE_STATS); H = W the output size, n >= 2 so that slabs cross image boundaries
 CONV_CASES = [
-    ("halo", 16777216 << 4, 2, 32, 128, 128, False, False),
-    ("halo", 16777216 << 4, 3, 32, 256, 256, True, True),
-    ("halo", 16777216 << 4, 2, 16, 128, 512, False, True),
-    ("gemm256x128", 4 | (8388608 << 4), 2, 32, 128, 128, True, True),
-    ("gemm256x128", 4 | (8388608 << 4), 3, 16, 256, 256, False, False),
-    ("gemm256x256", 5 | (8388608 << 4), 2, 16, 128, 512, True, False),
-    ("gemm256x256", 5 | (8388608 << 4), 2, 32, 128, 256, False, True),
-    ("separate", 4194304 << 4, 2, 32, 128, 256, False, True),
-    ("separate", 4194304 << 4, 3, 32, 128, 128, True, False),
+    ("halo", hip.DBG_CONV_HALO_SMALL << 4, 2, 32, 128, 128, False, False),
+    ("halo", hip.DBG_CONV_HALO_SMALL << 4, 3, 32, 256, 256, True, True),
+    ("halo", hip.DBG_CONV_HALO_SMALL << 4, 2, 16, 128, 512, False, True),
+    ("gemm256x128", 4 | (hip.DBG_CONV_IMPLICIT_GEMM << 4), 2, 32, 128, 128, True, True),
+    ("gemm256x128", 4 | (hip.DBG_CONV_IMPLICIT_GEMM << 4), 3, 16, 256, 256, False, False),
+    ("gemm256x256", 5 | (hip.DBG_CONV_IMPLICIT_GEMM << 4), 2, 16, 128, 512, True, False),
+    ("gemm256x256", 5 | (hip.DBG_CONV_IMPLICIT_GEMM << 4), 2, 32, 128, 256, False, True),
+    ("separate", hip.DBG_VAE_SEPARATE_STATS << 4, 2, 32, 128, 256, False, True),
+    ("separate", hip.DBG_VAE_SEPARATE_STATS << 4, 3, 32, 128, 128, True, False),
 ]
 
 

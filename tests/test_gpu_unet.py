@@ -86,7 +86,7 @@ def test_building_blocks_against_torch():
                                                    (2, 64, 64, 16, True)])
 def test_groupnorm_fused_small_path_vs_torch_and_three_kernel_path(N, HW, C, groups, film_on):
     """cpg % 8 == 0 and HW <= 4096: one fused launch (block per image x group chunk).  Against torch's group_norm and against the
-    three-kernel path (flag 16384) on the same data; both deterministic."""
+    three-kernel path (flag UNET_GN_ROWS) on the same data; both deterministic."""
     import torch.nn.functional as F
 
     from lfm_amd import hip
@@ -114,7 +114,7 @@ def test_groupnorm_fused_small_path_vs_torch_and_three_kernel_path(N, HW, C, gro
 
     fused = run()
     assert torch.equal(fused, run())
-    hip.gemm_select(16384 << 4)
+    hip.gemm_select(hip.DBG_UNET_GN_ROWS << 4)
     try:
         three = run()
     finally:
@@ -169,7 +169,7 @@ def test_conv3x3_split_k_on_the_256_kernel(N, H, Cin, Cout, mode):
     """The UNets' deep small-map convolutions AT BENCH BATCH SIZES (M = N H W >= 2048, >= 24 K-tiles per slice) take their split-K slices on the 256x256 kernel
     (csrc/gemm_kernel.h: splitk256_slices -- the stateful ASrcConv tap walk started in the middle of the K range, stride-2 / nearest-upsample source addressing,
     the fp32 slab epilogue of that kernel); round-5 advisor finding: no parity case reached it (every shape of test_conv3x3_split_k_small_maps has M <= 512).
-    Checked against torch's conv2d, against the 128x128 slices (flag 65536) and for bit-repeatability."""
+    Checked against torch's conv2d, against the 128x128 slices (flag GEMM_SPLITK128) and for bit-repeatability."""
     import torch.nn.functional as F
 
     from lfm_amd import hip
@@ -203,7 +203,7 @@ def test_conv3x3_split_k_on_the_256_kernel(N, H, Cin, Cout, mode):
             hip.gemm_select(0)
         return out
 
-    big, small = run(0), run(65536)
+    big, small = run(0), run(hip.DBG_GEMM_SPLITK128)
     assert torch.equal(big, run(0))
     assert rel_l2(big.reshape(N, H, H, Cout).permute(0, 3, 1, 2), ref) < 2e-3
     assert rel_l2(small.reshape(N, H, H, Cout).permute(0, 3, 1, 2), ref) < 2e-3
@@ -296,7 +296,7 @@ def test_unet_options_match_reference_golden(golden_dir, which):
 @pytest.mark.parametrize("N,heads,ch,T", [(2, 4, 128, 256), (3, 2, 64, 256), (2, 4, 64, 64), (1, 8, 128, 64), (2, 2, 96, 64)])
 def test_unet_attention_mfma_vs_torch_and_the_valu_kernel(N, heads, ch, T):
     """QKVAttentionLegacy (unet.py:310-334) on the MFMA kernel (T = 64 / 256, ch = 64 / 128) against fp32 torch on the same fp16 operands and
-    against the VALU kernel (flag 16); any other shape (ch = 96 here) must still take the VALU kernel and agree with torch.  Scores have a
+    against the VALU kernel (flag UNET_ATT_VALU); any other shape (ch = 96 here) must still take the VALU kernel and agree with torch.  Scores have a
     realistic spread (|s| up to ~8 after scaling), so a wrong max / sum would show."""
     from lfm_amd import hip
 
@@ -322,12 +322,12 @@ def test_unet_attention_mfma_vs_torch_and_the_valu_kernel(N, heads, ch, T):
     assert torch.isfinite(got).all()
     assert rel_l2(got, ref) < 2e-3
     if 64 * (T + 1) * 4 + 2 * T * (ch + 2) * 2 <= 160 * 1024:  # the VALU kernel keeps K, V and a score block in the LDS: T = 256 x ch = 128 does not fit
-        valu = run(16)
+        valu = run(hip.DBG_UNET_ATT_VALU)
         assert rel_l2(valu, ref) < 2e-3
         assert rel_l2(got, valu) < 2e-3
     else:
         with pytest.raises(hip.LfmHipError):
-            run(16)
+            run(hip.DBG_UNET_ATT_VALU)
 
 
 @pytest.mark.parametrize("N,HW,Ca,Cb,film_on", [(2, 256, 1024, 512, True), (2, 4096, 256, 256, True), (3, 64, 64, 32, False), (2, 1024, 512, 256, True),
@@ -372,7 +372,7 @@ def test_two_source_groupnorm_and_linear_equal_the_concatenated_path(N, HW, Ca, 
 @pytest.mark.parametrize("N,H,W,Cin,nch", [(2, 32, 48, 128, 3), (1, 64, 64, 256, 4), (3, 16, 16, 192, 1)])
 def test_halo_output_conv_vs_torch_and_the_implicit_gemm(N, H, W, Cin, nch):
     """lfm_conv3x3_out_f32 (the UNets' / the VAE decoder's <= 4-channel output convolution, fp16 NHWC -> fp32 NCHW) on the halo-tiled kernel
-    (conv3x3_halo_out_kernel, forced at these small sizes with flag 16777216) against torch and against the implicit GEMM (flag 8388608):
+    (conv3x3_halo_out_kernel, forced at these small sizes with flag CONV_HALO_SMALL) against torch and against the implicit GEMM (flag CONV_IMPLICIT_GEMM):
     border and interior tiles, 4 / 6 / 8 channel quarters, 1 / 3 / 4 real output channels."""
     import torch.nn.functional as F
 
@@ -400,16 +400,16 @@ def test_halo_output_conv_vs_torch_and_the_implicit_gemm(N, H, W, Cin, nch):
             hip.gemm_select(0)
         return out.cpu()
 
-    halo = run(16777216)
+    halo = run(hip.DBG_CONV_HALO_SMALL)
     assert torch.isfinite(halo).all()
     assert rel_l2(halo, ref) < 1e-4  # fp32 accumulation and output: only the summation order differs from torch
-    assert rel_l2(run(8388608), halo) < 1e-5
+    assert rel_l2(run(hip.DBG_CONV_IMPLICIT_GEMM), halo) < 1e-5
 
 
 @pytest.mark.parametrize("N,H,W,Cin,Cout", [(2, 24, 40, 4, 256), (3, 16, 16, 9, 128), (1, 33, 17, 8, 192), (2, 8, 8, 16, 64)])
 def test_input_conv_mfma_vs_torch_and_the_scalar_kernel(N, H, W, Cin, Cout):
     """lfm_conv3x3_in_f32 (fp32 NCHW latent -> fp16 NHWC, unet.py:416-420; 4 / 8 / 9 / 16 input channels = plain, semantic, inpainting, widest) on
-    the MFMA kernel with hi / lo-split operands against torch fp32 and against the scalar fp32 kernel (flag 1): the fp32 results agree to ~2^-20, so
+    the MFMA kernel with hi / lo-split operands against torch fp32 and against the scalar fp32 kernel (flag UNET_CONV_IN_SCALAR): the fp32 results agree to ~2^-20, so
     after the fp16 rounding of the output the two kernels differ by at most one ulp, and only rarely."""
     import torch.nn.functional as F
 
@@ -433,7 +433,7 @@ def test_input_conv_mfma_vs_torch_and_the_scalar_kernel(N, H, W, Cin, Cout):
             hip.gemm_select(0)
         return out.reshape(N, H, W, Cout).permute(0, 3, 1, 2).float().cpu()
 
-    got, scalar = run(0), run(1)
+    got, scalar = run(0), run(hip.DBG_UNET_CONV_IN_SCALAR)
     assert torch.isfinite(got).all()
     assert rel_l2(got, ref) < 5e-4 and rel_l2(scalar, ref) < 5e-4
     diff = (got - scalar).abs()

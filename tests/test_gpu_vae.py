@@ -111,7 +111,7 @@ def test_halo_conv_matches_torch_and_the_implicit_gemm(N, H, W, Cin, Cout, mode)
     xs = F.interpolate(x.float(), scale_factor=2, mode="nearest") if mode else x.float()
     ref = F.conv2d(xs, w.float(), b, padding=1)
     for resid, r in ((None, ref), (rd, ref + res.float())):
-        halo, gemm = run(16777216, resid), run(8388608, resid)  # flags: the halo kernel at any size / the implicit GEMM
+        halo, gemm = run(hip.DBG_CONV_HALO_SMALL, resid), run(hip.DBG_CONV_IMPLICIT_GEMM, resid)  # flags: the halo kernel at any size / the implicit GEMM
         assert torch.isfinite(halo).all()
         assert rel_l2(halo, r) < 1e-3
         assert float((halo - gemm).abs().max()) <= 2 * 2.0 ** -10 * float(r.abs().max())

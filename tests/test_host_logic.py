@@ -405,6 +405,104 @@ def test_conv_split_k_plan_for_the_small_maps():
     assert ws(0, 8, 64, 128) == 0
 
 
+# (M, N, K) -> kernel under lfm_gemm_select 0 / 1 / 4 / 5 / 6 for an instantiation that fits 32-bit offsets but cannot take kernel 6 (a convolution source)
+_GEMM_PLAN = [
+    ((16384, 3072, 1024), (5, 1, 4, 5, 5)),   # DiT-L/2 qkv, batch 64
+    ((16384, 1024, 1024), (5, 1, 4, 5, 5)),   # proj
+    ((16384, 4096, 1024), (5, 1, 4, 5, 5)),   # fc1
+    ((16384, 1024, 4096), (5, 1, 4, 5, 5)),   # fc2
+    ((16384, 2304, 768), (5, 1, 4, 5, 5)),    # DiT-B/2
+    ((16384, 768, 768), (5, 1, 4, 5, 5)),
+    ((16384, 384, 384), (4, 1, 4, 5, 5)),     # `mid`: fewer than 192 tiles of 256x256, at least 192 of 256x128
+    ((16384, 512, 512), (4, 1, 4, 5, 5)),
+    ((4096, 1536, 512), (4, 1, 4, 5, 5)),
+    ((32768, 256, 256), (4, 1, 4, 5, 5)),
+    ((4096, 512, 512), (1, 1, 4, 5, 5)),      # below 192 tiles of either
+    ((1048576, 128, 1152), (4, 1, 4, 5, 5)),  # `narrow`
+    ((262144, 256, 2304), (5, 1, 4, 5, 5)),   # VAE
+    ((65536, 512, 4608), (5, 1, 4, 5, 5)),
+    ((1024, 512, 4608), (1, 1, 4, 5, 5)),
+    ((256, 3072, 1024), (1, 1, 4, 5, 5)),
+    ((1048576, 64, 64), (1, 1, 4, 5, 5)),
+    ((16384, 1024, 96), (1, 1, 4, 1, 1)),     # K % 64 != 0: no 256x256 kernel
+    ((65536, 128, 32), (4, 1, 4, 1, 1)),      # K % 64 != 0, K % 32 == 0, narrow
+]
+
+
+def test_gemm_plan_is_the_kernel_that_runs():
+    """lfm_gemm_plan (no launch) = the one chooser every GEMM launch goes through (csrc/gemm_dispatch.h: gemm_choose): the kernel per shape under every
+    selection, for an instantiation that cannot take kernel 6 (a forced 6 runs 5), for one that can (a forced 6 runs 6, and so does the automatic choice with
+    LFM_OPT_GEMM_V6 wherever it picked 5), and for operands beyond 32-bit offsets (no 256x256 kernel: 1; the 256x128 kernel stays)."""
+    from lfm_amd import hip
+
+    sels = (0, 1, 4, 5, 6)
+    try:
+        for (M, N, K), want in _GEMM_PLAN:
+            for sel, k in zip(sels, want):
+                hip.gemm_select(sel)
+                assert hip.gemm_plan(M, N, K, caps=hip.GEMM_CAP_FITS) == k, (M, N, K, sel)
+                assert hip.gemm_plan(M, N, K, caps=hip.GEMM_CAP_FITS | hip.GEMM_CAP_V6) == (6 if sel == 6 and k == 5 else k), (M, N, K, sel, "v6-capable")
+                for caps in (0, hip.GEMM_CAP_V6):
+                    assert hip.gemm_plan(M, N, K, caps=caps) == (1 if k in (5, 6) else k), (M, N, K, sel, "does not fit")
+        hip.gemm_select(0)
+        hip.set_option(hip.OPT_GEMM_V6, 1)
+        for (M, N, K), want in _GEMM_PLAN:
+            assert hip.gemm_plan(M, N, K, caps=hip.GEMM_CAP_FITS | hip.GEMM_CAP_V6) == (6 if want[0] == 5 else want[0]), (M, N, K, "OPT_GEMM_V6")
+            assert hip.gemm_plan(M, N, K, caps=hip.GEMM_CAP_FITS) == want[0], (M, N, K, "OPT_GEMM_V6, not v6-capable")
+        assert [hip.gemm_plan(256, 256, 1024, batch=b) for b in (192, 191, 95)] == [6, 4, 1]  # a batch counts as tiles: 192 of 256x256; 382 / 190 of 256x128
+    finally:
+        hip.gemm_select(0)
+        hip.set_option(hip.OPT_GEMM_V6, 0)
+
+
+# pairs of flags of DIFFERENT consumers on the same bits (csrc/debug_flags.h says "shares" next to both): today's overlaps, acknowledged one by one.
+# A new pair fails test_debug_flags_have_one_definition until it is added here on purpose.
+_SHARED_FLAG_BITS = {
+    ("DBG_QKV_TRACE", "DBG_TRACE_GEMM"),
+    ("DBG_ATT_WIDE", "DBG_GEMM_GM4"),
+    ("DBG_GEMM_SPLITK128", "DBG_LN_BPERMUTE"),
+    ("DBG_LN_FOUR_ROWS", "DBG_QKV_NO_VT_WRITES"),
+    ("DBG_LN_TWO_ROWS", "DBG_QKV_NO_QK_WRITES"),
+    ("DBG_QKV_PER_ITEM", "DBG_VAE_SEPARATE_STATS"),
+    ("DBG_GEMM_ABL", "DBG_TRACE_COL"),
+    ("DBG_DIT_PATCH_ROUND1", "DBG_GEMM_ABL"), ("DBG_DIT_PATCH_ROUND1", "DBG_TRACE_COL"),
+    ("DBG_GEMM_ABL", "DBG_QKV_PER_ITEM"), ("DBG_QKV_PER_ITEM", "DBG_TRACE_COL"),
+    ("DBG_GEMM_ABL", "DBG_VAE_SEPARATE_STATS"), ("DBG_TRACE_COL", "DBG_VAE_SEPARATE_STATS"),
+    ("DBG_CONV_IMPLICIT_GEMM", "DBG_GEMM_ABL"), ("DBG_CONV_IMPLICIT_GEMM", "DBG_TRACE_COL"),
+    ("DBG_CONV_HALO_SMALL", "DBG_GEMM_ABL"), ("DBG_CONV_HALO_SMALL", "DBG_TRACE_COL"),
+    ("DBG_ATT_MODE", "DBG_GEMM_OPT"),
+    ("DBG_ATT_MODE", "DBG_QKV_NO_KEY_LOOP"), ("DBG_GEMM_OPT", "DBG_QKV_NO_KEY_LOOP"),
+    ("DBG_ATT_MODE", "DBG_QKV_TWO_KTILES"), ("DBG_GEMM_OPT", "DBG_QKV_TWO_KTILES"),
+}
+
+
+def test_debug_flags_have_one_definition():
+    """csrc/debug_flags.h defines every ablation flag of lfm_gemm_select once: lfm_amd.hip exports exactly the same names and values, no consumer uses a bit
+    twice, every bit is a flag bit (27 of them above the 4-bit kernel id), and the flags of different consumers that share bits are the acknowledged ones."""
+    from lfm_amd import hip
+
+    src = open(os.path.join(os.path.dirname(hip.__file__), "csrc", "debug_flags.h")).read()
+    header = {n: int(v) for n, v in re.findall(r"^constexpr int LFM_(DBG_\w+) = (\d+);", src, re.M)}
+    assert len(header) == len(re.findall(r"LFM_DBG_\w+ =", src)) > 30  # every definition has the one-line form this test reads
+    assert header == {n: v for n, v in vars(hip).items() if n.startswith("DBG_")}
+    bits = {}  # name (a field without _SHIFT / _MASK) -> bit mask
+    for n, v in header.items():
+        if n.endswith("_SHIFT"):
+            bits[n[:-6]] = header[n[:-6] + "_MASK"] << v
+        elif not n.endswith("_MASK"):
+            assert v & (v - 1) == 0, n  # a flag is one bit
+            bits[n] = v
+    assert all(0 < m < (1 << 27) for m in bits.values())
+    prefix = lambda n: n.split("_")[1]
+    shared = {(a, b) for a in bits for b in bits if a < b and bits[a] & bits[b]}
+    assert not [p for p in shared if prefix(p[0]) == prefix(p[1])]
+    assert shared == _SHARED_FLAG_BITS
+    for a, b in shared:  # the header says so next to both
+        for x, y in ((a, b), (b, a)):
+            line = [l for l in src.splitlines() if ("LFM_" + x + " =") in l or ("LFM_" + x + "_SHIFT =") in l or ("LFM_" + x + "_MASK =") in l]
+            assert any(y[4:] in l for l in line), (x, y)
+
+
 def test_seeded_edm_state_is_order_independent_and_fp16_exact():
     """oracle/edm_state.py: the weights of the full-size EDM fixtures are regenerated from (tensor name, shape, seed) on both sides -- the reference module in
     oracle/make_golden.py, the product module in the GPU tests -- so the draw must not depend on the order parameters are registered in, and every value must

@@ -17,11 +17,11 @@ Bh, heads, T = 64, 16, 256
 Q = torch.randn(Bh * T, heads * 64, device=dev).half(); K = torch.randn_like(Q); Vt = torch.randn(Bh, heads, 64, T, device=dev).half()
 X = torch.randn(Bh * T, 1024, device=dev); sh = torch.randn(1, 1024, device=dev); sc = torch.randn(1, 1024, device=dev)
 for rnd in range(3):
-    for name, fl in (("full", 0), ("memory phases only", 1 << 25), ("compute only", 2 << 25)):
+    for name, fl in (("full", 0), ("memory phases only", 1 << hip.DBG_ATT_MODE_SHIFT), ("compute only", 2 << hip.DBG_ATT_MODE_SHIFT)):
         hip.gemm_select(fl << 4)
         ms = timeit(lambda: hip.dit_attention(Q, K, Vt, Bh, heads, T))
         print(f"attention {name:20s}: {ms*1e3:6.1f} us", flush=True)
-    for name, fl in (("1 row / wave, DPP sums (ships)", 0), ("1 row / wave", 65536), ("2 rows / wave (round 1)", 524288), ("4 rows / wave", 262144)):
+    for name, fl in (("1 row / wave, DPP sums (ships)", 0), ("1 row / wave", hip.DBG_LN_BPERMUTE), ("2 rows / wave (round 1)", hip.DBG_LN_TWO_ROWS), ("4 rows / wave", hip.DBG_LN_FOUR_ROWS)):
         hip.gemm_select(fl << 4)
         out = hip.ln_modulate(X, sh, sc, T, 0)
         if fl == 0: base = out

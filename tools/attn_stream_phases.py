@@ -24,7 +24,7 @@ for stream in (1, 0):
             if mode == 3 and not stream: continue
             res = []
             for _ in range(5):
-                hip.gemm_select((mode << 25) << 4)
+                hip.gemm_select((mode << hip.DBG_ATT_MODE_SHIFT) << 4)
                 res.append(loop(lambda: hip.dit_attention(Q, K, Vt, Bh, heads, T)))
             hip.gemm_select(0)
             print(f"{'streamed' if stream else 'per-item'} kernel, {per_cu} workgroup(s) per CU, {names[mode]:40s}: median {statistics.median(res):6.1f} us  min {min(res):6.1f}")

@@ -1,4 +1,4 @@
-"""s_memtime timeline of the attention kernel's trace build (MODE 3: select flags 33554432 | 67108864) at the DiT-L/2 batch-64 shape: wave 0 of the
+"""s_memtime timeline of the attention kernel's trace build (ATT_MODE 3) at the DiT-L/2 batch-64 shape: wave 0 of the
 first workgroup (first round of workgroups) and of the last one (second round).  Where do the ~40k cycles of a workgroup go?  Written at the end of
 round 2, not yet run on hardware.  usage: python tools/attn_trace.py"""
 import ctypes as C, sys, torch
@@ -7,7 +7,7 @@ from lfm_amd import hip
 dev = torch.device("cuda:0")
 Bh, heads, T = 64, 16, 256
 Q = torch.randn(Bh * T, heads * 64, device=dev).half(); K = torch.randn_like(Q); Vt = torch.randn(Bh, heads, 64, T, device=dev).half()
-hip.gemm_select(((1 << 25) | (2 << 25)) << 4)
+hip.gemm_select((3 << hip.DBG_ATT_MODE_SHIFT) << 4)
 for _ in range(3): hip.dit_attention(Q, K, Vt, Bh, heads, T)
 torch.cuda.synchronize()
 buf = (C.c_ulonglong * 64)()

@@ -6,7 +6,7 @@ from lfm_amd import hip
 dev = torch.device("cuda:0")
 Bh, heads, T = 64, 16, 256
 Q = torch.randn(Bh * T, heads * 64, device=dev).half(); K = torch.randn_like(Q); Vt = torch.randn(Bh, heads, 64, T, device=dev).half()
-hip.gemm_select(((1 << 25) | (2 << 25)) << 4)
+hip.gemm_select((3 << hip.DBG_ATT_MODE_SHIFT) << 4)
 for _ in range(3): hip.dit_attention(Q, K, Vt, Bh, heads, T)
 torch.cuda.synchronize()
 n = Bh * heads

@@ -30,9 +30,9 @@ for name, nbytes in (("X", M * D * 4), ("A (attention output O)", M * D * 2), ("
     regions.append((name, off, nbytes)); off += al(nbytes)
 mode = sys.argv[4] if len(sys.argv) > 4 else ""
 if mode == "nofold": hip.set_option(hip.OPT_FOLD_LN, 0)       # separate LayerNorm-modulate launches
-if mode == "wide": hip.gemm_select(256 << 4)                  # attention: 4 waves x 64 queries
+if mode == "wide": hip.gemm_select(hip.DBG_ATT_WIDE << 4)     # attention: 4 waves x 64 queries (the same bit is GEMM_GM4)
 if mode == "v6": hip.set_option(hip.OPT_GEMM_V6, 1)           # the one-wave-per-SIMD GEMMs
-if mode == "noxcd": hip.gemm_select(16 << 4)
+if mode == "noxcd": hip.gemm_select(hip.DBG_UNET_ATT_VALU << 4)  # as recorded: flag 16, which no DiT kernel reads (GEMM_NO_XCD_REMAP is 128)
 print("mode:", mode or "shipped", flush=True)
 out_ref = m(t, x).clone(); ws = m._ws[1]
 assert off <= ws.numel(), (off, ws.numel())

@@ -1,4 +1,4 @@
-"""A/B of the 3x3 convolution kernels through the C ABI (lfm_conv3x3_f16): the halo-tiled direct kernel (default) against the implicit GEMM (flag 8388608)
+"""A/B of the 3x3 convolution kernels through the C ABI (lfm_conv3x3_f16): the halo-tiled direct kernel (default) against the implicit GEMM (flag CONV_IMPLICIT_GEMM)
 on the shapes of the VAE decoder's last level and of the ADM UNet.  Usage: python tools/conv_probe.py [reps]"""
 import os
 import sys
@@ -25,7 +25,7 @@ for N, H, W, Cin, Cout in SHAPES:
     out = torch.empty(N * H * W, Cout, device=dev, dtype=torch.float16)
     flop = 2.0 * N * H * W * Cout * 9 * Cin
     res = {}
-    for name, flags in (("implicit", 8388608), ("halo", 0)) + tuple((f"halo+flag{f}", f) for f in EXTRA):
+    for name, flags in (("implicit", hip.DBG_CONV_IMPLICIT_GEMM), ("halo", 0)) + tuple((f"halo+flag{f}", f) for f in EXTRA):
         hip.gemm_select(flags << 4)
         for _ in range(2):
             hip.check(L.lfm_conv3x3_f16(hip.ptr(x), hip.ptr(w), hip.ptr(b), None, hip.ptr(out), N, H, W, Cin, Cout, 0, hip.stream_ptr()), "conv")

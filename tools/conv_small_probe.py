@@ -1,5 +1,5 @@
 """The UNets' 3x3 convolutions on 16x16 (and smaller) maps: the split-K implicit GEMM they take today (fewer than 256 halo tiles) against the
-halo-tiled direct kernel forced onto the same shapes (flag 16777216), through lfm_conv3x3_f16_ws with the workspace the models pass.
+halo-tiled direct kernel forced onto the same shapes (flag CONV_HALO_SMALL), through lfm_conv3x3_f16_ws with the workspace the models pass.
 Usage: python tools/conv_small_probe.py [reps]"""
 import os
 import sys
@@ -25,7 +25,7 @@ for N, H, W, Cin, Cout in SHAPES:
     ws = torch.empty(max(wsb, 16), device=dev, dtype=torch.uint8)
     flop = 2.0 * N * H * W * Cout * 9 * Cin
     res, outs = {}, {}
-    for name, flags in (("today", 0), ("implicit", 8388608), ("halo forced", 16777216)):
+    for name, flags in (("today", 0), ("implicit", hip.DBG_CONV_IMPLICIT_GEMM), ("halo forced", hip.DBG_CONV_HALO_SMALL)):
         out = torch.empty(N * H * W, Cout, device=dev, dtype=torch.float16)
         hip.gemm_select(flags << 4)
 

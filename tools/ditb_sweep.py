@@ -21,7 +21,7 @@ def timeit(n=6):
     for _ in range(n): run()
     e.record(); torch.cuda.synchronize()
     return s.elapsed_time(e) / n
-variants = {"default": (0, 0, 1), "tile groups of 8 (flag 32)": (32, 0, 1), "tile groups of 2 (flag 64)": (64, 0, 1), "no XCD remap (flag 128)": (128, 0, 1),
+variants = {"default": (0, 0, 1), "tile groups of 8 (flag 32)": (hip.DBG_GEMM_GM8, 0, 1), "tile groups of 2 (flag 64)": (hip.DBG_GEMM_GM2, 0, 1), "no XCD remap (flag 128)": (hip.DBG_GEMM_NO_XCD_REMAP, 0, 1),
             "one-wave-per-SIMD GEMMs (LFM_OPT_GEMM_V6)": (0, 1, 1), "per-item attention": (0, 0, 0)}
 res = {k: [] for k in variants}
 ref = None

@@ -16,7 +16,7 @@ def timeit(fn, n=20, warm=3):
 for M, N, K in ((16384, 4096, 1024), (16384, 1024, 4096), (16384, 1024, 1024)):
     A = (torch.randn(M, K, device=dev) * 0.5).half(); W = (torch.randn(N, K, device=dev) * 0.03).half(); b = torch.randn(N, device=dev)
     out = torch.zeros(M, N, device=dev, dtype=torch.float16)
-    f = lambda k, opt, noepi: k | (((4 if noepi else 0) | (opt << 25)) << 4)
+    f = lambda k, opt, noepi: k | (((hip.DBG_GEMM_NO_EPILOGUE if noepi else 0) | (opt << hip.DBG_GEMM_OPT_SHIFT)) << 4)
     variants = [(f"v{k} OPT {o}{' no epilogue' if ne else ''}", f(k, o, ne)) for ne in (0, 1) for k, o in ((5, 0), (5, 1), (5, 2), (5, 3), (6, 0), (6, 1))]
     hip.gemm_select(5); ref = hip.gemm_f16(A, W, b, epilogue=1).clone()
     same = {}

@@ -1,5 +1,5 @@
 """Is the fp16-output epilogue bound per CU or chip-wide?  fc1-shaped GEMM (N 4096, K 1024, GELU epilogue) with 64 / 128 / 256 / 1024 tiles
-(one tile per CU on a quarter / half / all of the chip, then four per CU), with and without the epilogue (flag 4), kernel v5 forced."""
+(one tile per CU on a quarter / half / all of the chip, then four per CU), with and without the epilogue (flag GEMM_NO_EPILOGUE), kernel v5 forced."""
 import sys, statistics, torch
 sys.path.insert(0, "."); sys.path.insert(0, "/root/repo")
 from lfm_amd import hip
@@ -21,7 +21,7 @@ for epi in (1, 3):
     fn = lambda: hip.gemm_f16(A, W, b, epilogue=epi, out=out, gate=gate, gate_stride=NN, tokens=256)
     res = {}
     for rnd in range(5):
-        for name, sel in (("full", 5), ("noepi", 5 | (4 << 4))):
+        for name, sel in (("full", 5), ("noepi", 5 | (hip.DBG_GEMM_NO_EPILOGUE << 4))):
             hip.gemm_select(sel); res.setdefault(name, []).append(timeit(fn))
     hip.gemm_select(0)
     f, ne = statistics.median(res["full"]) * 1e3, statistics.median(res["noepi"]) * 1e3

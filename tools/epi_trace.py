@@ -1,4 +1,4 @@
-"""s_memtime stamps of the epilogue of the 16x16x32 GEMM (kernel 5, flag 2): where do the ~7.5 us per tile go?
+"""s_memtime stamps of the epilogue of the 16x16x32 GEMM (kernel 5, flag TRACE_GEMM): where do the ~7.5 us per tile go?
 slots: 0 = K loop done; per 32-row block i: 1+4i scratch filled, 2+4i read back, 3+4i aux loads returned, 4+4i stores issued; 17 = done.
 (transposed V tiles of the QKV epilogue: only 4+4i -- after each of the four 32-column x 64-row passes -- and 17.)
     python tools/epi_trace.py            # fc1+GELU, bias-only fp16, gated fp32 residual (proj / fc2 shapes), QKV (a Q tile and a V^T tile)
@@ -26,7 +26,7 @@ def show(tag, swapped=False):
 
 def run(tag, epi, N, K, col=0, flags=0):
     A = (torch.randn(M, K, device=dev) * 0.5).half(); W = (torch.randn(N, K, device=dev) * 0.03).half(); b = torch.randn(N, device=dev)
-    hip.gemm_select(5 | ((2 | flags | (col << 21)) << 4))
+    hip.gemm_select(5 | ((hip.DBG_TRACE_GEMM | flags | (col << hip.DBG_TRACE_COL_SHIFT)) << 4))
     for rep in range(2):
         if epi == "qkv":
             hip.gemm_qkv_f16(A, W, b, 64, 256)
@@ -44,4 +44,4 @@ run("gate+resid fp32, proj (N 1024, K 1024)", 3, 1024, 1024)
 run("gate+resid fp32, fc2  (N 1024, K 4096)", 3, 1024, 4096)
 run("qkv, Q tile  (N 3072, K 1024)", "qkv", 3072, 1024, 0)
 run("qkv, V^T tile (N 3072, K 1024)", "qkv", 3072, 1024, 8)
-run("qkv, V^T tile, stores skipped", "qkv", 3072, 1024, 8, flags=131072)
+run("qkv, V^T tile, stores skipped", "qkv", 3072, 1024, 8, flags=hip.DBG_TRACE_NO_STORES)

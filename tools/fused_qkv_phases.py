@@ -1,5 +1,5 @@
 """Phase split of the fused QKV + attention kernel on an LFM_MEASURE build (LFM_HIP_LIBRARY=...), to be run under rocprofv3 --kernel-trace --stats: eager DiT
-forwards with the kernel's measurement flags (lfm_gemm_select flags 33554432: no key loop, 67108864: one K-tile only); read the kernel's own duration from the
+forwards with the kernel's measurement flags (lfm_gemm_select flags QKV_NO_KEY_LOOP = 33554432, QKV_TWO_KTILES = 67108864); read the kernel's own duration from the
 stats (whole forwards mislead: garbage activations are cheap operands for the kernels downstream).  usage: fused_qkv_phases.py FLAGS [model] [batch] [fused 0/1]"""
 import sys, torch
 sys.path.insert(0, "."); sys.path.insert(0, "/root/repo")

@@ -10,7 +10,7 @@ for p in m.parameters():
     if not bool(p.any()): torch.nn.init.normal_(p, std=0.02)
 m = m.to(dev).eval()
 x = torch.randn(64, 4, 32, 32, device=dev); t = torch.tensor(0.5, device=dev)
-hip.gemm_select((2 | (int(sys.argv[1]) if len(sys.argv) > 1 else 0)) << 4)
+hip.gemm_select((hip.DBG_QKV_TRACE | (int(sys.argv[1]) if len(sys.argv) > 1 else 0)) << 4)
 for _ in range(3): m(t, x)
 torch.cuda.synchronize()
 buf = (C.c_ulonglong * 64)()

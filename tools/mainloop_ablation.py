@@ -1,5 +1,5 @@
-"""(M) Where does the 256x256 GEMM's main loop go?  fc1 / fc2 shapes with the epilogue switched off (flag 4) and the main-loop ablations of the
-LFM_MEASURE build (flags n << 21: 1 = no LDS-DMA after the prologue, 2 = no fragment reads, 3 = neither, 4 = static priority, 5 = 3 without barriers, 6 = 3 with one barrier per K-tile), interleaved medians.
+"""(M) Where does the 256x256 GEMM's main loop go?  fc1 / fc2 shapes with the epilogue switched off (flag GEMM_NO_EPILOGUE) and the main-loop ablations of the
+LFM_MEASURE build (field GEMM_ABL = n: 1 = no LDS-DMA after the prologue, 2 = no fragment reads, 3 = neither, 4 = static priority, 5 = 3 without barriers, 6 = 3 with one barrier per K-tile), interleaved medians.
 usage: LFM_MEASURE=1 python -m lfm_amd._build && python tools/mainloop_ablation.py"""
 import statistics, sys, torch
 sys.path.insert(0, "."); sys.path.insert(0, "/root/repo")
@@ -16,9 +16,10 @@ def timeit(fn, n=20, warm=3):
 for M, N, K in ((16384, 4096, 1024), (16384, 1024, 4096)):
     A = (torch.randn(M, K, device=dev) * 0.5).half(); W = (torch.randn(N, K, device=dev) * 0.03).half(); b = torch.randn(N, device=dev)
     out = torch.zeros(M, N, device=dev, dtype=torch.float16)
-    variants = [("full kernel", 0), ("no epilogue", 4), ("no epilogue, static prio", 4 | (4 << 21)), ("no epilogue, no DMA", 4 | (1 << 21)),
-                ("no epilogue, no fragment reads", 4 | (2 << 21)), ("no epilogue, MFMA + barriers only", 4 | (3 << 21)), ("no epilogue, MFMA only, no barriers", 4 | (5 << 21)), ("no epilogue, MFMA only, 1 barrier per K-tile", 4 | (6 << 21)), ("no epilogue, MFMA only, no barriers, PINNED acc", 4 | (7 << 21)),
-                ("no epilogue, full loop, PINNED acc", 4 | (7 << 21) | (1 << 24)), ("full kernel, PINNED acc", (7 << 21) | (1 << 24))]
+    NE, abl = hip.DBG_GEMM_NO_EPILOGUE, lambda n: n << hip.DBG_GEMM_ABL_SHIFT  # variant 8 = 7 with the field's top bit
+    variants = [("full kernel", 0), ("no epilogue", NE), ("no epilogue, static prio", NE | abl(4)), ("no epilogue, no DMA", NE | abl(1)),
+                ("no epilogue, no fragment reads", NE | abl(2)), ("no epilogue, MFMA + barriers only", NE | abl(3)), ("no epilogue, MFMA only, no barriers", NE | abl(5)), ("no epilogue, MFMA only, 1 barrier per K-tile", NE | abl(6)), ("no epilogue, MFMA only, no barriers, PINNED acc", NE | abl(7)),
+                ("no epilogue, full loop, PINNED acc", NE | abl(15)), ("full kernel, PINNED acc", abl(15))]
     res = {n: [] for n, _ in variants}
     for rnd in range(5):
         for name, fl in variants:

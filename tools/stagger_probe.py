@@ -32,7 +32,7 @@ for name, N, K, epi in [] if ONLY == "attn" else [("fc1  bias+gelu", 4096, 1024,
     for rnd in range(3):
         for tk in TICKS:
             hip.check(L.lfm_set_option(3, tk), "opt")
-            for sel, nm in ((4, "v4"), (4 | (4 << 4), "v4 no epilogue")):
+            for sel, nm in ((4, "v4"), (4 | (hip.DBG_GEMM_NO_EPILOGUE << 4), "v4 no epilogue")):
                 hip.gemm_select(sel); res.setdefault((nm, tk), []).append(timeit(run))
         hip.check(L.lfm_set_option(3, 0), "opt")
         hip.gemm_select(5); res.setdefault(("v5", 0), []).append(timeit(run))

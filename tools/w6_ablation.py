@@ -16,7 +16,7 @@ def timeit(fn, n=20, warm=3):
 for M, N, K in ((16384, 4096, 1024), (16384, 1024, 4096)):
     A = (torch.randn(M, K, device=dev) * 0.5).half(); W = (torch.randn(N, K, device=dev) * 0.03).half(); b = torch.randn(N, device=dev)
     out = torch.zeros(M, N, device=dev, dtype=torch.float16)
-    f = lambda k, abl: k | ((4 | (abl << 21)) << 4)
+    f = lambda k, abl: k | ((hip.DBG_GEMM_NO_EPILOGUE | (abl << hip.DBG_GEMM_ABL_SHIFT)) << 4)
     variants = [("v5 no epilogue", f(5, 0)), ("v5 MFMA + barriers only", f(5, 3)), ("v5 MFMA only", f(5, 5)),
                 ("v6 no epilogue", f(6, 0)), ("v6 no DMA", f(6, 1)), ("v6 no reads", f(6, 2)), ("v6 MFMA + barrier only", f(6, 3)), ("v6 MFMA only", f(6, 4)),
                 ("v6 DMA 2/group early", f(6, 8))]

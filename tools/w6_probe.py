@@ -36,9 +36,9 @@ for name, N, K, epi in shapes:
         else: outs[k] = [run().clone()]
     hip.gemm_select(0)
     same = all(torch.equal(a, c) for a, c in zip(outs[5], outs[6]))
-    variants = [("v5 full", 5), ("v6 full", 6), ("v5 no epilogue", 5 | (4 << 4)), ("v6 no epilogue", 6 | (4 << 4))]
+    variants = [("v5 full", 5), ("v6 full", 6), ("v5 no epilogue", 5 | (hip.DBG_GEMM_NO_EPILOGUE << 4)), ("v6 no epilogue", 6 | (hip.DBG_GEMM_NO_EPILOGUE << 4))]
     if epi == 1:
-        variants += [("v6 no epi, no DMA", 6 | ((4 | (1 << 21)) << 4)), ("v6 no epi, no reads", 6 | ((4 | (2 << 21)) << 4)), ("v6 no epi, MFMA+barrier only", 6 | ((4 | (3 << 21)) << 4))]
+        variants += [("v6 no epi, no DMA", 6 | ((hip.DBG_GEMM_NO_EPILOGUE | (1 << hip.DBG_GEMM_ABL_SHIFT)) << 4)), ("v6 no epi, no reads", 6 | ((hip.DBG_GEMM_NO_EPILOGUE | (2 << hip.DBG_GEMM_ABL_SHIFT)) << 4)), ("v6 no epi, MFMA+barrier only", 6 | ((hip.DBG_GEMM_NO_EPILOGUE | (3 << hip.DBG_GEMM_ABL_SHIFT)) << 4))]
     res = {n: [] for n, _ in variants}
     for rnd in range(5):
         for n, sel in variants:
