@@ -430,6 +430,7 @@ __global__ __launch_bounds__(512) void qkv_attention_kernel(const half_t* __rest
       nrow_m = ntile_m * G256_BM + (int)threadIdx.x;
       nrow_part = ep.st.part + (long)nrow_m * ep.st.tiles_p * 2;
     }
+    static_assert(G256H_MAX_PARTS == 5, "next_req reloads the row partials as rsr.p[0] .. p[4]: a further slot would keep the first item's value");
     auto next_req = [&](int idx) {
       if (!has_next) return;
       __builtin_amdgcn_sched_barrier(0);
