@@ -3,110 +3,7 @@
 // implicit-GEMM 3x3 convolution (same / nearest-2x-upsampled input / stride 2), 1x1 convolution / linear with residual,
 // general GroupNorm(32) with optional FiLM scale-shift and SiLU, channel concat, small-T attention, timestep embedding.
 #include "../../include/lfm_hip.h"
-#include "gemm_dispatch.h"
-#include "conv_halo_kernel.h"
-
-// ------------------------------------------------------------------ implicit-GEMM A source, NHWC fp16, 3x3, pad 1
-// MODE 0: same size.  MODE 1: input is nearest-2x upsampled on the fly (Upsample, unet.py:73-100).
-// MODE 2: stride 2 (Downsample, unet.py:103-128): output (oy,ox) reads input (2oy+dy-1, 2ox+dx-1).
-template <int MODE>
-struct ASrcConv {
-  const half_t* in;
-  const half_t* zeros;
-  int H, W, Cin, M;  // OUTPUT spatial size; M = N*H*W
-  int tap, ci0;
-  int tap_begin, ci_begin;  // split-K: slice bz starts at k = bz * bs (init), a multiple of 64 <= Cin granularity
-  __device__ __forceinline__ void init(int bz, long bs) {
-    const long k = (long)bz * bs;
-    tap_begin = (int)(k / Cin);
-    ci_begin = (int)(k - (long)tap_begin * Cin);
-  }
-  struct Row {
-    int n, y, x;
-  };
-  __device__ __forceinline__ Row row(int m) const {
-    if (m >= M) m = M - 1;
-    Row r;
-    r.x = m % W;
-    const int t = m / W;
-    r.y = t % H;
-    r.n = t / H;
-    return r;
-  }
-  __device__ __forceinline__ void begin_tile(int kt, int bk) {
-    if (kt == 0) {
-      tap = tap_begin;
-      ci0 = ci_begin;
-    } else {
-      ci0 += bk;
-      if (ci0 >= Cin) {
-        ci0 = 0;
-        ++tap;
-      }
-    }
-  }
-  __device__ __forceinline__ const half_t* ptr(const Row& r, int koff) const {
-    const int dy = tap / 3 - 1, dx = tap % 3 - 1;
-    if (MODE == 2) {
-      const int Hi = H * 2, Wi = W * 2;
-      const int iy = 2 * r.y + dy, ix = 2 * r.x + dx;
-      if ((unsigned)iy >= (unsigned)Hi || (unsigned)ix >= (unsigned)Wi) return zeros + koff;
-      return in + (((long)r.n * Hi + iy) * Wi + ix) * Cin + ci0 + koff;
-    }
-    const int iy = r.y + dy, ix = r.x + dx;
-    if ((unsigned)iy >= (unsigned)H || (unsigned)ix >= (unsigned)W) return zeros + koff;
-    const int Hs = H >> (MODE == 1), Ws = W >> (MODE == 1);
-    return in + (((long)r.n * Hs + (iy >> (MODE == 1))) * Ws + (ix >> (MODE == 1))) * Cin + ci0 + koff;
-  }
-};
-
-struct EpiResidF16 {  // out = acc + bias (+ residual) -> fp16
-  half_t* C;
-  long ldc;
-  const float* bias;
-  const half_t* resid;
-  struct Aux {
-    f32x4 b;
-    half4_t r;
-  };
-  __device__ __forceinline__ Aux load(int m, int n) const {
-    Aux a;
-    a.b = bias ? *(const f32x4*)(bias + n) : (f32x4){0.f, 0.f, 0.f, 0.f};
-    a.r = resid ? *(const half4_t*)(resid + (long)m * ldc + n) : (half4_t){0, 0, 0, 0};
-    return a;
-  }
-  __device__ __forceinline__ void store(int m, int n, f32x4 v, const Aux& a) const {
-    v += a.b;
-    half4_t h = {(half_t)(v.x + (float)a.r.x), (half_t)(v.y + (float)a.r.y), (half_t)(v.z + (float)a.r.z), (half_t)(v.w + (float)a.r.w)};
-    *(half4_t*)(C + (long)m * ldc + n) = h;
-  }
-  __device__ __forceinline__ bool wide_ok() const { return (ldc & 7) == 0 && ((uintptr_t)C & 15) == 0 && (!resid || ((uintptr_t)resid & 15) == 0); }
-  __device__ __forceinline__ void store8(int m, int n, f32x4 lo, f32x4 hi, const Aux& al, const Aux& ah) const {
-    lo += al.b;
-    hi += ah.b;
-    half8_t h = {(half_t)(lo.x + (float)al.r.x), (half_t)(lo.y + (float)al.r.y), (half_t)(lo.z + (float)al.r.z), (half_t)(lo.w + (float)al.r.w),
-                 (half_t)(hi.x + (float)ah.r.x), (half_t)(hi.y + (float)ah.r.y), (half_t)(hi.z + (float)ah.r.z), (half_t)(hi.w + (float)ah.r.w)};
-    *(half8_t*)(C + (long)m * ldc + n) = h;
-  }
-};
-
-struct EpiNCHWF32 {  // Cout <= 4 output conv: fp32 NCHW, channels beyond nch are padding
-  float* out;
-  const float* bias;  // [4]
-  int HW, nch;
-  typedef f32x4 Aux;
-  __device__ __forceinline__ Aux load(int, int n) const { return *(const f32x4*)(bias + n); }
-  __device__ __forceinline__ void store(int m, int n, f32x4 v, const Aux& b) const {
-    if (n != 0) return;
-    v += b;
-    const int img = m / HW, pix = m - img * HW;
-    float* o = out + (long)img * nch * HW + pix;
-    o[0] = v.x;
-    if (nch > 1) o[HW] = v.y;
-    if (nch > 2) o[2 * HW] = v.z;
-    if (nch > 3) o[3 * HW] = v.w;
-  }
-};
+#include "nhwc_common.h"  // ASrcConv<MODE>, EpiResidF16, EpiNCHWF32, GnIn, gn_stats_rows_kernel, conv_halo_allowed
 
 static __device__ half_t g_zero_page[64];  // zero padding rows for the conv gathers (zero-initialised device global)
 
@@ -145,7 +42,7 @@ extern "C" size_t lfm_conv3x3_workspace_bytes(int N, int H, int W, int Cin, int 
 template <int MODE>
 static int conv3x3_mode(const half_t* xi, const half_t* z, const half_t* wi, const EpiResidF16& epi, int H, int W, int Cin, int Cout, int M, float* ws,
                         size_t ws_bytes, hipStream_t st) {
-  ASrcConv<MODE> a{xi, z, H, W, Cin, M, 0, 0, 0, 0};
+  ASrcConv<MODE> a{xi, z, H, W, Cin, M};
   const int rc = launch_gemm_splitk_src(a, wi, 9L * Cin, M, Cout, 9 * Cin, epi, ws, ws_bytes, st, CONV_SPLITK_MAX_TILES, CONV_SPLITK_MAX_WG);
   if (rc != 1) return rc;
   return launch_gemm_auto(a, wi, 9L * Cin, M, Cout, 9 * Cin, epi, st);
@@ -167,7 +64,7 @@ extern "C" int lfm_conv3x3_f16_ws(const void* in, const void* w, const float* bi
   float* ws = (float*)workspace;
   // plain and upsample-fused 3x3 convolutions on 16-aligned maps that fill the chip: the halo-tiled direct kernel (conv_halo_kernel.h);
   // CONV_IMPLICIT_GEMM: the implicit GEMM instead (A/B and parity tests)
-  if (mode != 2 && lfm_gemm_selected() == 0 && !(lfm_gemm_debug_flags() & LFM_DBG_CONV_IMPLICIT_GEMM) && !(((uintptr_t)out | (uintptr_t)resid) & 15)) {
+  if (mode != 2 && conv_halo_allowed(out, resid)) {
     const int rc = mode == 1 ? launch_conv3x3_halo<1>(xi, z, wi, N, H, W, Cin, Cout, epi, st) : launch_conv3x3_halo<0>(xi, z, wi, N, H, W, Cin, Cout, epi, st);
     if (rc != 1) return rc;
   }
@@ -189,11 +86,11 @@ extern "C" int lfm_conv3x3_out_f32(const void* in, const void* w4, const float* 
   if (!z) return LFM_ERR_LAUNCH;
   const int M = N * H * W;
   const EpiNCHWF32 eo{out_nchw, bias4, H * W, nch};
-  if (lfm_gemm_selected() == 0 && !(lfm_gemm_debug_flags() & LFM_DBG_CONV_IMPLICIT_GEMM)) {  // flag: the implicit GEMM (A/B)
+  if (conv_halo_allowed()) {  // (fp32 scalar stores: no alignment term)
     const int rc = launch_conv3x3_halo_out((const half_t*)in, z, (const half_t*)w4, N, H, W, Cin, eo, (hipStream_t)stream);
     if (rc != 1) return rc;
   }
-  return launch_gemm_tn(ASrcConv<0>{(const half_t*)in, z, H, W, Cin, M, 0, 0, 0, 0}, (const half_t*)w4, 9L * Cin, M, 4, 9 * Cin, eo, (hipStream_t)stream);
+  return launch_gemm_tn(ASrcConv<0>{(const half_t*)in, z, H, W, Cin, M}, (const half_t*)w4, 9L * Cin, M, 4, 9 * Cin, eo, (hipStream_t)stream);
 }
 
 extern "C" int lfm_linear_f16(const void* A, long lda, const void* W, long ldw, void* C, long ldc, int M, int N, int K, const float* bias,
@@ -328,12 +225,11 @@ static int launch_conv_in_mfma(const float* x, const float* w, const float* b, h
   const int KS = cdiv(Cin * 9, 16), LD = KS * 16 + 8;
   const size_t lds = ((size_t)2 * Cout + 2 * CIM_PIX) * LD * 2;
   if (lds > 160 * 1024) return 1;
-  static unsigned long long attr_set = 0;
-  int devid = 0;
-  (void)hipGetDevice(&devid);
-  if (!((attr_set >> (devid & 63)) & 1)) {
+  static lfm_device_mask attr_set{0};
+  const unsigned long long dbit = lfm_device_bit();
+  if (lfm_device_todo(attr_set, dbit)) {
     if (hipFuncSetAttribute((const void*)conv_in_mfma_kernel<NT>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) return LFM_ERR_LAUNCH;
-    attr_set |= 1ull << (devid & 63);
+    lfm_device_done(attr_set, dbit);
   }
   const long chunks = cdiv((long)N * H * W, CIM_PIX);
   const int grid = (int)(chunks < 1024 ? chunks : 1024);  // a workgroup pays the weight split once and then walks its chunks
@@ -377,20 +273,8 @@ extern "C" int lfm_conv3x3_in_f32(const float* x_nchw, const float* w, const flo
 //           group's first slot mean, then
 //           a = rstd*gamma*(1+scale),  b = (beta - mean*rstd*gamma)*(1+scale) + shift     (FiLM optional)
 // 3) apply: y = silu?(x*a + b), 8 channels per thread
-// GroupNorm input = the channel concat [a | b] of two NHWC tensors read in place (th.cat([h, hs.pop()], dim=1) feeding a ResBlock's first
-// GroupNorm, unet.py:649 + :171: the concatenated tensor is never materialised); b == nullptr: a alone (Ca == C).  Ca % 8 == 0.
-struct GnIn {
-  const half_t* a;
-  const half_t* b;
-  int Ca, Cb;
-  __device__ __forceinline__ const half_t* at(long pix, int c) const { return c < Ca ? a + pix * Ca + c : b + pix * Cb + (c - Ca); }
-  // a thread that owns channel c of every pixel of image n: first pixel's address and the row stride of the tensor that holds c
-  __device__ __forceinline__ const half_t* column(long pix0, int c, long& stride) const {
-    const bool fa = c < Ca;
-    stride = fa ? Ca : Cb;
-    return fa ? a + pix0 * Ca + c : b + pix0 * Cb + (c - Ca);
-  }
-};
+// GnIn (one tensor, or the channel concat of two read in place), the row-wise statistics kernel gn_stats_rows_kernel (cpg % 4 == 0, C / 8 <= 256)
+// and the slot / merge arithmetic gn_slot, gn_merge: nhwc_common.h
 
 template <int VEC>
 __global__ __launch_bounds__(256) void gn_stats_general_kernel(GnIn in, float* __restrict__ part, int HW, int C, int cpg,
@@ -429,62 +313,7 @@ __global__ __launch_bounds__(256) void gn_stats_general_kernel(GnIn in, float* _
   if (threadIdx.x == 0) {  // slot [n][slab][g] = {mean, M2}
     float* o = part + (((long)n * gridDim.z + blockIdx.z) * G + g) * 2;
     const float ss = rs[0] + rs[1] + rs[2] + rs[3], qq = rq[0] + rq[1] + rq[2] + rq[3], rc = 1.f / (float)total / (float)VEC;
-    o[0] = k + ss * rc;
-    o[1] = fmaxf(qq - ss * ss * rc, 0.f);
-  }
-}
-
-// fast path (cpg % 4 == 0, C/8 <= 256): a block reads a slab of pixels with FULL rows (coalesced); thread = channel octet x pixel
-// row; per half-octet partial sums are folded through LDS (fixed order) and leave as slot [n][slab][half-octet] of the partial buffer.
-__global__ __launch_bounds__(256) void gn_stats_rows_kernel(GnIn in, float* __restrict__ part, int HW, int C, int pix_per_block) {
-  __shared__ float red[4][256];
-  const int n = blockIdx.y, c8n = C / 8, tid = threadIdx.x;
-  const int rows = 256 / c8n;
-  const int oct = tid % c8n, prow = tid / c8n;
-  const int p0 = blockIdx.x * pix_per_block;
-  const int p1 = min(p0 + pix_per_block, HW);
-  float s[2] = {0.f, 0.f}, q[2] = {0.f, 0.f};
-  long XS;  // row stride of the tensor that holds this thread's octet
-  const half_t* base = in.column((long)n * HW, oct * 8, XS);
-  const float k[2] = {(float)base[(long)p0 * XS], (float)base[(long)p0 * XS + 4]};  // the shifts: pixel p0 of this slab, per half-octet
-  if (prow < rows) {
-    auto add = [&](const half8_t& v) {
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const float f = (float)v[j] - k[j >> 2];
-        s[j >> 2] += f;
-        q[j >> 2] += f * f;
-      }
-    };
-    int p = p0 + prow;
-    for (; p + 3 * rows < p1; p += 4 * rows) {  // four independent loads in flight (one per iteration ran at 1.5 TB/s), summed in pixel order
-      const half8_t v0 = *(const half8_t*)(base + (long)p * XS), v1 = *(const half8_t*)(base + (long)(p + rows) * XS);
-      const half8_t v2 = *(const half8_t*)(base + (long)(p + 2 * rows) * XS), v3 = *(const half8_t*)(base + (long)(p + 3 * rows) * XS);
-      add(v0);
-      add(v1);
-      add(v2);
-      add(v3);
-    }
-    for (; p < p1; p += rows) add(*(const half8_t*)(base + (long)p * XS));
-  }
-  red[0][tid] = s[0];
-  red[1][tid] = s[1];
-  red[2][tid] = q[0];
-  red[3][tid] = q[1];
-  __syncthreads();
-  if (tid < c8n) {
-    for (int r = 1; r < rows; ++r) {
-      s[0] += red[0][tid + r * c8n];
-      s[1] += red[1][tid + r * c8n];
-      q[0] += red[2][tid + r * c8n];
-      q[1] += red[3][tid + r * c8n];
-    }
-    const float rc = 1.f / (float)((p1 - p0) * 4);
-    float* o = part + (((long)n * gridDim.x + blockIdx.x) * (C / 4) + tid * 2) * 2;  // {mean, M2} per half-octet
-    o[0] = k[0] + s[0] * rc;
-    o[1] = fmaxf(q[0] - s[0] * s[0] * rc, 0.f);
-    o[2] = k[1] + s[1] * rc;
-    o[3] = fmaxf(q[1] - s[1] * s[1] * rc, 0.f);
+    gn_slot(o, k, ss, qq, rc);
   }
 }
 
@@ -504,19 +333,13 @@ __global__ void gn_coef_kernel(const float* __restrict__ part, int slabs, int ro
     for (int b = 0; b < slabs; ++b) {
       const float* p = part + ((long)n * slabs + b) * Q * 2;
       const float cb = (float)(4 * min(ppb, HW - b * ppb));
-      for (int h = h0; h < h1; ++h) {
-        const float d = p[2 * h] - K;
-        sum += cb * d;
-        sq += p[2 * h + 1] + cb * d * d;
-      }
+      for (int h = h0; h < h1; ++h) gn_merge(sum, sq, p + 2 * h, cb, K);
     }
   } else {
     K = part[((long)n * slabs * G + g) * 2];
     for (int b = 0; b < slabs; ++b) {
       const float* p = part + (((long)n * slabs + b) * G + g) * 2;
-      const float cb = (float)(cpg * min(ppb, HW - b * ppb)), d = p[0] - K;
-      sum += cb * d;
-      sq += p[1] + cb * d * d;
+      gn_merge(sum, sq, p, (float)(cpg * min(ppb, HW - b * ppb)), K);
     }
   }
   const float cnt = (float)HW * (float)cpg, dl = sum / cnt, mean = K + dl;
@@ -1004,13 +827,12 @@ __global__ __launch_bounds__(256) void attention_unet_mfma_kernel(const half_t* 
 template <int CH, int T>
 static int launch_attention_unet_mfma(const half_t* qkv, half_t* out, int N, int heads, hipStream_t st) {
   constexpr int LDS = T * (CH * 2 + 16) + CH * (T * 2 + 16);
-  static unsigned long long attr_set = 0;
-  int devid = 0;
-  (void)hipGetDevice(&devid);
-  if (!((attr_set >> (devid & 63)) & 1)) {
+  static lfm_device_mask attr_set{0};
+  const unsigned long long dbit = lfm_device_bit();
+  if (lfm_device_todo(attr_set, dbit)) {
     if (hipFuncSetAttribute((const void*)attention_unet_mfma_kernel<CH, T>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS) != hipSuccess)
       return LFM_ERR_LAUNCH;
-    attr_set |= 1ull << (devid & 63);
+    lfm_device_done(attr_set, dbit);
   }
   hipLaunchKernelGGL((attention_unet_mfma_kernel<CH, T>), dim3(heads, N, T / 64), dim3(256), LDS, st, qkv, out, heads, 1.0f / sqrtf((float)CH));
   LFM_CHECK_LAUNCH();

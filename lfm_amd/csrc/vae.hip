@@ -5,196 +5,9 @@
 // k = tap*Cin + ci; the A-tile gather (shifted pixel rows, zero padding, optional nearest-2x upsample) is done
 // by the per-lane LDS-DMA source address.  GroupNorm statistics / apply+SiLU are bandwidth-bound side kernels.
 #include "../../include/lfm_hip.h"
-#include "gemm_dispatch.h"
-#include "conv_halo_kernel.h"
+#include "nhwc_common.h"  // ASrcConv<MODE>, EpiResidF16, EpiConvStatsF16, EpiNCHWF32, gn_stats_rows_kernel, conv_halo_allowed
 
-// ------------------------------------------------------------------ implicit-GEMM A source: 3x3 conv, pad 1, NHWC
-// UPS=1: the convolution runs on the nearest-2x upsampled image (diffusers Upsample2D) without materialising it.
-template <int UPS>
-struct ASrcConv3x3 {
-  const half_t* in;    // [N, Hs, Ws, Cin] with Hs = H >> UPS
-  const half_t* zeros; // >= 64 halves of zeros (padding rows)
-  int H, W, Cin, M;    // output (= conv input after upsample) spatial size; M = N*H*W
-  int tap, ci0;        // k-tile state: k0 = tap*Cin + ci0 (a 64-wide k tile never straddles a tap: Cin % 64 == 0)
-  __device__ __forceinline__ void init(int, long) {}
-  struct Row {
-    int n, y, x;
-  };
-  __device__ __forceinline__ Row row(int m) const {
-    if (m >= M) m = M - 1;
-    Row r;
-    r.x = m % W;
-    const int t = m / W;
-    r.y = t % H;
-    r.n = t / H;
-    return r;
-  }
-  __device__ __forceinline__ void begin_tile(int kt, int bk) {  // called with kt = 0, 1, 2, ... in order
-    if (kt == 0) {
-      tap = 0;
-      ci0 = 0;
-    } else {
-      ci0 += bk;
-      if (ci0 >= Cin) {
-        ci0 = 0;
-        ++tap;
-      }
-    }
-  }
-  __device__ __forceinline__ const half_t* ptr(const Row& r, int koff) const {
-    const int iy = r.y + tap / 3 - 1, ix = r.x + tap % 3 - 1;
-    if ((unsigned)iy >= (unsigned)H || (unsigned)ix >= (unsigned)W) return zeros + koff;
-    const int Hs = H >> UPS, Ws = W >> UPS;
-    return in + (((long)r.n * Hs + (iy >> UPS)) * Ws + (ix >> UPS)) * Cin + ci0 + koff;
-  }
-};
-
-// Encoder downsampling (diffusers Downsample2D with padding=0: F.pad(x, (0,1,0,1)) then conv3x3, stride 2): output (oy, ox) reads
-// input (2*oy + ky, 2*ox + kx), zero beyond the bottom / right edge.  H, W are the OUTPUT size; the input is [N, 2H, 2W, Cin].
-struct ASrcConvDown {
-  const half_t* in;
-  const half_t* zeros;
-  int H, W, Cin, M;
-  int tap, ci0;
-  __device__ __forceinline__ void init(int, long) {}
-  struct Row {
-    int n, y, x;
-  };
-  __device__ __forceinline__ Row row(int m) const {
-    if (m >= M) m = M - 1;
-    Row r;
-    r.x = m % W;
-    const int t = m / W;
-    r.y = t % H;
-    r.n = t / H;
-    return r;
-  }
-  __device__ __forceinline__ void begin_tile(int kt, int bk) {
-    if (kt == 0) {
-      tap = 0;
-      ci0 = 0;
-    } else {
-      ci0 += bk;
-      if (ci0 >= Cin) {
-        ci0 = 0;
-        ++tap;
-      }
-    }
-  }
-  __device__ __forceinline__ const half_t* ptr(const Row& r, int koff) const {
-    const int iy = 2 * r.y + tap / 3, ix = 2 * r.x + tap % 3;
-    if (iy >= 2 * H || ix >= 2 * W) return zeros + koff;
-    return in + (((long)r.n * (2 * H) + iy) * (2 * W) + ix) * Cin + ci0 + koff;
-  }
-};
-
-// ------------------------------------------------------------------ epilogues
-struct EpiConvF16 {  // out = acc + bias (+ residual)  -> fp16 NHWC
-  half_t* C;
-  long ldc;
-  const float* bias;
-  const half_t* resid;  // may be null; same layout as C
-  struct Aux {
-    f32x4 b;
-    half4_t r;
-  };
-  __device__ __forceinline__ Aux load(int m, int n) const {
-    Aux a;
-    a.b = *(const f32x4*)(bias + n);
-    if (resid) a.r = *(const half4_t*)(resid + (long)m * ldc + n);
-    else a.r = (half4_t){0, 0, 0, 0};
-    return a;
-  }
-  __device__ __forceinline__ void store(int m, int n, f32x4 v, const Aux& a) const {
-    v += a.b;
-    half4_t h = {(half_t)(v.x + (float)a.r.x), (half_t)(v.y + (float)a.r.y), (half_t)(v.z + (float)a.r.z), (half_t)(v.w + (float)a.r.w)};
-    *(half4_t*)(C + (long)m * ldc + n) = h;
-  }
-  __device__ __forceinline__ bool wide_ok() const { return (ldc & 7) == 0 && ((uintptr_t)C & 15) == 0 && (!resid || ((uintptr_t)resid & 15) == 0); }
-  __device__ __forceinline__ void store8(int m, int n, f32x4 lo, f32x4 hi, const Aux& al, const Aux& ah) const {
-    lo += al.b;
-    hi += ah.b;
-    half8_t h = {(half_t)(lo.x + (float)al.r.x), (half_t)(lo.y + (float)al.r.y), (half_t)(lo.z + (float)al.r.z), (half_t)(lo.w + (float)al.r.w),
-                 (half_t)(hi.x + (float)ah.r.x), (half_t)(hi.y + (float)ah.r.y), (half_t)(hi.z + (float)ah.r.z), (half_t)(hi.w + (float)ah.r.w)};
-    *(half8_t*)(C + (long)m * ldc + n) = h;
-  }
-};
-
-// EpiConvF16 that also leaves the GroupNorm statistics of what it stores (round 3): the next layer of every resnet is a GroupNorm over exactly this
-// tensor, and its statistics pass (gn_stats_kernel) re-read it from HBM just to add it up.  In the row-major hand-over of the 256-row kernels a lane
-// owns the same eight output columns for all of its rows, so it keeps shifted sums of the ROUNDED fp16 values per half-octet (a group is >= 4
-// channels wide) in registers, folds the eight lanes that share its columns at the end of the tile, and writes one fixed slot per (image, 128-row
-// slab, half-octet): part[n][slab][C / 4] = {mean, M2} of its 512 values, the layout gn_finish_kernel merges in a fixed order -- deterministic, no
-// atomics.  Shifted: a lane's sums are of x - k with k its own first value of the half-octet, so an offset group (|mean| >> std) keeps the
-// precision of its spread instead of cancelling sum(x^2) / n - mean^2; the finish re-shifts the eight lanes to one pivot before they are added.
-// Host-side preconditions (conv3): HW % 256 == 0 (a tile lies in one image), the 256x128 or 256x256 kernel, 16-byte-store path.
-struct EpiConvStatsF16 {
-  half_t* C;
-  long ldc;
-  const float* bias;
-  const half_t* resid;
-  float* part;  // [n][slabs][ldc / 4][2]
-  int HW, slabs;
-  mutable float s0, q0, s1, q1;  // sums of (x - k0), (x - k0)^2 over half-octet 0, the same for half-octet 1 around k1
-  mutable float k0, k1, cnt;     // shifts (set by the first store8) and values per half-octet so far
-  typedef EpiConvF16::Aux Aux;
-  __device__ __forceinline__ Aux load(int m, int n) const {
-    Aux a;
-    a.b = *(const f32x4*)(bias + n);
-    if (resid) a.r = *(const half4_t*)(resid + (long)m * ldc + n);
-    else a.r = (half4_t){0, 0, 0, 0};
-    return a;
-  }
-  __device__ __forceinline__ void store(int m, int n, f32x4 v, const Aux& a) const {  // (4-column path: not used with statistics, kept for the interface)
-    v += a.b;
-    half4_t h = {(half_t)(v.x + (float)a.r.x), (half_t)(v.y + (float)a.r.y), (half_t)(v.z + (float)a.r.z), (half_t)(v.w + (float)a.r.w)};
-    *(half4_t*)(C + (long)m * ldc + n) = h;
-  }
-  __device__ __forceinline__ bool wide_ok() const { return true; }  // checked on the host
-  __device__ __forceinline__ void store8(int m, int n, f32x4 lo, f32x4 hi, const Aux& al, const Aux& ah) const {
-    lo += al.b;
-    hi += ah.b;
-    const half8_t h = {(half_t)(lo.x + (float)al.r.x), (half_t)(lo.y + (float)al.r.y), (half_t)(lo.z + (float)al.r.z), (half_t)(lo.w + (float)al.r.w),
-                       (half_t)(hi.x + (float)ah.r.x), (half_t)(hi.y + (float)ah.r.y), (half_t)(hi.z + (float)ah.r.z), (half_t)(hi.w + (float)ah.r.w)};
-    *(half8_t*)(C + (long)m * ldc + n) = h;
-    if (cnt == 0.f) {
-      k0 = (float)h[0];
-      k1 = (float)h[4];
-    }
-    cnt += 4.f;
-    const float f0 = (float)h[0] - k0, f1 = (float)h[1] - k0, f2 = (float)h[2] - k0, f3 = (float)h[3] - k0;
-    const float f4 = (float)h[4] - k1, f5 = (float)h[5] - k1, f6 = (float)h[6] - k1, f7 = (float)h[7] - k1;
-    s0 += (f0 + f1) + (f2 + f3);
-    q0 += (f0 * f0 + f1 * f1) + (f2 * f2 + f3 * f3);
-    s1 += (f4 + f5) + (f6 + f7);
-    q1 += (f4 * f4 + f5 * f5) + (f6 * f6 + f7 * f7);
-  }
-  // fold the eight lanes that own the same columns and write the wave's slot: columns ncol0 + 8 (lane & 7) .. + 7 of slab `slab` of image `img`
-  __device__ __forceinline__ void finish_slab(int img, int slab, int ncol0, int lane) const {
-    // re-shift every lane's sums to the shifts of lane (lane & 7): sum (x - p) = s + c d, sum (x - p)^2 = q + d (2 s + c d) with d = k - p
-    const float p0 = __shfl(k0, lane & 7, 64), p1 = __shfl(k1, lane & 7, 64);
-    const float d0 = k0 - p0, d1 = k1 - p1;
-    float a = s0 + cnt * d0, b = q0 + d0 * (2.f * s0 + cnt * d0), c = s1 + cnt * d1, d = q1 + d1 * (2.f * s1 + cnt * d1), t = cnt;
-#pragma unroll
-    for (int o = 8; o < 64; o <<= 1) {  // the eight lanes lane & 7, + 8, .., + 56 own the same columns
-      a += __shfl_xor(a, o, 64);
-      b += __shfl_xor(b, o, 64);
-      c += __shfl_xor(c, o, 64);
-      d += __shfl_xor(d, o, 64);
-      t += __shfl_xor(t, o, 64);
-    }
-    if (lane < 8) {  // {mean, M2} per half-octet
-      float* o = part + (((long)img * slabs + slab) * (ldc >> 2) + ((ncol0 + lane * 8) >> 2)) * 2;
-      const float r = 1.f / t;
-      *(f32x4*)o = (f32x4){p0 + a * r, fmaxf(b - a * a * r, 0.f), p1 + c * r, fmaxf(d - c * c * r, 0.f)};
-    }
-  }
-  __device__ __forceinline__ void finish_tile(int m0, int n0, int g, int wn, int lane) const {
-    const int img = m0 / HW;
-    finish_slab(img, ((m0 - img * HW) >> 8) * 2 + g, n0 + wn * 64, lane);
-  }
-};
-
+// ------------------------------------------------------------------ epilogues (EpiResidF16, EpiConvStatsF16, EpiNCHWF32: nhwc_common.h)
 struct EpiTransposeF16 {  // per image: Ct[img][n][m % T] = acc + bias[n]   (V^T for the mid attention)
   half_t* Ct;
   const float* bias;
@@ -231,23 +44,6 @@ struct EpiBatchF16 {  // batched: O[bz][m][n] = acc -> fp16
   __device__ __forceinline__ void store(int m, int n, f32x4 v, const Aux&) const {
     half4_t h = {(half_t)v.x, (half_t)v.y, (half_t)v.z, (half_t)v.w};
     *(half4_t*)(C + (long)m * ldc + n) = h;
-  }
-};
-
-struct EpiConvOutNCHW {  // final conv (Cout=3, padded to 4): fp32 NCHW image, the `.sample` tensor
-  float* out;
-  const float* bias;  // [4]
-  int HW;             // H*W
-  typedef f32x4 Aux;
-  __device__ __forceinline__ Aux load(int, int n) const { return *(const f32x4*)(bias + n); }
-  __device__ __forceinline__ void store(int m, int n, f32x4 v, const Aux& b) const {
-    if (n != 0) return;
-    v += b;
-    const int img = m / HW, pix = m - img * HW;
-    float* o = out + (long)img * 3 * HW + pix;
-    o[0] = v.x;
-    o[HW] = v.y;
-    o[2 * HW] = v.z;
   }
 };
 
@@ -311,57 +107,14 @@ __global__ __launch_bounds__(256) void vae_conv_in_kernel(const float* __restric
 }
 
 // ------------------------------------------------------------------ GroupNorm(32 groups, eps 1e-6) on NHWC fp16
-// Two-stage, deterministic statistics (the reference is deterministic; float atomics are not): every block folds its slab of pixels
-// into per-half-octet partial {mean, M2} slots part[n][slab][C/4], a small second kernel merges the slabs and the half-octets of a
-// group in a fixed order into stats[n][g] = {mean, rstd}; apply fuses SiLU.
-// Offset data: a slab's sums are of x - k, k = the slab's first value of the half-octet (every thread of the octet reads the same k), and the
-// merge is shifted the same way, so a group whose mean is hundreds of standard deviations keeps its variance (the unshifted
-// sum(x^2) / n - mean^2 loses it to fp32 cancellation).
-// Block = 256 threads over a slab of pixels; thread t owns channel-octet (t % (C/8)) and strides over pixels.
+// Two-stage, deterministic statistics: the producing convolution's epilogue (EpiConvStatsF16) or a pass of its own (gn_stats_rows_kernel) folds
+// slabs of pixels into per-half-octet partial {mean, M2} slots part[n][slab][C/4] (nhwc_common.h: both shifted, so a group whose mean is hundreds
+// of standard deviations keeps its variance); a small second kernel merges the slabs and the half-octets of a group in a fixed order into
+// stats[n][g] = {mean, rstd}; apply fuses SiLU.
 #define VGN_MAX_SLABS 64
-__global__ __launch_bounds__(256) void gn_stats_kernel(const half_t* __restrict__ x, float* __restrict__ part, int HW, int C,
-                                                       int pix_per_block) {
-  __shared__ float red[4][256];
-  const int n = blockIdx.y, c8n = C / 8, tid = threadIdx.x;
-  const int oct = tid % c8n, prow = tid / c8n, pstride = 256 / c8n;
-  const int p0 = blockIdx.x * pix_per_block;
-  const int p1 = min(p0 + pix_per_block, HW);
-  float s[2] = {0.f, 0.f}, q[2] = {0.f, 0.f};  // per half-octet (4 channels): a group is >= 4 channels wide
-  const half_t* base = x + (long)n * HW * C + oct * 8;
-  const float k[2] = {(float)base[(long)p0 * C], (float)base[(long)p0 * C + 4]};  // the shifts: pixel p0 of this slab
-  for (int p = p0 + prow; p < p1; p += pstride) {
-    const half8_t v = *(const half8_t*)(base + (long)p * C);
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const float f = (float)v[j] - k[j >> 2];
-      s[j >> 2] += f;
-      q[j >> 2] += f * f;
-    }
-  }
-  red[0][tid] = s[0];
-  red[1][tid] = s[1];
-  red[2][tid] = q[0];
-  red[3][tid] = q[1];
-  __syncthreads();
-  if (tid < c8n) {  // fold the pixel-rows of this channel octet, then one {mean, M2} slot per half-octet
-    for (int r = 1; r < pstride; ++r) {
-      s[0] += red[0][tid + r * c8n];
-      s[1] += red[1][tid + r * c8n];
-      q[0] += red[2][tid + r * c8n];
-      q[1] += red[3][tid + r * c8n];
-    }
-    const float rc = 1.f / (float)((p1 - p0) * 4);
-    float* o = part + (((long)n * gridDim.x + blockIdx.x) * (C / 4) + tid * 2) * 2;
-    o[0] = k[0] + s[0] * rc;
-    o[1] = fmaxf(q[0] - s[0] * s[0] * rc, 0.f);
-    o[2] = k[1] + s[1] * rc;
-    o[3] = fmaxf(q[1] - s[1] * s[1] * rc, 0.f);
-  }
-}
 // one WAVE per (image, group): lane l folds slabs l, l + 64, ... in order, then a fixed-tree wave sum (deterministic).  (One thread per
 // (image, group) walking all slabs serially took 75 us once the convolution epilogues started to deliver 512 slabs per image.)
-// Slot {mean m, M2} of slab b holds c = 4 min(ppb, HW - b ppb) values; the merge is shifted by the group's first slot mean K:
-// sum (x - K) = sum c (m - K),  sum (x - K)^2 = sum M2 + c (m - K)^2 -- linear, so the lanes and the wave tree add as before.
+// Slot {mean m, M2} of slab b holds c = 4 min(ppb, HW - b ppb) values; the merge is shifted by the group's first slot mean K (gn_merge).
 __global__ __launch_bounds__(256) void gn_finish_kernel(const float* __restrict__ part, float* __restrict__ stats, int slabs, int ppb, int HW, int C,
                                                         int total) {
   const int i = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;  // (n, g)
@@ -372,11 +125,7 @@ __global__ __launch_bounds__(256) void gn_finish_kernel(const float* __restrict_
   for (int b = lane; b < slabs; b += 64) {
     const float* p = part + (((long)n * slabs + b) * (C / 4) + g * hpg) * 2;
     const float c = (float)(4 * min(ppb, HW - b * ppb));
-    for (int h = 0; h < hpg; ++h) {
-      const float d = p[2 * h] - K;
-      sum += c * d;
-      sq += p[2 * h + 1] + c * d * d;
-    }
+    for (int h = 0; h < hpg; ++h) gn_merge(sum, sq, p + 2 * h, c, K);
   }
   sum = wave_sum(sum);
   sq = wave_sum(sq);
@@ -499,18 +248,47 @@ extern "C" size_t lfm_vae_workspace_bytes(int R, int chunk) {
     if (_rc) return _rc; \
   } while (0)
 
-// ready_slabs > 0: the convolution that produced x already left its partial sums in `part` (EpiConvStatsF16), in that many slabs per image
-static int gn(const half_t* x, half_t* y, float* stats, float* part, const float* g, const float* b, int n, int HW, int C, bool silu,
-              hipStream_t st, int ready_slabs = 0, size_t part_pairs = 0) {
+struct VaeConv {  // a 3x3 convolution layer: w fp16 [Cout][9][Cin], b fp32 [Cout]; ups: on the nearest-2x upsampled input
+  const void* w;
+  const float* b;
+  int Cin, Cout;
+  bool ups;
+};
+
+// The host driver's state for n images: the carve, the stream, the four rotating activation buffers (x holds the current tensor) and what is known
+// about x.  The test entry points fill only ws.zeros / stats / part / part_pairs and call gn and conv3 with their own buffers.
+struct VaeCtx {
+  VaeWs ws;
+  int n;
+  hipStream_t st;
+  half_t *x, *t1, *t2, *t3;
+  int x_slabs;       // partial-sum slabs per image that the producer of x left in ws.part (0 = none: the GroupNorm runs its own statistics pass)
+  bool chain_stats;  // decoder: the last convolution of a resnet leaves the statistics of its output for the GroupNorm that follows
+  void rotate(half_t*& t) {  // the result was written to t: it becomes x, the old x becomes scratch
+    half_t* o = t;
+    t = x;
+    x = o;
+  }
+  int gn(const half_t* in, half_t* y, const float* g, const float* b, int HW, int C, bool silu, int ready_slabs) const;
+  int conv3(const half_t* in, half_t* out, const half_t* resid, int H, int W, const VaeConv& c, int* stat_slabs, int* stat_kernel = nullptr) const;
+  int conv_down(const void* w, const float* b, int Ho, int Wo, int C);
+  int resnet(const lfm_vae_resnet* r, int H, int W);
+  template <class W>
+  int mid_attention(const W* w, int T);
+};
+
+// y = silu?(GroupNorm(in) g + b).  ready_slabs > 0: the convolution that produced `in` already left its partial sums in ws.part (EpiConvStatsF16), in
+// that many slabs per image
+int VaeCtx::gn(const half_t* in, half_t* y, const float* g, const float* b, int HW, int C, bool silu, int ready_slabs) const {
   if (C % 128 || 256 % (C / 8) || C > 512) return LFM_ERR_SHAPE;  // groups of >= 4 channels, octet-per-thread mapping
   int slabs = ready_slabs, ppb = ready_slabs ? HW / ready_slabs : 0;  // pixels per slab (the convolution epilogues: 128)
   if (!ready_slabs) {
     // slabs per image: VGN_MAX_SLABS when the images fill the chip; a FEW images (--measure_time decodes ONE) get up to 512 -- 64 blocks walked a 256x256x128 map in
-    // 64 dependent 16-byte loads per thread, 68 us per GroupNorm and 38 % of the batch-1 decode (profiles/r06_latency_mode.txt) -- as far as `part` has room
-    // (part_pairs = its capacity in pairs, 0 = unknown: the old cap)
+    // 64 dependent 16-byte loads per thread, 68 us per GroupNorm and 38 % of the batch-1 decode (profiles/r06_latency_mode.txt) -- as far as ws.part has room
+    // (ws.part_pairs = its capacity in pairs, 0 = unknown: the old cap)
     int cap = VGN_MAX_SLABS;
-    if (part_pairs && n * VGN_MAX_SLABS < 1024) {
-      const long room = (long)(part_pairs / ((size_t)n * (C / 4)));
+    if (ws.part_pairs && n * VGN_MAX_SLABS < 1024) {
+      const long room = (long)(ws.part_pairs / ((size_t)n * (C / 4)));
       const long want = 1024 / n;
       cap = (int)(want < room ? want : room);
       if (cap > 512) cap = 512;
@@ -520,72 +298,75 @@ static int gn(const half_t* x, half_t* y, float* stats, float* part, const float
     if (cap > VGN_MAX_SLABS) ppb = cdiv(HW, cap) > 64 ? cdiv(HW, cap) : 64;  // >= 64 pixels per block: at least a few loads per thread
     if (cdiv(HW, ppb) > cap) ppb = cdiv(HW, cap);
     slabs = cdiv(HW, ppb);
-    hipLaunchKernelGGL(gn_stats_kernel, dim3(slabs, n), dim3(256), 0, st, x, part, HW, C, ppb);
+    hipLaunchKernelGGL(gn_stats_rows_kernel, dim3(slabs, n), dim3(256), 0, st, GnIn{in, nullptr, C, 0}, ws.part, HW, C, ppb);
     LFM_CHECK_LAUNCH();
   }
-  hipLaunchKernelGGL(gn_finish_kernel, dim3(cdiv(n * 32, 4)), dim3(256), 0, st, part, stats, slabs, ppb, HW, C, n * 32);
+  hipLaunchKernelGGL(gn_finish_kernel, dim3(cdiv(n * 32, 4)), dim3(256), 0, st, ws.part, ws.stats, slabs, ppb, HW, C, n * 32);
   LFM_CHECK_LAUNCH();
   const int app = HW >= 4096 ? 256 : (HW >= 256 ? 64 : HW);  // pixels per block: 16 .. 4 chunks per thread at 128 .. 512 channels
-  if (silu) hipLaunchKernelGGL(gn_apply_kernel<true>, dim3(cdiv(HW, app), n), dim3(256), 0, st, x, y, stats, g, b, HW, C, app);
-  else hipLaunchKernelGGL(gn_apply_kernel<false>, dim3(cdiv(HW, app), n), dim3(256), 0, st, x, y, stats, g, b, HW, C, app);
+  if (silu) hipLaunchKernelGGL(gn_apply_kernel<true>, dim3(cdiv(HW, app), n), dim3(256), 0, st, in, y, ws.stats, g, b, HW, C, app);
+  else hipLaunchKernelGGL(gn_apply_kernel<false>, dim3(cdiv(HW, app), n), dim3(256), 0, st, in, y, ws.stats, g, b, HW, C, app);
   LFM_CHECK_LAUNCH();
   return LFM_OK;
 }
 
 // out[n,H,W,Cout] = conv3x3(in (optionally nearest-2x upsampled)) + bias (+ resid)
-// *stat_slabs (optional): set to the number of partial-sum slabs per image this convolution left in `part` for the GroupNorm that follows, or 0;
-// *stat_kernel (optional): which kernel left them -- 1 the halo-tiled convolution, 2 a 256-row implicit GEMM, 0 none
-static int conv3(const half_t* in, const half_t* w, const float* b, const half_t* resid, half_t* out, const half_t* zeros, int n, int H, int W,
-                 int Cin, int Cout, bool ups, hipStream_t st, float* part = nullptr, int* stat_slabs = nullptr, int* stat_kernel = nullptr) {
+// stat_slabs (null: no statistics wanted): set to the number of partial-sum slabs per image this convolution left in ws.part for the GroupNorm that
+// follows, or 0; *stat_kernel (optional): which kernel left them -- 1 the halo-tiled convolution, 2 a 256-row implicit GEMM, 0 none
+int VaeCtx::conv3(const half_t* in, half_t* out, const half_t* resid, int H, int W, const VaeConv& c, int* stat_slabs, int* stat_kernel) const {
+  const int Cin = c.Cin, Cout = c.Cout, HW = H * W, M = n * HW;
+  const half_t* w = (const half_t*)c.w;
   if (Cin % 64 || Cout % 4) return LFM_ERR_SHAPE;
-  const int M = n * H * W;
   if (stat_slabs) *stat_slabs = 0;
   if (stat_kernel) *stat_kernel = 0;
-  const int HW = H * W;
+  // the statistics epilogue, as far as it does not depend on the kernel: a tile lies in one image, 16-byte stores, VAE_SEPARATE_STATS (A/B) not set
+  const bool stats_ok = ws.part && stat_slabs && (HW % 256) == 0 && !(((uintptr_t)out | (uintptr_t)resid) & 15) &&
+                        !(lfm_gemm_debug_flags() & LFM_DBG_VAE_SEPARATE_STATS);
+  const EpiResidF16 ep{out, Cout, c.b, resid};
+  const EpiConvStatsF16 es{ep, ws.part, HW, 2 * (HW / 256)};
+  auto left = [&](int kernel) {
+    *stat_slabs = es.slabs;
+    if (stat_kernel) *stat_kernel = kernel;
+  };
   // every 3x3 convolution on a 16-aligned map: the halo-tiled direct kernel (conv_halo_kernel.h; 1.1-1.2 PFLOP/s where the implicit GEMM reaches
-  // 0.65-1.05, profiles/r03_halo_conv_probe.txt); CONV_IMPLICIT_GEMM: the implicit GEMM instead (A/B)
-  if (lfm_gemm_selected() == 0 && !(((uintptr_t)out | (uintptr_t)resid) & 15) && !(lfm_gemm_debug_flags() & LFM_DBG_CONV_IMPLICIT_GEMM)) {
-    int rc;
-    if (part && stat_slabs && (HW % 256) == 0 && !(lfm_gemm_debug_flags() & LFM_DBG_VAE_SEPARATE_STATS)) {
-      EpiConvStatsF16 es{out, Cout, b, resid, part, HW, 2 * (HW / 256), 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-      rc = ups ? launch_conv3x3_halo<1>(in, zeros, w, n, H, W, Cin, Cout, es, st) : launch_conv3x3_halo<0>(in, zeros, w, n, H, W, Cin, Cout, es, st);
-      if (rc == 0) {
-        *stat_slabs = es.slabs;
-        if (stat_kernel) *stat_kernel = 1;
-      }
-    } else {
-      EpiConvF16 ep{out, Cout, b, resid};
-      rc = ups ? launch_conv3x3_halo<1>(in, zeros, w, n, H, W, Cin, Cout, ep, st) : launch_conv3x3_halo<0>(in, zeros, w, n, H, W, Cin, Cout, ep, st);
-    }
+  // 0.65-1.05, profiles/r03_halo_conv_probe.txt)
+  if (conv_halo_allowed(out, resid)) {
+    auto halo = [&](const auto& e) {
+      return c.ups ? launch_conv3x3_halo<1>(in, ws.zeros, w, n, H, W, Cin, Cout, e, st) : launch_conv3x3_halo<0>(in, ws.zeros, w, n, H, W, Cin, Cout, e, st);
+    };
+    const int rc = stats_ok ? halo(es) : halo(ep);
+    if (rc == 0 && stats_ok) left(1);
     if (rc != 1) return rc;
   }
   // the implicit GEMM.  The statistics epilogue leaves its partials in the slot layout of the 256-row kernels' tiles: ask which kernel runs for the types
   // about to be launched, take the epilogue only if that is one of them, and launch THAT kernel (one decision for the layout and the launch).
   auto gemm = [&](const auto& a) {
     const int kern = gemm_choose(M, Cout, 9 * Cin, 1, gemm_caps<std::decay_t<decltype(a)>, EpiConvStatsF16>(a, Cout, 9L * Cin));
-    if (part && stat_slabs && (HW % 256) == 0 && (kern == 4 || kern == 5) && (Cout % (kern == 4 ? 128 : 256)) == 0 && (Cout % 128) == 0 &&
-        !(((uintptr_t)out | (uintptr_t)resid) & 15) && !(lfm_gemm_debug_flags() & (LFM_DBG_GEMM_STORE8 | LFM_DBG_VAE_SEPARATE_STATS))) {
-      *stat_slabs = 2 * (HW / 256);
-      if (stat_kernel) *stat_kernel = 2;
-      return launch_gemm_kernel(kern, a, w, 9L * Cin, M, Cout, 9 * Cin, EpiConvStatsF16{out, Cout, b, resid, part, HW, *stat_slabs, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, st);
+    if (stats_ok && (kern == 4 || kern == 5) && (Cout % (kern == 4 ? 128 : 256)) == 0 && (Cout % 128) == 0 &&
+        !(lfm_gemm_debug_flags() & LFM_DBG_GEMM_STORE8)) {
+      left(2);
+      return launch_gemm_kernel(kern, a, w, 9L * Cin, M, Cout, 9 * Cin, es, st);
     }
-    return launch_gemm_auto(a, w, 9L * Cin, M, Cout, 9 * Cin, EpiConvF16{out, Cout, b, resid}, st);
+    return launch_gemm_auto(a, w, 9L * Cin, M, Cout, 9 * Cin, ep, st);
   };
-  if (ups) return gemm(ASrcConv3x3<1>{in, zeros, H, W, Cin, M, 0, 0});
-  return gemm(ASrcConv3x3<0>{in, zeros, H, W, Cin, M, 0, 0});
+  if (c.ups) return gemm(ASrcConv<1>{in, ws.zeros, H, W, Cin, M});
+  return gemm(ASrcConv<0>{in, ws.zeros, H, W, Cin, M});
 }
 
 // ---- test entry points: the decoder's GroupNorm (gn, its own statistics pass) and the conv3 -> gn hand-over, on the decoder's host code.
 // Workspace: [zeros 256 B][stats n x 32 x {mean, rstd}][part: the rest, in {mean, M2} pairs] (the decoder sizes part by lfm_vae_workspace_bytes;
 // gn takes as many statistics slabs as part has room for, as in the decoder).
-static int vae_test_carve(void* workspace, size_t bytes, int n, half_t*& zeros, float*& stats, float*& part, size_t& part_pairs) {
+static int vae_test_ctx(void* workspace, size_t bytes, int n, lfm_stream_t stream, VaeCtx& c) {
   if ((uintptr_t)workspace & 255) return LFM_ERR_ALIGN;
   const size_t head = 256 + a256((size_t)n * 64 * 4);
   if (bytes < head) return LFM_ERR_WORKSPACE;
-  zeros = (half_t*)workspace;
-  stats = (float*)((char*)workspace + 256);
-  part = (float*)((char*)workspace + head);
-  part_pairs = (bytes - head) / 8;
+  c = VaeCtx{};
+  c.ws.zeros = (half_t*)workspace;
+  c.ws.stats = (float*)((char*)workspace + 256);
+  c.ws.part = (float*)((char*)workspace + head);
+  c.ws.part_pairs = (bytes - head) / 8;
+  c.n = n;
+  c.st = (hipStream_t)stream;
   return LFM_OK;
 }
 
@@ -594,12 +375,10 @@ extern "C" int lfm_vae_groupnorm_f16(const void* x, void* y, const float* gamma,
   if (!x || !y || !gamma || !beta || !workspace) return LFM_ERR_ARG;
   if (n <= 0 || HW <= 0 || C <= 0) return LFM_ERR_SHAPE;
   if (((uintptr_t)x | (uintptr_t)y) & 15) return LFM_ERR_ALIGN;
-  half_t* zeros;
-  float *stats, *part;
-  size_t pairs;
-  RC(vae_test_carve(workspace, workspace_bytes, n, zeros, stats, part, pairs));
-  if (pairs < (size_t)n * VGN_MAX_SLABS * (C / 4)) return LFM_ERR_WORKSPACE;
-  return gn((const half_t*)x, (half_t*)y, stats, part, gamma, beta, n, HW, C, silu != 0, (hipStream_t)stream, 0, pairs);
+  VaeCtx c;
+  RC(vae_test_ctx(workspace, workspace_bytes, n, stream, c));
+  if (c.ws.part_pairs < (size_t)n * VGN_MAX_SLABS * (C / 4)) return LFM_ERR_WORKSPACE;
+  return c.gn((const half_t*)x, (half_t*)y, gamma, beta, HW, C, silu != 0, 0);
 }
 
 extern "C" int lfm_vae_conv3x3_gn_f16(const void* in, const void* w, const float* bias, const void* resid, void* conv_out, void* y, const float* gamma,
@@ -608,69 +387,102 @@ extern "C" int lfm_vae_conv3x3_gn_f16(const void* in, const void* w, const float
   if (!in || !w || !bias || !conv_out || !y || !gamma || !beta || !workspace) return LFM_ERR_ARG;
   if (n <= 0 || H <= 0 || W <= 0 || (ups && ((H | W) & 1))) return LFM_ERR_SHAPE;
   if (((uintptr_t)in | (uintptr_t)w | (uintptr_t)resid | (uintptr_t)conv_out | (uintptr_t)y) & 15) return LFM_ERR_ALIGN;
-  half_t* zeros;
-  float *stats, *part;
-  size_t pairs;
-  RC(vae_test_carve(workspace, workspace_bytes, n, zeros, stats, part, pairs));
+  VaeCtx c;
+  RC(vae_test_ctx(workspace, workspace_bytes, n, stream, c));
   const size_t conv_pairs = (size_t)n * 2 * (H * W / 256) * (Cout / 4), stat_pairs = (size_t)n * VGN_MAX_SLABS * (Cout / 4);
-  if (pairs < (conv_pairs > stat_pairs ? conv_pairs : stat_pairs)) return LFM_ERR_WORKSPACE;
-  hipStream_t st = (hipStream_t)stream;
-  if (lfm_zero_async(zeros, 256, st)) return LFM_ERR_LAUNCH;
+  if (c.ws.part_pairs < (conv_pairs > stat_pairs ? conv_pairs : stat_pairs)) return LFM_ERR_WORKSPACE;
+  if (lfm_zero_async(c.ws.zeros, 256, c.st)) return LFM_ERR_LAUNCH;
   int slabs = 0, kern = 0;
-  RC(conv3((const half_t*)in, (const half_t*)w, bias, (const half_t*)resid, (half_t*)conv_out, zeros, n, H, W, Cin, Cout, ups != 0, st, part, &slabs,
-           &kern));
-  RC(gn((const half_t*)conv_out, (half_t*)y, stats, part, gamma, beta, n, H * W, Cout, silu != 0, st, slabs, pairs));
+  RC(c.conv3((const half_t*)in, (half_t*)conv_out, (const half_t*)resid, H, W, VaeConv{w, bias, Cin, Cout, ups != 0}, &slabs, &kern));
+  RC(c.gn((const half_t*)conv_out, (half_t*)y, gamma, beta, H * W, Cout, silu != 0, slabs));
   if (stat_slabs) *stat_slabs = slabs;
   if (stat_kernel) *stat_kernel = kern;
   return LFM_OK;
 }
 
-// x_slabs: in = partial-sum slabs per image already in ws.part for x (0 = none), out = the same for the result
-static int resnet(const lfm_vae_resnet* r, half_t*& x, half_t*& t1, half_t*& t2, half_t*& t3, const VaeWs& ws, int n, int H, int W, hipStream_t st,
-                  int* x_slabs = nullptr) {
+// diffusers ResnetBlock2D: GroupNorm+SiLU -> conv -> GroupNorm+SiLU -> conv + (1x1 shortcut of) x.  x is replaced by the result (buffers rotate).
+int VaeCtx::resnet(const lfm_vae_resnet* r, int H, int W) {
   const int HW = H * W, M = n * HW;
-  int mid_slabs = 0, out_slabs = 0;
-  RC(gn(x, t1, ws.stats, ws.part, r->n1_g, r->n1_b, n, HW, r->cin, true, st, x_slabs ? *x_slabs : 0, ws.part_pairs));
-  RC(conv3(t1, (const half_t*)r->c1_w, r->c1_b, nullptr, t2, ws.zeros, n, H, W, r->cin, r->cout, false, st, ws.part, &mid_slabs));
-  RC(gn(t2, t1, ws.stats, ws.part, r->n2_g, r->n2_b, n, HW, r->cout, true, st, mid_slabs, ws.part_pairs));
+  int mid_slabs = 0;
+  RC(gn(x, t1, r->n1_g, r->n1_b, HW, r->cin, true, x_slabs));
+  RC(conv3(t1, t2, nullptr, H, W, VaeConv{r->c1_w, r->c1_b, r->cin, r->cout, false}, &mid_slabs));
+  RC(gn(t2, t1, r->n2_g, r->n2_b, HW, r->cout, true, mid_slabs));
   const half_t* skip = x;
   if (r->sc_w) {  // 1x1 conv shortcut
-    RC(launch_gemm_auto(ASrcRowMajor{x, r->cin, M, 0}, (const half_t*)r->sc_w, r->cin, M, r->cout, r->cin, EpiConvF16{t3, r->cout, r->sc_b, nullptr}, st));
+    RC(launch_gemm_auto(ASrcRowMajor{x, r->cin, M, 0}, (const half_t*)r->sc_w, r->cin, M, r->cout, r->cin, EpiResidF16{t3, r->cout, r->sc_b, nullptr}, st));
     skip = t3;
   }
-  RC(conv3(t1, (const half_t*)r->c2_w, r->c2_b, skip, t2, ws.zeros, n, H, W, r->cout, r->cout, false, st, x_slabs ? ws.part : nullptr,
-           x_slabs ? &out_slabs : nullptr));
-  if (x_slabs) *x_slabs = out_slabs;
-  half_t* o = t2;  // result in t2; rotate buffers so x is the result
-  t2 = x;
-  x = o;
+  x_slabs = 0;
+  RC(conv3(t1, t2, skip, H, W, VaeConv{r->c2_w, r->c2_b, r->cout, r->cout, false}, chain_stats ? &x_slabs : nullptr));
+  rotate(t2);
   return LFM_OK;
 }
 
 // mid-block attention (diffusers Attention, 1 head of 512 channels over T tokens, residual): GroupNorm -> q, k, v -> softmax(q k^T / sqrt(C)) v
-// -> to_out + x, all on the GEMM kernel.  x is replaced by the result (buffers rotate).
-static int mid_attention(const float* at_g, const float* at_b, const void* q_w, const float* q_b, const void* k_w, const float* k_b, const void* v_w,
-                         const float* v_b, const void* o_w, const float* o_b, half_t*& x, half_t*& t1, half_t*& t2, half_t*& t3, const VaeWs& ws,
-                         int n, int T, hipStream_t st, int x_slabs = 0) {
+// -> to_out + x, all on the GEMM kernel.  x is replaced by the result (buffers rotate).  W: lfm_vae_weights / lfm_vae_enc_weights name the fields alike.
+template <class W>
+int VaeCtx::mid_attention(const W* w, int T) {
   const int M = n * T, C = 512;
-  RC(gn(x, t1, ws.stats, ws.part, at_g, at_b, n, T, C, false, st, x_slabs, ws.part_pairs));
-  half_t* Qb = t2;                 // [M, C]
+  RC(gn(x, t1, w->at_g, w->at_b, T, C, false, x_slabs));
+  half_t* Qb = t2;                  // [M, C]
   half_t* Kb = t2 + (size_t)M * C;  // [M, C]
-  half_t* Vt = t3;                 // [n, C, T]
+  half_t* Vt = t3;                  // [n, C, T]
   half_t* Pb = t3 + (size_t)M * C;  // [n, T, T]
-  RC(launch_gemm_tn(ASrcRowMajor{t1, C, M, 0}, (const half_t*)q_w, C, M, C, C, EpiConvF16{Qb, C, q_b, nullptr}, st));
-  RC(launch_gemm_tn(ASrcRowMajor{t1, C, M, 0}, (const half_t*)k_w, C, M, C, C, EpiConvF16{Kb, C, k_b, nullptr}, st));
-  RC(launch_gemm_tn(ASrcRowMajor{t1, C, M, 0}, (const half_t*)v_w, C, M, C, C, EpiTransposeF16{Vt, v_b, T, C}, st));
+  const ASrcRowMajor a{t1, C, M, 0};
+  RC(launch_gemm_tn(a, (const half_t*)w->q_w, C, M, C, C, EpiResidF16{Qb, C, w->q_b, nullptr}, st));
+  RC(launch_gemm_tn(a, (const half_t*)w->k_w, C, M, C, C, EpiResidF16{Kb, C, w->k_b, nullptr}, st));
+  RC(launch_gemm_tn(a, (const half_t*)w->v_w, C, M, C, C, EpiTransposeF16{Vt, w->v_b, T, C}, st));
   RC(launch_gemm_tn(ASrcRowMajor{Qb, C, T, 0}, Kb, C, T, T, C, EpiBatchF32{ws.S, T}, st, n, (long)T * C, (long)T * C, (long)T * T));
   hipLaunchKernelGGL(softmax_rows_kernel, dim3(cdiv((long)n * T, 4)), dim3(256), 0, st, ws.S, Pb, (long)n * T, T, 1.4426950408889634f / sqrtf((float)C));
   LFM_CHECK_LAUNCH();
   half_t* Ob = t1;  // GN output is dead now
   RC(launch_gemm_tn(ASrcRowMajor{Pb, T, T, 0}, Vt, T, T, C, T, EpiBatchF16{Ob, C}, st, n, (long)T * T, (long)C * T, (long)T * C));
-  RC(launch_gemm_tn(ASrcRowMajor{Ob, C, M, 0}, (const half_t*)o_w, C, M, C, C, EpiConvF16{t2, C, o_b, x}, st));
-  half_t* o = t2;
-  t2 = x;
-  x = o;
+  RC(launch_gemm_tn(ASrcRowMajor{Ob, C, M, 0}, (const half_t*)w->o_w, C, M, C, C, EpiResidF16{t2, C, w->o_b, x}, st));
+  x_slabs = 0;
+  rotate(t2);
   return LFM_OK;
+}
+
+// post_quant_conv + conv_in: z [n,4,R,R] fp32 NCHW -> out fp16 NHWC [n,R,R,512]
+static int vae_conv_in(const lfm_vae_weights* w, const float* z, half_t* out, int n, int R, hipStream_t st) {
+  static lfm_device_mask set{0};
+  const unsigned long long dbit = lfm_device_bit();
+  if (lfm_device_todo(set, dbit)) {
+    if (hipFuncSetAttribute((const void*)vae_conv_in_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 36 * 512 * 4) != hipSuccess) return LFM_ERR_LAUNCH;
+    lfm_device_done(set, dbit);
+  }
+  // batch 1 (--measure_time: run_sampling(1, ..), reference test_flow_latent.py:223-246): 1024 pixels are FOUR blocks of 256 pixels -- 183 us for 38 MFLOP
+  // (profiles/r06_latency_mode.txt); 16 pixels per block put them on 64 CUs
+  const long pixels = (long)n * R * R;
+  const int ppb = pixels >= 256L * VCI_PIX ? VCI_PIX : (pixels >= 64L * VCI_PIX ? 64 : 16);
+  hipLaunchKernelGGL(vae_conv_in_kernel, dim3(cdiv(pixels, ppb)), dim3(256), 36 * 512 * 4, st, z, w->pq_w, w->pq_b, w->cin_w, w->cin_b, out, n, R, 512, ppb);
+  LFM_CHECK_LAUNCH();
+  return LFM_OK;
+}
+
+// one chunk of images: z [n,4,R,R] -> out [n,3,8R,8R]
+static int vae_decode_chunk(VaeCtx& c, const lfm_vae_weights* w, const float* z, float* out, int R) {
+  RC(vae_conv_in(w, z, c.x, c.n, R, c.st));
+  int H = R;
+  RC(c.resnet(&w->mid[0], H, H));
+  RC(c.mid_attention(w, R * R));
+  RC(c.resnet(&w->mid[1], H, H));
+  for (int i = 0; i < 4; ++i) {
+    for (int j = 0; j < 3; ++j) RC(c.resnet(&w->up[i][j], H, H));
+    if (i < 3) {
+      const int C = w->up[i][2].cout;
+      H *= 2;
+      RC(c.conv3(c.x, c.t1, nullptr, H, H, VaeConv{w->ups_w[i], w->ups_b[i], C, C, true}, &c.x_slabs));
+      c.rotate(c.t1);
+    }
+  }
+  RC(c.gn(c.x, c.t1, w->no_g, w->no_b, H * H, 128, true, c.x_slabs));
+  const int M = c.n * H * H;
+  const EpiNCHWF32 eo{out, w->cout_b, H * H, 3};
+  int rc = 1;
+  if (conv_halo_allowed()) rc = launch_conv3x3_halo_out(c.t1, c.ws.zeros, (const half_t*)w->cout_w, c.n, H, H, 128, eo, c.st);
+  if (rc == 1) rc = launch_gemm_tn(ASrcConv<0>{c.t1, c.ws.zeros, H, H, 128, M}, (const half_t*)w->cout_w, 9L * 128, M, 4, 9 * 128, eo, c.st);
+  return rc;
 }
 
 extern "C" int lfm_vae_decode(const lfm_vae_weights* w, void* workspace, size_t workspace_bytes, const float* z, float* out, int N, int R,
@@ -682,51 +494,9 @@ extern "C" int lfm_vae_decode(const lfm_vae_weights* w, void* workspace, size_t 
   if ((uintptr_t)workspace & 255) return LFM_ERR_ALIGN;
   hipStream_t st = (hipStream_t)stream;
   if (lfm_zero_async(ws.zeros, 256, st)) return LFM_ERR_LAUNCH;
-  const int T = R * R;
   for (int n0 = 0; n0 < N; n0 += chunk) {
-    const int n = (N - n0 < chunk) ? N - n0 : chunk;
-    half_t *x = ws.b0, *t1 = ws.b1, *t2 = ws.b2, *t3 = ws.b3;
-    {
-      static lfm_device_mask set{0};
-      const unsigned long long dbit = lfm_device_bit();
-      if (lfm_device_todo(set, dbit)) {
-        if (hipFuncSetAttribute((const void*)vae_conv_in_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 36 * 512 * 4) != hipSuccess)
-          return LFM_ERR_LAUNCH;
-        lfm_device_done(set, dbit);
-      }
-    }
-    // batch 1 (--measure_time: run_sampling(1, ..), reference test_flow_latent.py:223-246): 1024 pixels are FOUR blocks of 256 pixels -- 183 us for 38 MFLOP
-    // (profiles/r06_latency_mode.txt); 16 pixels per block put them on 64 CUs
-    const int vci_ppb = (long)n * T >= 256L * VCI_PIX ? VCI_PIX : ((long)n * T >= 64L * VCI_PIX ? 64 : 16);
-    hipLaunchKernelGGL(vae_conv_in_kernel, dim3(cdiv((long)n * T, vci_ppb)), dim3(256), 36 * 512 * 4, st, z + (long)n0 * 4 * T, w->pq_w, w->pq_b,
-                       w->cin_w, w->cin_b, x, n, R, 512, vci_ppb);
-    LFM_CHECK_LAUNCH();
-    int H = R;
-    int xs = 0;  // partial-sum slabs per image that the producer of x left in ws.part (0 = none: the GroupNorm runs its own statistics pass)
-    RC(resnet(&w->mid[0], x, t1, t2, t3, ws, n, H, H, st, &xs));
-    RC(mid_attention(w->at_g, w->at_b, w->q_w, w->q_b, w->k_w, w->k_b, w->v_w, w->v_b, w->o_w, w->o_b, x, t1, t2, t3, ws, n, T, st, xs));
-    xs = 0;
-    RC(resnet(&w->mid[1], x, t1, t2, t3, ws, n, H, H, st, &xs));
-    for (int i = 0; i < 4; ++i) {
-      for (int j = 0; j < 3; ++j) RC(resnet(&w->up[i][j], x, t1, t2, t3, ws, n, H, H, st, &xs));
-      if (i < 3) {
-        const int C = w->up[i][2].cout;
-        H *= 2;
-        RC(conv3(x, (const half_t*)w->ups_w[i], w->ups_b[i], nullptr, t1, ws.zeros, n, H, H, C, C, true, st, ws.part, &xs));
-        half_t* o = t1;
-        t1 = x;
-        x = o;
-      }
-    }
-    RC(gn(x, t1, ws.stats, ws.part, w->no_g, w->no_b, n, H * H, 128, true, st, xs, ws.part_pairs));
-    const int M = n * H * H;
-    {
-      const EpiConvOutNCHW eo{out + (long)n0 * 3 * H * H, w->cout_b, H * H};
-      int rc = 1;  // CONV_IMPLICIT_GEMM: the implicit GEMM (A/B)
-      if (lfm_gemm_selected() == 0 && !(lfm_gemm_debug_flags() & LFM_DBG_CONV_IMPLICIT_GEMM)) rc = launch_conv3x3_halo_out(t1, ws.zeros, (const half_t*)w->cout_w, n, H, H, 128, eo, st);
-      if (rc == 1) rc = launch_gemm_tn(ASrcConv3x3<0>{t1, ws.zeros, H, H, 128, M, 0, 0}, (const half_t*)w->cout_w, 9L * 128, M, 4, 9 * 128, eo, st);
-      RC(rc);
-    }
+    VaeCtx c{ws, (N - n0 < chunk) ? N - n0 : chunk, st, ws.b0, ws.b1, ws.b2, ws.b3, 0, true};
+    RC(vae_decode_chunk(c, w, z + (long)n0 * 4 * R * R, out + (long)n0 * 3 * 64 * R * R, R));
   }
   return LFM_OK;
 }
@@ -741,10 +511,33 @@ extern "C" int lfm_vae_decode(const lfm_vae_weights* w, void* workspace, size_t 
 extern "C" int lfm_conv3x3_in_f32(const float* x_nchw, const float* w, const float* bias, void* out_nhwc, int N, int H, int W, int Cin, int Cout,
                                   lfm_stream_t stream);
 
-static int conv_down(const half_t* in, const half_t* w, const float* b, half_t* out, const half_t* zeros, int n, int Ho, int Wo, int C, hipStream_t st) {
+// diffusers Downsample2D (stride 2, input padded (0,1,0,1)): x [n, 2 Ho, 2 Wo, C] -> [n, Ho, Wo, C].  x is replaced by the result.
+int VaeCtx::conv_down(const void* w, const float* b, int Ho, int Wo, int C) {
   if (C % 64) return LFM_ERR_SHAPE;
   const int M = n * Ho * Wo;
-  return launch_gemm_auto(ASrcConvDown{in, zeros, Ho, Wo, C, M, 0, 0}, w, 9L * C, M, C, 9 * C, EpiConvF16{out, C, b, nullptr}, st);
+  RC(launch_gemm_auto(ASrcConv<3>{x, ws.zeros, Ho, Wo, C, M}, (const half_t*)w, 9L * C, M, C, 9 * C, EpiResidF16{t1, C, b, nullptr}, st));
+  rotate(t1);
+  return LFM_OK;
+}
+
+// one chunk of images: x [n,3,8R,8R] -> moments [n,8,R,R]
+static int vae_encode_chunk(VaeCtx& c, const lfm_vae_enc_weights* w, const float* x, float* moments, int R) {
+  int H = 8 * R;
+  RC(lfm_conv3x3_in_f32(x, w->cin_w, w->cin_b, c.x, c.n, H, H, 3, 128, (lfm_stream_t)c.st));
+  for (int i = 0; i < 4; ++i) {
+    for (int j = 0; j < 2; ++j) RC(c.resnet(&w->down[i][j], H, H));
+    if (i < 3) {
+      H /= 2;
+      RC(c.conv_down(w->ds_w[i], w->ds_b[i], H, H, w->down[i][1].cout));
+    }
+  }
+  RC(c.resnet(&w->mid[0], H, H));
+  RC(c.mid_attention(w, H * H));
+  RC(c.resnet(&w->mid[1], H, H));
+  RC(c.gn(c.x, c.t1, w->no_g, w->no_b, H * H, 512, true, 0));
+  const int M = c.n * H * H;
+  return launch_gemm_tn(ASrcConv<0>{c.t1, c.ws.zeros, H, H, 512, M}, (const half_t*)w->cout_w, 9L * 512, M, 8, 9 * 512,
+                        EpiMomentsNCHW{moments, w->cout_b, H * H, 8}, c.st);
 }
 
 extern "C" int lfm_vae_encode(const lfm_vae_enc_weights* w, void* workspace, size_t workspace_bytes, const float* x, float* moments, int N, int R,
@@ -756,30 +549,9 @@ extern "C" int lfm_vae_encode(const lfm_vae_enc_weights* w, void* workspace, siz
   if ((uintptr_t)workspace & 255) return LFM_ERR_ALIGN;
   hipStream_t st = (hipStream_t)stream;
   if (lfm_zero_async(ws.zeros, 256, st)) return LFM_ERR_LAUNCH;
-  const int S = 8 * R;
   for (int n0 = 0; n0 < N; n0 += chunk) {
-    const int n = (N - n0 < chunk) ? N - n0 : chunk;
-    half_t *h = ws.b0, *t1 = ws.b1, *t2 = ws.b2, *t3 = ws.b3;
-    RC(lfm_conv3x3_in_f32(x + (long)n0 * 3 * S * S, w->cin_w, w->cin_b, h, n, S, S, 3, 128, stream));
-    int H = S;
-    for (int i = 0; i < 4; ++i) {
-      for (int j = 0; j < 2; ++j) RC(resnet(&w->down[i][j], h, t1, t2, t3, ws, n, H, H, st));
-      if (i < 3) {
-        const int C = w->down[i][1].cout;
-        H /= 2;
-        RC(conv_down(h, (const half_t*)w->ds_w[i], w->ds_b[i], t1, ws.zeros, n, H, H, C, st));
-        half_t* o = t1;
-        t1 = h;
-        h = o;
-      }
-    }
-    RC(resnet(&w->mid[0], h, t1, t2, t3, ws, n, H, H, st));
-    RC(mid_attention(w->at_g, w->at_b, w->q_w, w->q_b, w->k_w, w->k_b, w->v_w, w->v_b, w->o_w, w->o_b, h, t1, t2, t3, ws, n, H * H, st));
-    RC(resnet(&w->mid[1], h, t1, t2, t3, ws, n, H, H, st));
-    RC(gn(h, t1, ws.stats, ws.part, w->no_g, w->no_b, n, H * H, 512, true, st, 0, ws.part_pairs));
-    const int M = n * H * H;
-    RC(launch_gemm_tn(ASrcConv3x3<0>{t1, ws.zeros, H, H, 512, M, 0, 0}, (const half_t*)w->cout_w, 9L * 512, M, 8, 9 * 512,
-                      EpiMomentsNCHW{moments + (long)n0 * 8 * H * H, w->cout_b, H * H, 8}, st));
+    VaeCtx c{ws, (N - n0 < chunk) ? N - n0 : chunk, st, ws.b0, ws.b1, ws.b2, ws.b3, 0, false};
+    RC(vae_encode_chunk(c, w, x + (long)n0 * 3 * 64 * R * R, moments + (long)n0 * 8 * R * R, R));
   }
   return LFM_OK;
 }
