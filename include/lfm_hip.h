@@ -301,6 +301,14 @@ int lfm_vae_groupnorm_f16(const void* x, void* y, const float* gamma, const floa
 int lfm_vae_conv3x3_gn_f16(const void* in, const void* w, const float* bias, const void* resid, void* conv_out, void* y, const float* gamma,
                            const float* beta, void* workspace, size_t workspace_bytes, int n, int H, int W, int Cin, int Cout, int ups, int silu,
                            int* stat_slabs, int* stat_kernel, lfm_stream_t stream);
+/* Test entry point for the mid-block attention of the decoder and the encoder, running their own host code (GroupNorm -> q, k, v -> softmax(q k^T / sqrt(512)) v
+ * -> to_out + x): x, out fp16 NHWC [n, T, 512]; weights fp16 [512][512] row-major [out][in] as lfm_vae_weights holds them; biases and GroupNorm
+ * parameters fp32; all 16-byte aligned.  T % 64 == 0 (the decoder's T = R^2 with R % 8 == 0).  Workspace (256-byte aligned):
+ * lfm_vae_mid_attention_workspace_bytes(n, T), 0 for a shape that is refused. */
+size_t lfm_vae_mid_attention_workspace_bytes(int n, int T);
+int lfm_vae_mid_attention_f16(const void* x, void* out, const float* gn_gamma, const float* gn_beta, const void* q_w, const float* q_b,
+                              const void* k_w, const float* k_b, const void* v_w, const float* v_b, const void* o_w, const float* o_b,
+                              void* workspace, size_t workspace_bytes, int n, int T, lfm_stream_t stream);
 
 /* u8 NHWC = trunc(clamp((x+1)/2, 0, 1) * 255) of fp32 NCHW images (test_flow_latent_ddp.py:131-135). */
 int lfm_images_to_uint8(const float* x, uint8_t* out, int N, int H, int W, lfm_stream_t stream);

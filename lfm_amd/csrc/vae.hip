@@ -443,6 +443,80 @@ int VaeCtx::mid_attention(const W* w, int T) {
   return LFM_OK;
 }
 
+// ---- test entry point: the decoder's mid-block attention on the caller's weights.  Workspace: [zeros 256 B][stats n x 32 x {mean, rstd}][part: the
+// decoder's share per image at R^2 = T, n x max(32 T, VGN_MAX_SLABS x 128) pairs, so the GroupNorm picks the slab count it picks in a decode]
+// [four rotating buffers, each n T (512 + max(512, T)) halves: Q | K, and V^T | P, are the largest tenants][S: n x T x T fp32].
+struct VaeAttnTestWeights {  // the fields mid_attention reads, named as in lfm_vae_weights / lfm_vae_enc_weights
+  const float *at_g, *at_b;
+  const void* q_w;
+  const float* q_b;
+  const void* k_w;
+  const float* k_b;
+  const void* v_w;
+  const float* v_b;
+  const void* o_w;
+  const float* o_b;
+};
+
+static size_t vae_attn_test_carve(int n, int T, void* ws, VaeCtx* c) {
+  const size_t M = (size_t)n * T, buf = M * (512 + (T > 512 ? (size_t)T : 512)) * 2;
+  const size_t part_pairs = (size_t)n * (32 * (size_t)T > (size_t)VGN_MAX_SLABS * 128 ? 32 * (size_t)T : (size_t)VGN_MAX_SLABS * 128);
+  size_t off = 0;
+  char* base = (char*)ws;
+  auto take = [&](size_t bytes) {
+    char* p = base ? base + off : nullptr;
+    off += a256(bytes);
+    return p;
+  };
+  half_t* zeros = (half_t*)take(256);
+  float* stats = (float*)take((size_t)n * 64 * 4);
+  float* part = (float*)take(part_pairs * 8);
+  half_t* b[4];
+  for (int i = 0; i < 4; ++i) b[i] = (half_t*)take(buf);
+  float* S = (float*)take(M * T * 4);
+  if (c) {
+    c->ws.zeros = zeros;
+    c->ws.stats = stats;
+    c->ws.part = part;
+    c->ws.part_pairs = part_pairs;
+    c->ws.S = S;
+    c->x = b[0];
+    c->t1 = b[1];
+    c->t2 = b[2];
+    c->t3 = b[3];
+  }
+  return off;
+}
+
+extern "C" size_t lfm_vae_mid_attention_workspace_bytes(int n, int T) {
+  if (n <= 0 || T <= 0 || (T % 64)) return 0;
+  return vae_attn_test_carve(n, T, nullptr, nullptr);
+}
+
+extern "C" int lfm_vae_mid_attention_f16(const void* x, void* out, const float* gn_gamma, const float* gn_beta, const void* q_w, const float* q_b,
+                                         const void* k_w, const float* k_b, const void* v_w, const float* v_b, const void* o_w, const float* o_b,
+                                         void* workspace, size_t workspace_bytes, int n, int T, lfm_stream_t stream) {
+  if (!x || !out || !gn_gamma || !gn_beta || !q_w || !q_b || !k_w || !k_b || !v_w || !v_b || !o_w || !o_b || !workspace) return LFM_ERR_ARG;
+  if (n <= 0 || T <= 0 || (T % 64)) return LFM_ERR_SHAPE;  // the decoder's T = R^2 with R % 8 == 0
+  if ((long)n * T * (T > 512 ? T : 512) >= (1L << 31)) return LFM_ERR_SHAPE;  // 32-bit row offsets of the GEMM operands
+  if (((uintptr_t)x | (uintptr_t)out | (uintptr_t)q_w | (uintptr_t)k_w | (uintptr_t)v_w | (uintptr_t)o_w | (uintptr_t)gn_gamma | (uintptr_t)gn_beta |
+       (uintptr_t)q_b | (uintptr_t)k_b | (uintptr_t)v_b | (uintptr_t)o_b) & 15)
+    return LFM_ERR_ALIGN;
+  if ((uintptr_t)workspace & 255) return LFM_ERR_ALIGN;
+  if (workspace_bytes < vae_attn_test_carve(n, T, nullptr, nullptr)) return LFM_ERR_WORKSPACE;
+  VaeCtx c{};
+  vae_attn_test_carve(n, T, workspace, &c);
+  c.n = n;
+  c.st = (hipStream_t)stream;
+  c.x_slabs = 0;
+  const size_t bytes = (size_t)n * T * 512 * 2;
+  if (hipMemcpyAsync(c.x, x, bytes, hipMemcpyDeviceToDevice, c.st) != hipSuccess) return LFM_ERR_LAUNCH;
+  const VaeAttnTestWeights w{gn_gamma, gn_beta, q_w, q_b, k_w, k_b, v_w, v_b, o_w, o_b};
+  RC(c.mid_attention(&w, T));
+  if (hipMemcpyAsync(out, c.x, bytes, hipMemcpyDeviceToDevice, c.st) != hipSuccess) return LFM_ERR_LAUNCH;
+  return LFM_OK;
+}
+
 // post_quant_conv + conv_in: z [n,4,R,R] fp32 NCHW -> out fp16 NHWC [n,R,R,512]
 static int vae_conv_in(const lfm_vae_weights* w, const float* z, half_t* out, int n, int R, hipStream_t st) {
   static lfm_device_mask set{0};

@@ -169,6 +169,10 @@ def lib():
     L.lfm_vae_groupnorm_f16.argtypes = [V, V, V, V, V, C.c_size_t, I, I, I, I, V]
     L.lfm_vae_conv3x3_gn_f16.restype = I
     L.lfm_vae_conv3x3_gn_f16.argtypes = [V, V, V, V, V, V, V, V, V, C.c_size_t, I, I, I, I, I, I, I, C.POINTER(C.c_int), C.POINTER(C.c_int), V]
+    L.lfm_vae_mid_attention_workspace_bytes.restype = C.c_size_t
+    L.lfm_vae_mid_attention_workspace_bytes.argtypes = [I, I]
+    L.lfm_vae_mid_attention_f16.restype = I
+    L.lfm_vae_mid_attention_f16.argtypes = [V] * 13 + [C.c_size_t, I, I, V]
     _lib = L
     return L
 

@@ -74,6 +74,48 @@ def test_vae_encode_matches_oracle(N, S, chunk):
     assert rel_l2(img, ref_img) < 1e-2
 
 
+def test_vae_decode_at_r24_takes_every_fallback():
+    """R = 24 (R % 8 == 0 is all the ABI asks): the 24 x 24 level is not 16-aligned, so the halo convolution declines; HW = 576 is no multiple of 256,
+    so no convolution hands statistics to a GroupNorm there and the separate statistics pass runs; T = 576 leaves the batched mid-attention GEMMs a
+    ragged last tile per image; 3 latents in chunks of 2 leave a ragged second chunk."""
+    from lfm_amd.autoencoder import AutoencoderKL
+
+    dev = torch.device("cuda:0")
+    sd = vae_ref.make_vae_state(seed=3)
+    vae = AutoencoderKL(decode_chunk=2)
+    vae.load_state_dict(sd, strict=True)
+    vae = vae.to(dev)
+    z = torch.randn(3, 4, 24, 24, generator=torch.Generator().manual_seed(3 + 24)) * 1.5
+    ref = vae_ref.vae_decode(sd, z)
+    got = vae.decode(z.to(dev)).sample
+    assert got.shape == (3, 3, 192, 192)
+    assert float(ref.abs().mean()) > 1e-2
+    print("R = 24 decode rel-L2", rel_l2(got, ref), [rel_l2(got[[i]], ref[[i]]) for i in range(3)])
+    assert rel_l2(got, ref) < 5e-3
+    for i in range(3):
+        assert rel_l2(got[[i]], ref[[i]]) < 5e-3, i
+    assert torch.equal(got, vae.decode(z.to(dev)).sample)
+
+
+def test_vae_encode_at_s192():
+    """The encoder at R = 24: the same fallbacks at its last level, and the 576-token mid attention."""
+    from lfm_amd.autoencoder import AutoencoderKL
+
+    dev = torch.device("cuda:0")
+    sd = vae_ref.make_vae_state(seed=3, with_encoder=True)
+    vae = AutoencoderKL(with_encoder=True)
+    vae.load_state_dict(sd, strict=True)
+    vae = vae.to(dev)
+    x = torch.randn(2, 3, 192, 192, generator=torch.Generator().manual_seed(2 + 192)).clamp(-1, 1)
+    ref = vae_ref.vae_encode_moments(sd, x)
+    got = vae.encode(x.to(dev)).latent_dist.parameters
+    assert got.shape == (2, 8, 24, 24)
+    assert float(ref.abs().mean()) > 1e-2
+    print("S = 192 encode rel-L2", rel_l2(got, ref))
+    assert rel_l2(got, ref) < 5e-3
+    assert torch.equal(got, vae.encode(x.to(dev)).latent_dist.parameters)
+
+
 @pytest.mark.parametrize("N,H,W,Cin,Cout,mode", [(2, 48, 48, 128, 128, 0), (2, 32, 64, 64, 128, 0), (1, 64, 32, 256, 256, 0), (3, 16, 16, 192, 128, 0),
                                                   (2, 32, 32, 128, 384, 1), (1, 96, 32, 64, 128, 1)])
 def test_halo_conv_matches_torch_and_the_implicit_gemm(N, H, W, Cin, Cout, mode):
