@@ -235,6 +235,11 @@ int lfm_dit_attention(const void* Q, const void* K, const void* Vt, void* O, int
  * D = heads * head_dim. */
 int lfm_dit_attention_hd(const void* Q, const void* K, const void* Vt, void* O, int batch, int heads, int head_dim, int T,
                          lfm_stream_t stream);
+/* Which kernel lfm_dit_attention_hd runs for this shape under the calling thread's flags and the library options, or LFM_ERR_SHAPE for a shape no kernel
+ * serves: 1 = the 16-token kernel, 2 = one workgroup per (image, head) item, 3 = the same with four waves x 64 queries (flag LFM_DBG_ATT_WIDE), 4 = four key
+ * chunks (1024 tokens), 5 = the latency-mode query split (256 tokens x head_dim 64, at most 64 items), 6 = the streamed kernel (LFM_OPT_ATTENTION_STREAM;
+ * more than 64 items, each tensor below 2 GiB).  No launch; usable without a GPU. */
+int lfm_attention_plan(int batch, int heads, int head_dim, int T);
 
 /* ------------------------------------------------------------------ first-stage VAE decoder
  * Decode half of diffusers AutoencoderKL, config stabilityai/sd-vae-ft-mse (latent 4, block_out_channels

@@ -16,15 +16,14 @@
 // Keys are consumed in 32-key blocks with an online softmax (running max m, running sum l), which keeps
 // the live state at S 32 + P 16 + O 64 + Q 32 registers for hd 64, JQ 2 (2 waves / SIMD).
 #pragma once
-#include "gemm_kernel.h"
-#include "attention_stream_kernel.h"
-
+#include <type_traits>
+#include "attention_common.h"
+#include "attention_stream_kernel.h"  // attention_launch runs its kernel too
 
 // MODE 3 (measurement only): s_memtime stamps of wave 0 of the first workgroup (slots 0..31) and of the last one (32..63), read back with
 // lfm_attention_trace_read.  Slots: 0 start, 1 all DMAs / Q loads issued, 2 K and Q landed (first barrier), 3 + 4 k + {0: S(next) issued,
 // 1: softmax + PV of the even block done, 2: S(next even) issued, 3: softmax + PV of the odd block done} for the k-th loop iteration,
 // 19 stores issued, 20 stores acknowledged; inside the first softmax_pv: 21 softmax VALU done, 22 V^T landed (barrier), 23 PV MFMAs issued.
-// (the arrays are declared by attention_stream_kernel.h, included above: both kernels stamp into them)
 // MODE 3 also records, per workgroup (linear id < 2048): {HW_ID | XCC_ID << 32, start, loads landed, end} -- which CU it ran on and when
 
 // MODE (measurement only, tools/r2_probe3.py): 0 = the kernel; 1 = memory phases only (stage K / V^T, fetch Q, store a row per query, no
@@ -220,7 +219,7 @@ __global__ __launch_bounds__((T / (32 * JQ * QS)) * 64, HD == 64 && QS == 1 ? (T
   auto softmax_pv = [&](f32x16 (&S)[JQ], int kb) {
     half8_t P[JQ][2];
 #pragma unroll
-    for (int jq = 0; jq < JQ; ++jq)  // attention_stream_kernel.h: optimistic exponentials against the running reference, full path for the first block / on overflow risk
+    for (int jq = 0; jq < JQ; ++jq)  // attention_common.h: optimistic exponentials against the running reference, full path for the first block / on overflow risk
       att_softmax_block<NDB>(S[jq], kb == 0 && first_chunk, mrun[jq], lrun[jq], Oa[jq], scale_log2e, P[jq]);
     if (kb == 0 && first_chunk) {  // V^T was issued after K and Q: only now must it have landed (every wave's share)
       stamp(21);
@@ -387,111 +386,95 @@ __global__ __launch_bounds__(64) void dit_attention_t16_kernel(const half_t* __r
   }
 }
 
-// Q, K: [batch*T, heads*hd] token-major; Vt: [batch][heads*hd][T]; O: [batch*T, heads*hd].  hd 64 / 72; T in {16, 64, 128, 256, 1024}.
-static int attention_launch(const half_t* Q, const half_t* K, const half_t* Vt, half_t* O, int batch, int heads, int hd, int T, hipStream_t st) {
-  if (hd != 64 && hd != 72) return LFM_ERR_SHAPE;
-  const int D = heads * hd;
-  const float sl2 = (hd == 64 ? 0.125f : 0.11785113019775793f) * 1.4426950408889634f;  // hd^-0.5 * log2(e)
-  const size_t lds = (size_t)T * hd * 4;  // K + V^T, 2 bytes each
-  dim3 grid(heads, batch);
-  // Rounds 1-3: 8 waves x 32 queries (4 waves/SIMD) measured 44.3 us vs 40.2 us for 4 waves x 64 queries (two 8-byte V^T reads per fragment then).
-  // Round 4: with the V^T operand a single conflict-free ds_read_b128 (vt_pos) the balance flipped -- 8 waves x 32 queries (126 VGPRs: four waves per
-  // SIMD) 35.7 us, 4 waves x 64 queries (228 VGPRs: two) 38.9 us -- so the narrow shape is the default; flag ATT_WIDE selects the wide one (A/B)
-  const bool narrow = T == 256 && !(lfm_gemm_debug_flags() & LFM_DBG_ATT_WIDE);
-  [[maybe_unused]] const int mode = (lfm_gemm_debug_flags() >> LFM_DBG_ATT_MODE_SHIFT) & LFM_DBG_ATT_MODE_MASK;  // the measurement-only variants MODE 1 / 2 / 3 (hd 64, 256 tokens)
+// ---- dispatch.  attention_choose is the ONE place that knows which kernel serves a shape (lfm_attention_plan returns its answer without a launch:
+// tests/test_host_logic.py pins the table); attention_launch runs that answer.
+enum {
+  ATT_KERN_T16 = 1,     // dit_attention_t16_kernel
+  ATT_KERN_ITEM = 2,    // one workgroup per (image, head): 64 / 128 / 256 tokens
+  ATT_KERN_WIDE = 3,    // the same with four waves x 64 queries (flag ATT_WIDE; hd 64, 256 tokens)
+  ATT_KERN_CHUNKS = 4,  // 1024 tokens: four key chunks of 256 through the LDS, one workgroup per 256 queries
+  ATT_KERN_QSPLIT = 5,  // latency mode (hd 64, 256 tokens, at most 64 items): two workgroups of four waves per item
+  ATT_KERN_STREAM = 6,  // attention_stream_kernel.h (hd 64, 256 tokens, more than 64 items): persistent workgroups, K / V^T streamed through an LDS ring
+};
+// the measurement-only variants MODE 1 / 2 / 3 of the hd-64, 256-token kernels (product builds have none)
+static inline int att_measure_mode() {
 #ifdef LFM_MEASURE
-  if (mode && hd == 64 && T == 256 && narrow && lfm_attention_stream_enabled() && batch * heads > 64) {  // the streamed kernel's phase split
-    const int rc = attention_stream_launch(Q, K, Vt, O, batch, heads, st, mode);
-    if (rc <= 0) return rc;
-  }
-  if (mode && hd == 64 && T == 256 && narrow) {  // the shipped shape (8 waves x 32 queries); ATT_WIDE + mode = the wide one below
-    static bool set = false;
-    if (!set) {
-      (void)hipFuncSetAttribute((const void*)dit_attention_kernel<256, 1, 64, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 256 * 64 * 4);
-      (void)hipFuncSetAttribute((const void*)dit_attention_kernel<256, 1, 64, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 256 * 64 * 4);
-      (void)hipFuncSetAttribute((const void*)dit_attention_kernel<256, 1, 64, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, 256 * 64 * 4);
-      set = true;
-    }
-    if (mode == 3) hipLaunchKernelGGL((dit_attention_kernel<256, 1, 64, 3>), grid, dim3(512), lds, st, Q, K, Vt, O, D, heads, sl2, lfm_stagger_ticks());
-    else if (mode == 1) hipLaunchKernelGGL((dit_attention_kernel<256, 1, 64, 1>), grid, dim3(512), lds, st, Q, K, Vt, O, D, heads, sl2, lfm_stagger_ticks());
-    else hipLaunchKernelGGL((dit_attention_kernel<256, 1, 64, 2>), grid, dim3(512), lds, st, Q, K, Vt, O, D, heads, sl2, lfm_stagger_ticks());
-    LFM_CHECK_LAUNCH();
-    return LFM_OK;
-  }
-  if (mode && hd == 64 && T == 256) {
-    static bool set = false;
-    if (!set) {
-      (void)hipFuncSetAttribute((const void*)dit_attention_kernel<256, 2, 64, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 256 * 64 * 4);
-      (void)hipFuncSetAttribute((const void*)dit_attention_kernel<256, 2, 64, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 256 * 64 * 4);
-      (void)hipFuncSetAttribute((const void*)dit_attention_kernel<256, 2, 64, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, 256 * 64 * 4);
-      set = true;
-    }
-    if (mode == 3) hipLaunchKernelGGL((dit_attention_kernel<256, 2, 64, 3>), grid, dim3(256), lds, st, Q, K, Vt, O, D, heads, sl2, lfm_stagger_ticks());
-    else if (mode == 1) hipLaunchKernelGGL((dit_attention_kernel<256, 2, 64, 1>), grid, dim3(256), lds, st, Q, K, Vt, O, D, heads, sl2, lfm_stagger_ticks());
-    else hipLaunchKernelGGL((dit_attention_kernel<256, 2, 64, 2>), grid, dim3(256), lds, st, Q, K, Vt, O, D, heads, sl2, lfm_stagger_ticks());
-    LFM_CHECK_LAUNCH();
-    return LFM_OK;
-  }
+  return (lfm_gemm_debug_flags() >> LFM_DBG_ATT_MODE_SHIFT) & LFM_DBG_ATT_MODE_MASK;
+#else
+  return 0;
 #endif
-  if (T == 16) {
+}
+// Kernel for `batch` images x `heads` heads of `hd` dims x T tokens under the calling thread's flags and the library options, or LFM_ERR_SHAPE.  Pure host code.
+static inline int attention_choose(int batch, int heads, int hd, int T) {
+  if (hd != 64 && hd != 72) return LFM_ERR_SHAPE;
+  if (hd == 64 && T == 256) {  // the benchmarked shape
+    // Rounds 1-3: 8 waves x 32 queries (4 waves/SIMD) measured 44.3 us vs 40.2 us for 4 waves x 64 queries (two 8-byte V^T reads per fragment then).
+    // Round 4: with the V^T operand a single conflict-free ds_read_b128 (vt_pos) the balance flipped -- 8 waves x 32 queries (126 VGPRs: four waves per
+    // SIMD) 35.7 us, 4 waves x 64 queries (228 VGPRs: two) 38.9 us -- so the narrow shape is the default; flag ATT_WIDE selects the wide one (A/B)
+    if (lfm_gemm_debug_flags() & LFM_DBG_ATT_WIDE) return ATT_KERN_WIDE;
     const int items = batch * heads;
-    if (hd == 64) hipLaunchKernelGGL(dit_attention_t16_kernel<64>, dim3((items + 3) / 4), dim3(64), 0, st, Q, K, Vt, O, D, heads, items, sl2);
-    else hipLaunchKernelGGL(dit_attention_t16_kernel<72>, dim3((items + 3) / 4), dim3(64), 0, st, Q, K, Vt, O, D, heads, items, sl2);
-    LFM_CHECK_LAUNCH();
-    return LFM_OK;
+    if (items <= 64 && !att_measure_mode()) return ATT_KERN_QSPLIT;  // (it has no measurement variants: a mode runs the per-item kernel's)
+    // the streamed kernel addresses each of Q, K, V^T, O with 32-bit buffer offsets whose bit 31 is its out-of-range mark: tensors below 2 GiB only
+    if (items > 64 && lfm_attention_stream_enabled() && (long)items * 256 * 64 * 2 < (1L << 31)) return ATT_KERN_STREAM;
+    return ATT_KERN_ITEM;
   }
-  // the dynamic-LDS attribute is per (function, device): one bit per device and instantiation
-  const unsigned long long dbit = lfm_device_bit();
-#define ATT_CASE(TT, JQ, HD)                                                                                                             \
-  {                                                                                                                                     \
-    static lfm_device_mask set{0};                                                                                                      \
-    if (lfm_device_todo(set, dbit)) {                                                                                                   \
-      (void)hipFuncSetAttribute((const void*)dit_attention_kernel<TT, JQ, HD>, hipFuncAttributeMaxDynamicSharedMemorySize, TT * HD * 4); \
-      lfm_device_done(set, dbit);                                                                                                       \
-    }                                                                                                                                   \
-    hipLaunchKernelGGL((dit_attention_kernel<TT, JQ, HD>), grid, dim3((TT / (32 * JQ)) * 64), lds, st, Q, K, Vt, O, D, heads, sl2, lfm_stagger_ticks()); \
-  }
-  if (T == 1024) {  // four key chunks of 256 through the LDS, one workgroup per 256 queries
-    const dim3 grid4(heads, batch, 4);
-    if (hd == 64) {
-      static lfm_device_mask set{0};
-      if (lfm_device_todo(set, dbit)) (void)hipFuncSetAttribute((const void*)dit_attention_kernel<256, 1, 64, 0, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, 256 * 64 * 4);
-      lfm_device_done(set, dbit);
-      hipLaunchKernelGGL((dit_attention_kernel<256, 1, 64, 0, 4>), grid4, dim3(512), (size_t)256 * 64 * 4, st, Q, K, Vt, O, D, heads, sl2, lfm_stagger_ticks());
-    } else {
-      static lfm_device_mask set{0};  // its own flag: the hd-72 kernel needs 72 KiB, above the 64-KiB default, whatever the hd-64 one did before
-      if (lfm_device_todo(set, dbit)) (void)hipFuncSetAttribute((const void*)dit_attention_kernel<256, 1, 72, 0, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, 256 * 72 * 4);
-      lfm_device_done(set, dbit);
-      hipLaunchKernelGGL((dit_attention_kernel<256, 1, 72, 0, 4>), grid4, dim3(512), (size_t)256 * 72 * 4, st, Q, K, Vt, O, D, heads, sl2, lfm_stagger_ticks());
-    }
-    LFM_CHECK_LAUNCH();
-    return LFM_OK;
-  }
-  if (hd == 64 && T == 256 && narrow && batch * heads <= 64) {  // latency mode: two workgroups of four waves per (image, head)
-    static lfm_device_mask set{0};
-    if (lfm_device_todo(set, dbit)) (void)hipFuncSetAttribute((const void*)dit_attention_kernel<256, 1, 64, 0, 1, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 256 * 64 * 4);
-    lfm_device_done(set, dbit);
-    hipLaunchKernelGGL((dit_attention_kernel<256, 1, 64, 0, 1, 2>), dim3(heads, batch, 2), dim3(256), lds, st, Q, K, Vt, O, D, heads, sl2, 0);
-    LFM_CHECK_LAUNCH();
-    return LFM_OK;
-  }
-  if (hd == 64 && T == 256 && narrow && lfm_attention_stream_enabled()) {  // round 6: persistent workgroups, K / V^T streamed through an LDS ring (attention_stream_kernel.h)
-    const int rc = attention_stream_launch(Q, K, Vt, O, batch, heads, st);
-    if (rc <= 0) return rc;  // 1: not for that kernel (tensors of 2 GiB and more) -> the per-item kernel below
-  }
-  if (hd == 64) {
-    if (T == 64) ATT_CASE(64, 2, 64)
-    else if (T == 128) ATT_CASE(128, 2, 64)
-    else if (T == 256 && narrow) ATT_CASE(256, 1, 64)
-    else if (T == 256) ATT_CASE(256, 2, 64)
-    else return LFM_ERR_SHAPE;
-  } else {  // hd 72: one query block per wave (48 accumulator + 20 Q registers per block)
-    if (T == 64) ATT_CASE(64, 1, 72)
-    else if (T == 128) ATT_CASE(128, 1, 72)
-    else if (T == 256) ATT_CASE(256, 1, 72)
-    else return LFM_ERR_SHAPE;
-  }
-#undef ATT_CASE
+  if (T == 16) return ATT_KERN_T16;
+  if (T == 1024) return ATT_KERN_CHUNKS;
+  if (T == 64 || T == 128 || T == 256) return ATT_KERN_ITEM;
+  return LFM_ERR_SHAPE;
+}
+
+struct AttArgs {  // what every launch below passes on
+  const half_t *Q, *K, *Vt;
+  half_t* O;
+  int batch, heads;
+  float sl2;  // hd^-0.5 * log2(e)
+  int stag;   // measurement builds: start offset of the second resident workgroups
+  hipStream_t st;
+};
+// One instantiation of dit_attention_kernel: grid, block and LDS size are what its template arguments say.
+template <int T, int JQ, int HD, int MODE = 0, int NCH = 1, int QS = 1>
+static int att_run(const AttArgs& a) {
+  constexpr int LDS = T * HD * 4;  // K + V^T, 2 bytes each (hd 72: 72 KiB, above the 64-KiB default)
+  if (!lfm_kernel_lds<&dit_attention_kernel<T, JQ, HD, MODE, NCH, QS>>(LDS)) return LFM_ERR_LAUNCH;
+  hipLaunchKernelGGL((dit_attention_kernel<T, JQ, HD, MODE, NCH, QS>), dim3(a.heads, a.batch, NCH * QS), dim3(T / (32 * JQ * QS) * 64), LDS, a.st, a.Q, a.K, a.Vt,
+                     a.O, a.heads * HD, a.heads, a.sl2, a.stag);
   LFM_CHECK_LAUNCH();
   return LFM_OK;
+}
+// f(std::integral_constant<int, MODE>) for the calling thread's measurement mode
+template <class F>
+static int att_with_mode(F&& f) {
+#ifdef LFM_MEASURE
+  switch (att_measure_mode()) {
+    case 1: return f(std::integral_constant<int, 1>{});
+    case 2: return f(std::integral_constant<int, 2>{});
+    case 3: return f(std::integral_constant<int, 3>{});
+  }
+#endif
+  return f(std::integral_constant<int, 0>{});
+}
+
+// Q, K: [batch*T, heads*hd] token-major; Vt: [batch][heads*hd][T]; O: [batch*T, heads*hd].  hd 64 / 72; T in {16, 64, 128, 256, 1024}.
+static int attention_launch(const half_t* Q, const half_t* K, const half_t* Vt, half_t* O, int batch, int heads, int hd, int T, hipStream_t st) {
+  const int kern = attention_choose(batch, heads, hd, T);
+  if (kern < 0) return kern;
+  AttArgs a{Q, K, Vt, O, batch, heads, (hd == 64 ? 0.125f : 0.11785113019775793f) * 1.4426950408889634f, lfm_stagger_ticks(), st};
+  switch (kern) {
+    case ATT_KERN_T16: {
+      const int items = batch * heads, D = heads * hd;
+      if (hd == 64) hipLaunchKernelGGL(dit_attention_t16_kernel<64>, dim3((items + 3) / 4), dim3(64), 0, st, Q, K, Vt, O, D, heads, items, a.sl2);
+      else hipLaunchKernelGGL(dit_attention_t16_kernel<72>, dim3((items + 3) / 4), dim3(64), 0, st, Q, K, Vt, O, D, heads, items, a.sl2);
+      LFM_CHECK_LAUNCH();
+      return LFM_OK;
+    }
+    case ATT_KERN_CHUNKS: return hd == 64 ? att_run<256, 1, 64, 0, 4>(a) : att_run<256, 1, 72, 0, 4>(a);
+    case ATT_KERN_QSPLIT: a.stag = 0; return att_run<256, 1, 64, 0, 1, 2>(a);
+    case ATT_KERN_STREAM: return att_with_mode([&](auto m) { return attention_stream_launch<decltype(m)::value>(Q, K, Vt, O, batch, heads, st); });
+    case ATT_KERN_WIDE: return att_with_mode([&](auto m) { return att_run<256, 2, 64, decltype(m)::value>(a); });
+  }
+  // ATT_KERN_ITEM.  hd 72: one query block per wave (48 accumulator + 20 Q registers per block)
+  if (hd == 72) return T == 64 ? att_run<64, 1, 72>(a) : T == 128 ? att_run<128, 1, 72>(a) : att_run<256, 1, 72>(a);
+  if (T == 256) return att_with_mode([&](auto m) { return att_run<256, 1, 64, decltype(m)::value>(a); });
+  return T == 64 ? att_run<64, 2, 64>(a) : att_run<128, 2, 64>(a);
 }

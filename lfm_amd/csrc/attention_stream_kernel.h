@@ -11,7 +11,7 @@
 // workgroup's first item is ever waited for with nothing else to do.
 //
 // Same arithmetic as dit_attention_kernel<256, 1, 64>: eight waves x 32 queries, S^T = K Q^T on v_mfma_f32_32x32x16_f16 (a lane owns one query: row max / row sum
-// are in-lane plus one lane^32 exchange), online softmax over 32-key blocks (att_softmax_block below, shared by both kernels), P rounded to fp16 straight into the
+// are in-lane plus one lane^32 exchange), online softmax over 32-key blocks (att_softmax_block, attention_common.h, shared by both kernels), P rounded to fp16 straight into the
 // B operand of O^T = V^T P^T, V^T rows in the vt_pos token order -- the results are BIT-IDENTICAL to that kernel's (tests/test_gpu_dit.py::
 // test_attention_stream_matches_per_item).
 //   * every LDS address of the key loop is one of four per-lane registers + an immediate (slot, key block and k-slot are compile-time: the item body is fully unrolled);
@@ -29,83 +29,10 @@
 // per-workgroup trace shows both resident from the start: profiles/r06_attention_stream.txt.)
 #pragma once
 #include <stdlib.h>
-#include "gemm_kernel.h"
+#include "attention_common.h"
 
-#define ATS_VMCNT(n) asm volatile("s_waitcnt vmcnt(" #n ")" ::: "memory")
-#define ATS_BARRIER()                              \
-  do {                                             \
-    __builtin_amdgcn_s_barrier();                  \
-    asm volatile("" ::: "memory");                 \
-  } while (0)
-
-// One 32-key block of the online softmax for the query a lane owns (S: its 16 scores of the block, the other 16 live in lane ^ 32), shared by the streamed and the
-// per-item kernels (same arithmetic in the same order => bit-identical results whichever kernel evaluates an item).  Round 6: the key loop is bound by instruction
-// ISSUE, not by a pipe -- per SIMD, whether it holds two or four waves, one 32-key block of one wave goes through in ~850 cycles while its 8 MFMAs occupy the matrix
-// pipe for 256 and ~5 single-issue instructions hide under each of them (profiles/r06_attention_stream.txt) -- so the block is written for instruction count:
-//   * OPTIMISTIC exponentials: p = 2^((s - mrun) scale) is taken against the running reference mrun WITHOUT first looking for the block's maximum; the lane's own sum of
-//     its 16 p (needed anyway) tells whether that was safe -- every p <= sum <= 2^14 stays far inside fp16 (P is the fp16 operand of the P V MFMA; row sums and O are
-//     fp32).  Only when some lane's sum exceeds 2^14 (or is not a number), and for the first block of an item, the block takes the FULL path: row maximum (3-input
-//     maxima + one lane ^ 32 exchange), mrun <- max, O and l rescaled by 2^((old - new) scale), exponentials again.  The reference follows the maximum lazily, as
-//     before (rounds 3-5 moved it when the maximum had grown by more than 2^8); fp16 rounds P relative to its size, so the result does not depend on where in
-//     [2^-14 .. 2^14] the block's largest p lands.
-//   * row sum as a TREE of packed adds (8 issue slots; the serial chain of rounds 1-5 drew a wait state per link: 18).
-// `first` is wave-uniform.  Returns the packed P of the block (k-slots 0 and 1) in P.
-template <int NDB>
-__device__ __forceinline__ void att_softmax_block(const f32x16& S, bool first, float& mrun, float& lrun, f32x16 (&Oa)[NDB], float scale_log2e, half8_t (&P)[2]) {
-  f32x2 p[8];
-  const f32x2 sc2 = {scale_log2e, scale_log2e};
-  auto expo = [&]() {
-    const float mbs = mrun * scale_log2e;
-    const f32x2 nmb2 = {-mbs, -mbs};
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      const f32x2 s2 = {S[2 * e], S[2 * e + 1]};
-      const f32x2 a2 = __builtin_elementwise_fma(s2, sc2, nmb2);  // ONE fused multiply-add on every path and in every kernel that inlines this (v_pk_fma_f32 / v_fma_f32)
-      p[e] = (f32x2){__builtin_amdgcn_exp2f(a2.x), __builtin_amdgcn_exp2f(a2.y)};
-    }
-  };
-  auto lane_sum = [&]() {
-    const f32x2 t = ((p[0] + p[1]) + (p[2] + p[3])) + ((p[4] + p[5]) + (p[6] + p[7]));  // v_pk_add_f32 x 7
-    return t.x + t.y;
-  };
-  float ls = 0.f;
-  bool full = first;
-  if (!first) {
-    expo();
-    ls = lane_sum();
-    full = !__all(ls <= 16384.0f);
-  }
-  if (full) {  // wave-uniform
-    float mx = fmaxf(fmaxf(S[0], S[1]), S[2]);
-#pragma unroll
-    for (int e = 3; e < 15; e += 2) mx = fmaxf(fmaxf(mx, S[e]), S[e + 1]);
-    mx = fmaxf(mx, S[15]);
-    mx = fmaxf(mx, xhalf(mx));
-    const float mnew = fmaxf(mrun, mx);
-    const float alpha = __builtin_amdgcn_exp2f((mrun - mnew) * scale_log2e);
-    mrun = mnew;
-    lrun *= alpha;
-#pragma unroll
-    for (int db = 0; db < NDB; ++db) Oa[db] *= alpha;
-    expo();
-    ls = lane_sum();
-  }
-  lrun += ls;
-#pragma unroll
-  for (int e = 0; e < 8; ++e) {
-    P[e >> 2][(e & 3) * 2] = (half_t)p[e].x;
-    P[e >> 2][(e & 3) * 2 + 1] = (half_t)p[e].y;
-  }
-}
-
-#ifndef ATT_TRACE_SLOTS
-#define ATT_TRACE_SLOTS 64
-#define ATT_WG_TRACE 2048
-static __device__ unsigned long long att_trace[ATT_TRACE_SLOTS];
-static __device__ unsigned long long att_wg_trace[ATT_WG_TRACE][4];
-#endif
 // MODE (measurement builds only, the ATT_MODE field of the flags, like the per-item kernel): 1 = memory only (LDS-DMA ring, waits, barriers, Q loads, O stores; no MFMA / softmax),
-// 2 = compute only (every LDS-DMA and Q load out of range: no operand traffic), 3 = s_memtime trace (attention_kernel.h: att_trace = wave 0 of the first / last
+// 2 = compute only (every LDS-DMA and Q load out of range: no operand traffic), 3 = s_memtime trace (att_trace = wave 0 of the first / last
 // workgroup: slot 0 start, 1 prologue issued, 2 + 14 i + 3 j + {0 before the wait, 1 after the wait, 2 after the barrier} for stage j of the workgroup's item i < 2,
 // 14 + 14 i key loop done, 15 + 14 i stores issued; att_wg_trace = {HW_ID | XCC_ID << 32, start, first barrier passed, end} per workgroup)
 template <int MODE = 0>
@@ -338,44 +265,22 @@ __global__ __launch_bounds__(512, 4) void dit_attention_stream_kernel(const half
   }
 }
 
-// grid = min(items, 2 x CUs): two resident workgroups per CU (72 KiB of LDS, <= 128 VGPRs)
-static int attention_stream_launch(const half_t* Q, const half_t* K, const half_t* Vt, half_t* O, int batch, int heads, hipStream_t st, int mode = 0) {
+// grid = min(items, 2 x CUs): two resident workgroups per CU (72 KiB of LDS, <= 128 VGPRs).  MODE: the measurement variants (attention_launch picks one).
+template <int MODE = 0>
+static int attention_stream_launch(const half_t* Q, const half_t* K, const half_t* Vt, half_t* O, int batch, int heads, hipStream_t st) {
   constexpr int T = 256, HD = 64, LDS = 4 * 16384 + 8 * 1024;
   const long items = (long)batch * heads;
   const long bytes = items * T * HD * 2;  // = batch * T * D * 2: each of Q, K, V^T, O
-  if (items <= 0 || bytes >= (1L << 31)) return 1;  // not for this kernel (32-bit buffer offsets, bit 31 = the out-of-range mark)
-  int devid = 0;
-  (void)hipGetDevice(&devid);
-  static lfm_device_mask set{0};
-  static std::atomic<int> cus[64];
-  const unsigned long long dbit = 1ull << (devid & 63);
-  if (lfm_device_todo(set, dbit)) {
-    (void)hipFuncSetAttribute((const void*)dit_attention_stream_kernel<0>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-#ifdef LFM_MEASURE
-    (void)hipFuncSetAttribute((const void*)dit_attention_stream_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-    (void)hipFuncSetAttribute((const void*)dit_attention_stream_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-    (void)hipFuncSetAttribute((const void*)dit_attention_stream_kernel<3>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-#endif
-    int n = 0;
-    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, devid) != hipSuccess || n <= 0) n = 256;
-    cus[devid & 63].store(n, std::memory_order_relaxed);
-    lfm_device_done(set, dbit);
-  }
+  if (items <= 0 || bytes >= (1L << 31)) return LFM_ERR_SHAPE;  // 32-bit buffer offsets, bit 31 = the out-of-range mark: attention_choose never sends such tensors here
+  if (!lfm_kernel_lds<&dit_attention_stream_kernel<MODE>>(LDS)) return LFM_ERR_LAUNCH;
   long per_cu = 2;
 #ifdef LFM_MEASURE
   if (const char* e = getenv("LFM_ATS_WG_PER_CU")) per_cu = atoi(e) == 1 ? 1 : 2;  // measurement: one persistent workgroup per CU (twice the items each)
 #endif
-  const int G = (int)(items < per_cu * cus[devid & 63].load(std::memory_order_relaxed) ? items : per_cu * cus[devid & 63].load(std::memory_order_relaxed));
+  const long resident = per_cu * lfm_cu_count();
+  const int G = (int)(items < resident ? items : resident);
   const float sl2 = 0.125f * 1.4426950408889634f;  // hd^-0.5 * log2(e)
-#define ATS_LAUNCH(M) hipLaunchKernelGGL(dit_attention_stream_kernel<M>, dim3(G), dim3(512), LDS, st, Q, K, Vt, O, heads * HD, heads, (int)items, G / heads, G % heads, (unsigned)bytes, sl2)
-#ifdef LFM_MEASURE
-  if (mode == 1) ATS_LAUNCH(1);
-  else if (mode == 2) ATS_LAUNCH(2);
-  else if (mode == 3) ATS_LAUNCH(3);
-  else
-#endif
-    ATS_LAUNCH(0);
-#undef ATS_LAUNCH
-  (void)mode;
-  return hipGetLastError() == hipSuccess ? 0 : LFM_ERR_LAUNCH;
+  hipLaunchKernelGGL(dit_attention_stream_kernel<MODE>, dim3(G), dim3(512), LDS, st, Q, K, Vt, O, heads * HD, heads, (int)items, G / heads, G % heads, (unsigned)bytes, sl2);
+  LFM_CHECK_LAUNCH();
+  return LFM_OK;
 }

@@ -135,13 +135,39 @@ static inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
 // two threads racing through the first call both run the (idempotent) set-up, nobody skips it, nobody reads a half-written flag.  (Rounds 1-5: plain
 // `static bool set` / `static unsigned long long` -- per process, unsynchronised: round-5 review, weak item 1.)
 typedef std::atomic<unsigned long long> lfm_device_mask;
-static inline unsigned long long lfm_device_bit() {
+static inline int lfm_device_index() {  // the current device's slot in the per-device masks and caches
   int d = 0;
   (void)hipGetDevice(&d);
-  return 1ull << (d & 63);
+  return d & 63;
 }
+static inline unsigned long long lfm_device_bit() { return 1ull << lfm_device_index(); }
 static inline bool lfm_device_todo(const lfm_device_mask& m, unsigned long long bit) { return !(m.load(std::memory_order_acquire) & bit); }
 static inline void lfm_device_done(lfm_device_mask& m, unsigned long long bit) { m.fetch_or(bit, std::memory_order_release); }
+// The set-up nearly every launcher needs: allow `Kernel` `bytes` of dynamic LDS on the current device, once per (kernel, device) -- the kernel is a template
+// argument, so every kernel has a mask of its own.  False = the runtime refused (the device is not marked: the next call asks again); callers return LFM_ERR_LAUNCH.
+template <auto Kernel>
+static inline bool lfm_kernel_lds(int bytes) {
+  static lfm_device_mask set{0};
+  const unsigned long long bit = lfm_device_bit();
+  if (lfm_device_todo(set, bit)) {
+    if (hipFuncSetAttribute((const void*)Kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes) != hipSuccess) return false;
+    lfm_device_done(set, bit);
+  }
+  return true;
+}
+// compute units of the current device (the grids of the persistent kernels), asked once per device
+static inline int lfm_cu_count() {
+  static std::atomic<int> cus[64];
+  int dev = 0;
+  (void)hipGetDevice(&dev);
+  std::atomic<int>& c = cus[dev & 63];
+  int n = c.load(std::memory_order_relaxed);
+  if (n <= 0) {
+    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
+    c.store(n, std::memory_order_relaxed);
+  }
+  return n;
+}
 
 // Zero a small device buffer with a KERNEL instead of hipMemsetAsync: inside a captured hipGraph a memset becomes a memset node, and
 // graphs of the host-sequenced UNets (GroupNorm statistics are zeroed before every accumulation) produced NaN on the first replay

@@ -196,11 +196,11 @@ static int check_shape(const lfm_dit_shape* s) {
   if (!s) return LFM_ERR_ARG;
   if (s->depth <= 0 || s->hidden <= 0 || s->heads <= 0 || s->patch <= 0 || s->in_ch <= 0 || s->res <= 0) return LFM_ERR_SHAPE;
   if (s->hidden % s->heads) return LFM_ERR_SHAPE;
-  const int hd = s->hidden / s->heads;
-  if (hd != 64 && hd != 72) return LFM_ERR_SHAPE;  // S / B / L: 64; XL: 1152 / 16 = 72
   if (s->res % s->patch) return LFM_ERR_SHAPE;
   const int T = (s->res / s->patch) * (s->res / s->patch);
-  if (T != 16 && T != 64 && T != 128 && T != 256 && T != 1024) return LFM_ERR_SHAPE;  // attention kernels: LDS-resident K / V^T up to 256 tokens; 1024 = four key chunks
+  // an attention kernel for (head_dim, tokens) -- S / B / L: 64; XL: 1152 / 16 = 72; LDS-resident K / V^T up to 256 tokens, 1024 = four key chunks (the answer
+  // for ONE image: whether a shape is served does not depend on the batch)
+  if (attention_choose(1, s->heads, s->hidden / s->heads, T) < 0) return LFM_ERR_SHAPE;
   if (s->hidden % 64 || s->hidden > 256 * LN_MAXV || s->mlp_hidden % 64) return LFM_ERR_SHAPE;
   const int kk = s->patch * s->patch * s->in_ch;
   if (kk > FIN_MAXO || (kk > PE_MAXK && (kk % 64))) return LFM_ERR_SHAPE;  // small patches: register kernel; large: GEMM (K % 64 == 0)
@@ -232,6 +232,11 @@ extern "C" int lfm_dit_attention_hd(const void* Q, const void* K, const void* Vt
   if (batch <= 0 || heads <= 0) return LFM_ERR_SHAPE;
   if (((uintptr_t)Q | (uintptr_t)K | (uintptr_t)Vt | (uintptr_t)O) & 15) return LFM_ERR_ALIGN;
   return attention_launch((const half_t*)Q, (const half_t*)K, (const half_t*)Vt, (half_t*)O, batch, heads, head_dim, T, (hipStream_t)stream);
+}
+// Which kernel lfm_dit_attention_hd runs for a shape under the calling thread's flags and the library options (attention_kernel.h: attention_choose; host only).
+extern "C" int lfm_attention_plan(int batch, int heads, int head_dim, int T) {
+  if (batch <= 0 || heads <= 0) return LFM_ERR_SHAPE;
+  return attention_choose(batch, heads, head_dim, T);
 }
 extern "C" int lfm_dit_attention(const void* Q, const void* K, const void* Vt, void* O, int batch, int heads, int T, lfm_stream_t stream) {
   return lfm_dit_attention_hd(Q, K, Vt, O, batch, heads, 64, T, stream);

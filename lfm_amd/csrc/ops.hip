@@ -9,14 +9,13 @@ static __device__ half_t g_zero_page[64];  // zero padding rows for the conv gat
 
 static const half_t* zero_page() {  // the symbol's address is per DEVICE (one slot per device, written once; racing threads write the same value)
   static std::atomic<const half_t*> p[64];
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  const half_t* v = p[dev & 63].load(std::memory_order_acquire);
+  const int dev = lfm_device_index();
+  const half_t* v = p[dev].load(std::memory_order_acquire);
   if (!v) {
     void* d = nullptr;
     if (hipGetSymbolAddress(&d, HIP_SYMBOL(g_zero_page)) != hipSuccess) return nullptr;
     v = (const half_t*)d;
-    p[dev & 63].store(v, std::memory_order_release);
+    p[dev].store(v, std::memory_order_release);
   }
   return v;
 }
@@ -225,12 +224,7 @@ static int launch_conv_in_mfma(const float* x, const float* w, const float* b, h
   const int KS = cdiv(Cin * 9, 16), LD = KS * 16 + 8;
   const size_t lds = ((size_t)2 * Cout + 2 * CIM_PIX) * LD * 2;
   if (lds > 160 * 1024) return 1;
-  static lfm_device_mask attr_set{0};
-  const unsigned long long dbit = lfm_device_bit();
-  if (lfm_device_todo(attr_set, dbit)) {
-    if (hipFuncSetAttribute((const void*)conv_in_mfma_kernel<NT>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) return LFM_ERR_LAUNCH;
-    lfm_device_done(attr_set, dbit);
-  }
+  if (!lfm_kernel_lds<&conv_in_mfma_kernel<NT>>(160 * 1024)) return LFM_ERR_LAUNCH;
   const long chunks = cdiv((long)N * H * W, CIM_PIX);
   const int grid = (int)(chunks < 1024 ? chunks : 1024);  // a workgroup pays the weight split once and then walks its chunks
   hipLaunchKernelGGL(conv_in_mfma_kernel<NT>, dim3(grid), dim3(256), lds, st, x, w, b, out, N, H, W, Cin, Cout, KS);
@@ -253,12 +247,7 @@ extern "C" int lfm_conv3x3_in_f32(const float* x_nchw, const float* w, const flo
   }
   const size_t lds = (size_t)Cin * 9 * Cout * 4;
   if (lds > 160 * 1024) return LFM_ERR_SHAPE;
-  static lfm_device_mask set{0};
-  const unsigned long long dbit = lfm_device_bit();
-  if (lfm_device_todo(set, dbit)) {
-    if (hipFuncSetAttribute((const void*)conv_in_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) return LFM_ERR_LAUNCH;
-    lfm_device_done(set, dbit);
-  }
+  if (!lfm_kernel_lds<&conv_in_kernel>(160 * 1024)) return LFM_ERR_LAUNCH;
   hipLaunchKernelGGL(conv_in_kernel, dim3(cdiv((long)N * H * W, CI_PIX)), dim3(256), lds, (hipStream_t)stream, x_nchw, w, bias,
                      (half_t*)out_nhwc, N, H, W, Cin, Cout);
   LFM_CHECK_LAUNCH();
@@ -827,13 +816,7 @@ __global__ __launch_bounds__(256) void attention_unet_mfma_kernel(const half_t* 
 template <int CH, int T>
 static int launch_attention_unet_mfma(const half_t* qkv, half_t* out, int N, int heads, hipStream_t st) {
   constexpr int LDS = T * (CH * 2 + 16) + CH * (T * 2 + 16);
-  static lfm_device_mask attr_set{0};
-  const unsigned long long dbit = lfm_device_bit();
-  if (lfm_device_todo(attr_set, dbit)) {
-    if (hipFuncSetAttribute((const void*)attention_unet_mfma_kernel<CH, T>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS) != hipSuccess)
-      return LFM_ERR_LAUNCH;
-    lfm_device_done(attr_set, dbit);
-  }
+  if (!lfm_kernel_lds<&attention_unet_mfma_kernel<CH, T>>(LDS)) return LFM_ERR_LAUNCH;
   hipLaunchKernelGGL((attention_unet_mfma_kernel<CH, T>), dim3(heads, N, T / 64), dim3(256), LDS, st, qkv, out, heads, 1.0f / sqrtf((float)CH));
   LFM_CHECK_LAUNCH();
   return LFM_OK;
@@ -854,13 +837,7 @@ extern "C" int lfm_attention_small_f16(const void* qkv, void* out, int N, int T,
   const int QB = T < 64 ? T : 64;  // queries per workgroup
   const size_t lds = (size_t)QB * (T + 1) * 4 + (size_t)2 * T * (ch + 2) * 2;
   if (lds > 160 * 1024) return LFM_ERR_SHAPE;  // every reference config has T <= 64 (8x8 / 4x4 feature maps)
-  static lfm_device_mask set{0};
-  const unsigned long long dbit = lfm_device_bit();
-  if (lfm_device_todo(set, dbit)) {
-    if (hipFuncSetAttribute((const void*)attention_small_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
-      return LFM_ERR_LAUNCH;
-    lfm_device_done(set, dbit);
-  }
+  if (!lfm_kernel_lds<&attention_small_kernel>(160 * 1024)) return LFM_ERR_LAUNCH;
   hipLaunchKernelGGL(attention_small_kernel, dim3(heads, N, cdiv(T, QB)), dim3(256), lds, (hipStream_t)stream, (const half_t*)qkv, (half_t*)out,
                      T, heads, ch, QB);
   LFM_CHECK_LAUNCH();

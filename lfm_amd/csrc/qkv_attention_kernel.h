@@ -30,7 +30,7 @@
 // order, inside the key loop {column-constant and (waves 0-3) row-statistic loads interleaved with A0(0) A0(0) B0(0) B0(0) B1(0)} A1(0) A1(0), then 4 output stores,
 // A0(1) A0(1) B0(1) B0(1): the K loop may start once B1(0) has landed = all but the newest 10 (the first item of a workgroup: 6, there are no stores in between).
 #pragma once
-#include "attention_kernel.h"
+#include "attention_common.h"
 #include "gemm256h_kernel.h"
 
 struct QkvAttnArgs {
@@ -574,19 +574,8 @@ static inline int launch_qkv_attention(const half_t* A, long lda, const half_t* 
       (ep.uv_stride % 4) != 0)
     return LFM_ERR_ALIGN;
   if (ep.st.tiles_p > G256H_MAX_PARTS) return LFM_ERR_SHAPE;
-  int devid = 0;
-  (void)hipGetDevice(&devid);
-  static lfm_device_mask attr_set{0};
-  static std::atomic<int> cus[64];
-  const unsigned long long dbit = 1ull << (devid & 63);
-  if (lfm_device_todo(attr_set, dbit)) {
-    if (hipFuncSetAttribute((const void*)qkv_attention_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, QKVA_LDS_BYTES) != hipSuccess) return LFM_ERR_LAUNCH;
-    int n = 0;
-    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, devid) != hipSuccess || n <= 0) n = 256;
-    cus[devid & 63].store(n, std::memory_order_relaxed);
-    lfm_device_done(attr_set, dbit);
-  }
-  const int items = (M / G256_BM) * heads, ncu = cus[devid & 63].load(std::memory_order_relaxed);
+  if (!lfm_kernel_lds<&qkv_attention_kernel>(QKVA_LDS_BYTES)) return LFM_ERR_LAUNCH;
+  const int items = (M / G256_BM) * heads, ncu = lfm_cu_count();
   const int dbg = lfm_gemm_debug_flags();
   const int grid = (items <= ncu || (dbg & LFM_DBG_QKV_PER_ITEM)) ? items : ncu;  // one persistent workgroup per CU (flag: one workgroup per item, A/B)
   hipLaunchKernelGGL(qkv_attention_kernel, dim3(grid), dim3(512), QKVA_LDS_BYTES, stream, A, lda, W, ldw, M, K, ep, items, dbg);

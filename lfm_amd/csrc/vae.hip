@@ -519,12 +519,7 @@ extern "C" int lfm_vae_mid_attention_f16(const void* x, void* out, const float* 
 
 // post_quant_conv + conv_in: z [n,4,R,R] fp32 NCHW -> out fp16 NHWC [n,R,R,512]
 static int vae_conv_in(const lfm_vae_weights* w, const float* z, half_t* out, int n, int R, hipStream_t st) {
-  static lfm_device_mask set{0};
-  const unsigned long long dbit = lfm_device_bit();
-  if (lfm_device_todo(set, dbit)) {
-    if (hipFuncSetAttribute((const void*)vae_conv_in_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 36 * 512 * 4) != hipSuccess) return LFM_ERR_LAUNCH;
-    lfm_device_done(set, dbit);
-  }
+  if (!lfm_kernel_lds<&vae_conv_in_kernel>(36 * 512 * 4)) return LFM_ERR_LAUNCH;
   // batch 1 (--measure_time: run_sampling(1, ..), reference test_flow_latent.py:223-246): 1024 pixels are FOUR blocks of 256 pixels -- 183 us for 38 MFLOP
   // (profiles/r06_latency_mode.txt); 16 pixels per block put them on 64 CUs
   const long pixels = (long)n * R * R;

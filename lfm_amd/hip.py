@@ -113,6 +113,8 @@ def lib():
     L.lfm_dit_plan.argtypes = [C.POINTER(DitShape), C.POINTER(DitCall), C.POINTER(C.c_int)]
     L.lfm_gemm_plan.restype = C.c_int
     L.lfm_gemm_plan.argtypes = [C.c_int] * 5
+    L.lfm_attention_plan.restype = C.c_int
+    L.lfm_attention_plan.argtypes = [C.c_int] * 4
     L.lfm_dit_attention_hd.restype = C.c_int
     L.lfm_dit_attention_hd.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]
     L.lfm_grid_advance.restype = C.c_int
@@ -347,6 +349,12 @@ GEMM_CAP_V6, GEMM_CAP_FITS = 1, 2  # lfm_gemm_plan caps: row-major A and an epil
 def gemm_plan(M, N, K, batch=1, caps=GEMM_CAP_V6 | GEMM_CAP_FITS):
     """The GEMM kernel (1 / 4 / 5 / 6) the library runs for this shape under the calling thread's current selection (no launch, no GPU needed)."""
     return lib().lfm_gemm_plan(int(M), int(N), int(K), int(batch), int(caps))
+
+
+def attention_plan(batch, heads, head_dim, T):
+    """The kernel id (1 .. 6, include/lfm_hip.h: lfm_attention_plan) dit_attention runs for this shape under the calling thread's flags and the library
+    options, or LFM_ERR_SHAPE (-1) for a shape no kernel serves (no launch, no GPU needed)."""
+    return lib().lfm_attention_plan(int(batch), int(heads), int(head_dim), int(T))
 
 
 def set_option(key, value):

@@ -455,6 +455,55 @@ def test_gemm_plan_is_the_kernel_that_runs():
         hip.set_option(hip.OPT_GEMM_V6, 0)
 
 
+# (batch, heads, head_dim, tokens) -> lfm_attention_plan under (the defaults, flag ATT_WIDE, LFM_OPT_ATTENTION_STREAM off).  1 = the 16-token kernel, 2 = one workgroup
+# per item, 3 = its wide form, 4 = four key chunks, 5 = the query split, 6 = the streamed kernel, -1 = LFM_ERR_SHAPE.  Written from the rules, not from the C++:
+# only 256 tokens x head_dim 64 has more than one kernel -- wide if asked for, else the query split up to 64 items, else streamed while a tensor
+# (items x 256 x 64 fp16 = items x 32 KiB) stays below 2 GiB = up to 65535 items, else per item.
+_ATTENTION_PLAN = [
+    ((4, 16, 64, 16), (1, 1, 1)), ((4, 16, 72, 16), (1, 1, 1)),
+    ((4, 16, 64, 64), (2, 2, 2)), ((4, 16, 72, 64), (2, 2, 2)),
+    ((4, 16, 64, 128), (2, 2, 2)), ((4, 16, 72, 128), (2, 2, 2)),
+    ((4, 16, 64, 256), (5, 3, 5)),                                  # 64 items: the query split (wide: for 64 items too)
+    ((4, 16, 72, 256), (2, 2, 2)),                                  # ATT_WIDE is a head_dim 64 kernel
+    ((4, 16, 64, 1024), (4, 4, 4)), ((4, 16, 72, 1024), (4, 4, 4)),
+    ((1, 1, 64, 1024), (4, 4, 4)), ((4096, 16, 64, 1024), (4, 4, 4)),  # four key chunks whatever the item count
+    ((1, 1, 64, 256), (5, 3, 5)), ((1, 2, 64, 256), (5, 3, 5)),
+    ((5, 13, 64, 256), (6, 3, 2)),                                  # 65 items
+    ((65, 1, 64, 256), (6, 3, 2)),
+    ((64, 16, 64, 256), (6, 3, 2)),                                 # the benchmarked shape
+    ((4369, 15, 64, 256), (6, 3, 2)),                               # 65535 items: 2 GiB - 32 KiB per tensor
+    ((4096, 16, 64, 256), (2, 3, 2)),                               # 65536 items: 2 GiB
+    ((4096, 16, 72, 256), (2, 2, 2)),
+    ((4, 16, 80, 256), (-1, -1, -1)), ((4, 16, 80, 16), (-1, -1, -1)), ((4, 16, 128, 64), (-1, -1, -1)),
+    ((4, 16, 64, 4096), (-1, -1, -1)), ((4, 16, 72, 4096), (-1, -1, -1)), ((4, 16, 64, 32), (-1, -1, -1)), ((4, 16, 64, 512), (-1, -1, -1)),
+]
+
+
+def test_attention_plan_is_the_kernel_that_runs():
+    """lfm_attention_plan (no launch) = the one chooser lfm_dit_attention_hd and the block loop go through (csrc/attention_kernel.h: attention_choose): the kernel per
+    shape under the defaults, under flag ATT_WIDE and with the streamed kernel switched off; shapes no kernel serves are refused."""
+    from lfm_amd import hip
+
+    def plans():
+        return [hip.attention_plan(*shape) for shape, _ in _ATTENTION_PLAN]
+
+    want = lambda i: [w[i] for _, w in _ATTENTION_PLAN]
+    shapes = [s for s, _ in _ATTENTION_PLAN]
+    try:
+        assert list(zip(shapes, plans())) == list(zip(shapes, want(0)))
+        hip.gemm_select(hip.DBG_ATT_WIDE << 4)
+        assert list(zip(shapes, plans())) == list(zip(shapes, want(1)))
+        hip.gemm_select(0)
+        hip.set_option(hip.OPT_ATTENTION_STREAM, 0)
+        assert list(zip(shapes, plans())) == list(zip(shapes, want(2)))
+        hip.gemm_select(hip.DBG_ATT_WIDE << 4)  # both: the flag decides first
+        assert hip.attention_plan(64, 16, 64, 256) == 3
+    finally:
+        hip.gemm_select(0)
+        hip.set_option(hip.OPT_ATTENTION_STREAM, 1)
+    assert hip.attention_plan(0, 16, 64, 256) == -1 and hip.attention_plan(4, 0, 64, 256) == -1  # as lfm_dit_attention_hd refuses them
+
+
 # pairs of flags of DIFFERENT consumers on the same bits (csrc/debug_flags.h says "shares" next to both): today's overlaps, acknowledged one by one.
 # A new pair fails test_debug_flags_have_one_definition until it is added here on purpose.
 _SHARED_FLAG_BITS = {
