@@ -197,6 +197,10 @@ int lfm_profile_blocks_read(float* host_ms_out, int max_n);
  * core of a DiTBlock (models/DiT.py:120) run as ONE kernel -- a workgroup per (image, head) computes the head's 256 x 192 slice of the projection and attends on
  * it out of the LDS; Q, K, V never reach HBM (csrc/qkv_attention_kernel.h); 0 = two kernels.  Same arithmetic in the same order: bit-identical results. */
 #define LFM_OPT_FUSED_QKV_ATTENTION 6
+/* key 7 (LFM_OPT_UNET_ATTENTION_STREAM), value 0 / 1 / 2, default 1: lfm_attention_small_f16 runs the shapes that neither its resident MFMA kernel nor
+ * its VALU kernel serves (ch % 16 == 0, ch <= 256, any token count) on the streamed kernel (csrc/unet_attention_stream_kernel.h).  0 = those shapes are
+ * refused (LFM_ERR_SHAPE); 2 = EVERY shape with ch % 16 == 0, ch <= 256 takes the streamed kernel (parity tests and A/B only). */
+#define LFM_OPT_UNET_ATTENTION_STREAM 7
 int lfm_set_option(int key, int value);
 /* The settings lfm_dit_forward would run `call` with if it were enqueued by the calling thread now (per-call fields over the library defaults):
  * *gemm_select_out = kernel | flags << 4, *fold_ln_out = 0 / 1.  No launch; usable without a GPU. */
@@ -369,10 +373,19 @@ int lfm_concat_channels_f16(const void* a, const void* b, void* out, long pixels
 /* y = x + e[n][c] broadcast over the pixels of image n (ResBlock without scale-shift norm: h + emb_out[..., None, None], unet.py:233-235);
  * x, y fp16 NHWC [N*HW, C], e fp32 rows e_stride apart */
 int lfm_add_image_vec_f16(const void* x, const float* e, long e_stride, void* y, int N, int HW, int C, lfm_stream_t stream);
-/* QKVAttentionLegacy (unet.py:310-334): qkv fp16 [N*T, 3C], columns [head][q|k|v][ch]; out fp16 [N*T, C] columns [head][ch].
- * T = 64 / 256 with ch = 64 / 128 (16-byte aligned pointers): MFMA kernel; any other shape: a VALU kernel that keeps K, V and a 64-query score
- * block in the LDS (LFM_ERR_SHAPE when that exceeds 160 KiB). */
+/* QKVAttentionLegacy (unet.py:310-334) and the attention of EDM's UNetBlock: qkv fp16 [N*T, 3C], columns [head][q|k|v][ch]; out fp16 [N*T, C], columns
+ * [head][ch]; softmax(q k^T / sqrt(ch)) v with fp32 scores and softmax.  Three kernels (lfm_unet_attention_plan tells which):
+ *   2 = the resident MFMA kernel: T = 64 / 256 with ch = 64 / 128, all of K and V^T of a head in the LDS;
+ *   1 = the VALU kernel: any ch, K, V and a 64-query score block in the LDS -- min(T, 64) (T + 1) 4 + 4 T (ch + 2) bytes <= 160 KiB
+ *       (T <= 314 at ch = 64, T <= 127 at ch = 256);
+ *   3 = the streamed MFMA kernel (LFM_OPT_UNET_ATTENTION_STREAM): every other shape with ch % 16 == 0 and ch <= 256, ANY T -- keys in blocks of 64
+ *       through a double-buffered LDS stage, online softmax.
+ * The MFMA kernels need 16-byte aligned pointers; otherwise the VALU kernel runs where it fits.  LFM_ERR_SHAPE when no kernel serves the shape
+ * (ch % 16 != 0 or ch > 256 beyond the VALU kernel's LDS bound).  No workspace, no synchronisation, graph-capturable. */
 int lfm_attention_small_f16(const void* qkv, void* out, int N, int T, int heads, int ch, lfm_stream_t stream);
+/* Which kernel lfm_attention_small_f16 runs for this shape with 16-byte aligned operands under the calling thread's flags (LFM_DBG_UNET_ATT_VALU decides
+ * first: 1 or LFM_ERR_SHAPE) and the library options: 1 / 2 / 3 as above, or LFM_ERR_SHAPE.  No launch; usable without a GPU. */
+int lfm_unet_attention_plan(int N, int T, int heads, int ch);
 /* emb = time_embed(timestep_embedding(t, F)) (+ label_emb[y]) (nn.py:103-121, unet.py:633-641): fp32 [N,E] and fp16 silu(emb).
  * label_table has label_rows rows; a label outside [0, label_rows) (an IndexError in the reference) poisons its row with NaN. */
 int lfm_time_embed(const float* t, int t_len, const float* w0, const float* b0, const float* w2, const float* b2, const float* label_table,

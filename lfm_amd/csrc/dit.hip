@@ -24,6 +24,7 @@ static struct {
   Opt stagger{0};     // measurement builds, lfm_set_option key 3
   Opt att_stream{1};  // LFM_OPT_ATTENTION_STREAM: 256 tokens x head_dim 64 with more than 64 (image, head) items on the persistent streamed kernel
   Opt fused_qkv{1};   // LFM_OPT_FUSED_QKV_ATTENTION: folded path at 256 tokens x head_dim 64: QKV projection + attention in one kernel (qkv_attention_kernel.h)
+  Opt unet_att_stream{1};  // LFM_OPT_UNET_ATTENTION_STREAM: UNet attention shapes neither the resident nor the VALU kernel serves on the streamed kernel (ops.hip: unet_attention_choose)
 } g_def;
 static thread_local int tl_sel_set = 0, tl_gemm_sel = 0, tl_gemm_dbg = 0;  // per-call kernel selection active on this thread
 static thread_local int tl_fold = 0;                                       // 0: default, LFM_CALL_OFF, LFM_CALL_ON
@@ -44,6 +45,7 @@ int lfm_gemm_prefers_v4(int M, int N, int K) {  // no shape today: only the A/B 
 int lfm_gemm_v6_default() { return opt_get(g_def.v6); }
 int lfm_stagger_ticks() { return opt_get(g_def.stagger); }
 int lfm_attention_stream_enabled() { return opt_get(g_def.att_stream); }
+int lfm_unet_attention_stream_mode() { return opt_get(g_def.unet_att_stream); }
 // Which kernel launch_gemm_auto runs for a shape under the calling thread's selection (host only, no GPU needed): caps bit 0 = the instantiation can take
 // kernel 6 (row-major A, no per-lane tile accumulators in the epilogue), bit 1 = the operands fit 32-bit buffer offsets.
 extern "C" int lfm_gemm_plan(int M, int N, int K, int batch, int caps) { return gemm_choose(M, N, K, batch, caps); }
@@ -95,6 +97,7 @@ extern "C" int lfm_set_option(int key, int value) {
     case 4: opt_set(g_def.skinny, value < 0 || value > 2 ? 1 : value); break;  // LFM_OPT_SKINNY_GEMM: 0 = the split-K 128x128 path of rounds 2-4 for M <= 256 (A/B, parity)
     case 5: opt_set(g_def.att_stream, value != 0); break;  // LFM_OPT_ATTENTION_STREAM: 0 = one workgroup per (image, head) item (the rounds 1-5 kernel; A/B and the bit-equality test)
     case 6: opt_set(g_def.fused_qkv, value != 0); break;   // LFM_OPT_FUSED_QKV_ATTENTION: 0 = the QKV GEMM and the attention kernel as two launches (A/B and the bit-equality test)
+    case 7: opt_set(g_def.unet_att_stream, value < 0 || value > 2 ? 1 : value); break;  // LFM_OPT_UNET_ATTENTION_STREAM: 0 = those shapes refused (as before the kernel), 2 = every shape it takes (parity, A/B)
     default: return LFM_ERR_ARG;
   }
   return LFM_OK;

@@ -677,8 +677,9 @@ extern "C" int lfm_concat_channels_f16(const void* a, const void* b, void* out, 
 // ------------------------------------------------------------------ small-T attention (QKVAttentionLegacy, unet.py:310-334)
 // qkv: fp16 [N*T, 3*C], column layout [head][q | k | v][ch] (what reshape(bs*heads, 3*ch, T).split(ch) means for a
 // token-major tensor); out: fp16 [N*T, C] with columns [head][ch].  softmax((q*s)(k*s)^T) v with s = ch^-1/4, fp32 softmax.
-// One workgroup per (head, image); T <= 256, ch <= 256.  FLOPs are negligible (T <= 64 in every reference config), so this
-// is a plain VALU kernel: K and V rows in LDS as fp32, one query per thread-group.
+// Three kernels, chosen by unet_attention_choose below: this VALU kernel (any ch; all of K and V of a head as fp16 rows plus a 64-query fp32 score block in
+// the LDS, which bounds T: 314 tokens at ch = 64, 127 at ch = 256), the resident MFMA kernel (T = 64 / 256 x ch = 64 / 128) and the streamed MFMA kernel
+// (unet_attention_stream_kernel.h: ch % 16 == 0, ch <= 256, any T).  One workgroup per (head, image, 64 queries), one query per thread-group.
 __global__ __launch_bounds__(256) void attention_small_kernel(const half_t* __restrict__ qkv, half_t* __restrict__ out, int T, int heads, int ch,
                                                               int QB) {
   extern __shared__ __attribute__((aligned(16))) char smraw[];  // S fp32 [QB][T+1], then K, V fp16 [T][ch+2]
@@ -822,26 +823,57 @@ static int launch_attention_unet_mfma(const half_t* qkv, half_t* out, int N, int
   return LFM_OK;
 }
 
+#include "unet_attention_stream_kernel.h"
+
+// ---- dispatch.  unet_attention_choose is the ONE place that knows which kernel serves a shape with 16-byte-aligned operands (lfm_unet_attention_plan returns its
+// answer without a launch: the CPU truth table of tests/test_unet_attention_ref.py).  Nothing a kernel served before the streamed one existed moves to it:
+// flag UNET_ATT_VALU decides first, then the four resident shapes, then whatever the VALU kernel's LDS admits, and only the rest is streamed.
+enum { UNET_ATT_VALU = 1, UNET_ATT_RESIDENT = 2, UNET_ATT_STREAM = 3 };
+static inline size_t unet_attention_valu_lds(int T, int ch) {  // S fp32 [min(T, 64)][T + 1], then K, V fp16 [T][ch + 2]
+  return (size_t)(T < 64 ? T : 64) * ((size_t)T + 1) * 4 + (size_t)4 * T * ((size_t)ch + 2);
+}
+static inline int unet_attention_choose(int T, int heads, int ch) {
+  if (T <= 0 || heads <= 0 || ch <= 0) return LFM_ERR_SHAPE;
+  const bool valu_fits = unet_attention_valu_lds(T, ch) <= 160 * 1024;
+  const bool stream_fits = ch % 16 == 0 && ch <= 256;
+  const int stream = lfm_unet_attention_stream_mode();
+  if (lfm_gemm_debug_flags() & LFM_DBG_UNET_ATT_VALU) return valu_fits ? UNET_ATT_VALU : LFM_ERR_SHAPE;  // flag: the VALU kernel or nothing (A/B)
+  if (stream == 2 && stream_fits) return UNET_ATT_STREAM;  // parity tests and A/B: every shape the streamed kernel takes
+  if ((T == 64 || T == 256) && (ch == 64 || ch == 128)) return UNET_ATT_RESIDENT;
+  if (valu_fits) return UNET_ATT_VALU;
+  if (stream && stream_fits) return UNET_ATT_STREAM;
+  return LFM_ERR_SHAPE;
+}
+extern "C" int lfm_unet_attention_plan(int N, int T, int heads, int ch) {
+  if (N <= 0) return LFM_ERR_SHAPE;
+  return unet_attention_choose(T, heads, ch);
+}
+
 extern "C" int lfm_attention_small_f16(const void* qkv, void* out, int N, int T, int heads, int ch, lfm_stream_t stream) {
   if (!qkv || !out) return LFM_ERR_ARG;
   if (N <= 0 || T <= 0 || heads <= 0 || ch <= 0) return LFM_ERR_SHAPE;
-  if (!(((uintptr_t)qkv | (uintptr_t)out) & 15) && !(lfm_gemm_debug_flags() & LFM_DBG_UNET_ATT_VALU)) {  // flag: the VALU kernel (A/B)
-    const half_t* qi = (const half_t*)qkv;
-    half_t* oi = (half_t*)out;
-    hipStream_t st = (hipStream_t)stream;
-    if (T == 256 && ch == 128) return launch_attention_unet_mfma<128, 256>(qi, oi, N, heads, st);
-    if (T == 256 && ch == 64) return launch_attention_unet_mfma<64, 256>(qi, oi, N, heads, st);
-    if (T == 64 && ch == 128) return launch_attention_unet_mfma<128, 64>(qi, oi, N, heads, st);
-    if (T == 64 && ch == 64) return launch_attention_unet_mfma<64, 64>(qi, oi, N, heads, st);
+  const half_t* qi = (const half_t*)qkv;
+  half_t* oi = (half_t*)out;
+  hipStream_t st = (hipStream_t)stream;
+  int kern = unet_attention_choose(T, heads, ch);
+  if ((((uintptr_t)qkv | (uintptr_t)out) & 15) && kern != UNET_ATT_VALU)  // the MFMA kernels read and write 16-byte chunks: the VALU kernel where it fits
+    kern = unet_attention_valu_lds(T, ch) <= 160 * 1024 ? UNET_ATT_VALU : LFM_ERR_SHAPE;
+  switch (kern) {
+    case UNET_ATT_RESIDENT:
+      if (T == 256 && ch == 128) return launch_attention_unet_mfma<128, 256>(qi, oi, N, heads, st);
+      if (T == 256 && ch == 64) return launch_attention_unet_mfma<64, 256>(qi, oi, N, heads, st);
+      if (T == 64 && ch == 128) return launch_attention_unet_mfma<128, 64>(qi, oi, N, heads, st);
+      return launch_attention_unet_mfma<64, 64>(qi, oi, N, heads, st);
+    case UNET_ATT_STREAM: return attention_unet_stream_launch(qi, oi, N, T, heads, ch, st);
+    case UNET_ATT_VALU: {
+      const int QB = T < 64 ? T : 64;  // queries per workgroup
+      if (!lfm_kernel_lds<&attention_small_kernel>(160 * 1024)) return LFM_ERR_LAUNCH;
+      hipLaunchKernelGGL(attention_small_kernel, dim3(heads, N, cdiv(T, QB)), dim3(256), unet_attention_valu_lds(T, ch), st, qi, oi, T, heads, ch, QB);
+      LFM_CHECK_LAUNCH();
+      return LFM_OK;
+    }
+    default: return LFM_ERR_SHAPE;
   }
-  const int QB = T < 64 ? T : 64;  // queries per workgroup
-  const size_t lds = (size_t)QB * (T + 1) * 4 + (size_t)2 * T * (ch + 2) * 2;
-  if (lds > 160 * 1024) return LFM_ERR_SHAPE;  // every reference config has T <= 64 (8x8 / 4x4 feature maps)
-  if (!lfm_kernel_lds<&attention_small_kernel>(160 * 1024)) return LFM_ERR_LAUNCH;
-  hipLaunchKernelGGL(attention_small_kernel, dim3(heads, N, cdiv(T, QB)), dim3(256), lds, (hipStream_t)stream, (const half_t*)qkv, (half_t*)out,
-                     T, heads, ch, QB);
-  LFM_CHECK_LAUNCH();
-  return LFM_OK;
 }
 
 // ------------------------------------------------------------------ timestep embedding MLP (nn.py:103-121 + unet.py:633-641)

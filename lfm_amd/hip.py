@@ -165,6 +165,8 @@ def lib():
     L.lfm_add_image_vec_f16.argtypes = [V, V, LG, V, I, I, I, V]
     L.lfm_attention_small_f16.restype = I
     L.lfm_attention_small_f16.argtypes = [V, V, I, I, I, I, V]
+    L.lfm_unet_attention_plan.restype = I
+    L.lfm_unet_attention_plan.argtypes = [I, I, I, I]
     L.lfm_time_embed.restype = I
     L.lfm_time_embed.argtypes = [V, I, V, V, V, V, V, V, I, V, V, V, I, I, I, V]
     L.lfm_vae_groupnorm_f16.restype = I
@@ -308,6 +310,7 @@ OPT_FOLD_LN = 1  # adaLN LayerNorm-modulate folded into the GEMM epilogues, defa
 OPT_SKINNY_GEMM = 4  # batch-1 DiT linears on the latency-mode kernels (1, default: csrc/gemm_sq64_kernel.h where rows % 64 == 0, else csrc/gemm_skinny_kernel.h; 2: always the latter; 0: split-K path)
 OPT_ATTENTION_STREAM = 5  # 256-token hd-64 attention on persistent workgroups with an LDS ring of K / V^T stages (csrc/attention_stream_kernel.h), default on; 0: one workgroup per item
 OPT_FUSED_QKV_ATTENTION = 6  # folded path, 256 tokens x hd 64: QKV projection + attention in one kernel (csrc/qkv_attention_kernel.h), default on; 0: two kernels
+OPT_UNET_ATTENTION_STREAM = 7  # UNet attention shapes beyond the resident and the VALU kernel on the streamed kernel (csrc/unet_attention_stream_kernel.h), default 1; 0: refused; 2: every shape it takes
 OPT_GEMM_V6 = 2  # chip-filling row-major GEMMs on the one-wave-per-SIMD 256x256 kernel (csrc/gemm256w_kernel.h) instead of the 8-wave one
 
 
@@ -355,6 +358,21 @@ def attention_plan(batch, heads, head_dim, T):
     """The kernel id (1 .. 6, include/lfm_hip.h: lfm_attention_plan) dit_attention runs for this shape under the calling thread's flags and the library
     options, or LFM_ERR_SHAPE (-1) for a shape no kernel serves (no launch, no GPU needed)."""
     return lib().lfm_attention_plan(int(batch), int(heads), int(head_dim), int(T))
+
+
+def unet_attention_plan(N, T, heads, ch):
+    """The kernel (1 VALU, 2 resident MFMA, 3 streamed MFMA; include/lfm_hip.h: lfm_unet_attention_plan) lfm_attention_small_f16 runs for this shape with
+    16-byte-aligned operands under the calling thread's flags and the library options, or LFM_ERR_SHAPE (-1) (no launch, no GPU needed)."""
+    return lib().lfm_unet_attention_plan(int(N), int(T), int(heads), int(ch))
+
+
+def unet_attention(qkv, out, N, T, heads, ch):
+    """lfm_attention_small_f16 on qkv fp16 [N*T, 3*heads*ch] -> out fp16 [N*T, heads*ch]; a shape no kernel serves is named with its limit."""
+    if unet_attention_plan(N, T, heads, ch) < 0:
+        raise LfmHipError(f"UNet attention: no kernel serves T = {T} tokens x {ch} channels per head (limit: channels per head % 16 == 0 and <= 256 for any "
+                          f"token count; other widths only while min(T, 64) * (T + 1) * 4 + 4 * T * (ch + 2) <= {160 * 1024} bytes of LDS)")
+    check(lib().lfm_attention_small_f16(ptr(qkv), ptr(out), N, T, heads, ch, stream_ptr(qkv.device)), "lfm_attention_small_f16")
+    return out
 
 
 def set_option(key, value):

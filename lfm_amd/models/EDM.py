@@ -324,8 +324,7 @@ class DhariwalUNet(nn.Module):
             t = self._gn(x, N, T, Cout, p["gn2"], None, False)
             qkv = self._linear(t, p["qkv"])
             a = torch.empty(N * T, Cout, dtype=torch.float16, device=x.device)
-            hip.check(hip.lib().lfm_attention_small_f16(hip.ptr(qkv), hip.ptr(a), N, T, b.num_heads, ch, hip.stream_ptr(x.device)),
-                      "lfm_attention_small_f16")
+            hip.unet_attention(qkv, a, N, T, b.num_heads, ch)
             x = self._linear(a, p["proj"], resid=x)
         return x, H, W
 

@@ -337,8 +337,7 @@ class UNetModel(nn.Module):
         t = self._gn(h, N, T, Cch, p["gn"], None, False)
         qkv = self._linear(t, p["qkv"])
         a = torch.empty(N * T, Cch, dtype=torch.float16, device=h.device)
-        hip.check(hip.lib().lfm_attention_small_f16(hip.ptr(qkv), hip.ptr(a), N, T, m.num_heads, Cch // m.num_heads,
-                                                    hip.stream_ptr(h.device)), "lfm_attention_small_f16")
+        hip.unet_attention(qkv, a, N, T, m.num_heads, Cch // m.num_heads)
         return self._linear(a, p["proj"], resid=h)
 
     def _run_block(self, prefix, block, h, N, H, W, emb_silu):
