@@ -591,12 +591,12 @@ __global__ __launch_bounds__(256) void final_layer_kernel(const float* __restric
 // and reduces 64 partial dot products through 63 ds_bpermute exchanges: 64 us for 67 MB = 1.0 TB/s.  Here one wave owns SIXTEEN token rows as ONE
 // v_mfma_f32_16x16x32_f16 row tile and N = p*p*C / 16 column tiles; K = D is walked in 32-deep steps with the operands built in registers in the
 // MFMA fragment layout (lane l: row l & 15, eight consecutive k at 8 (l >> 4)), so
-//   * the LayerNorm statistics are in-lane sums plus two lane exchanges (the four lanes l, l^16, l^32, l^48 share a row);
+//   * the LayerNorm statistics are in-lane (count, mean, M2) merges plus two lane exchanges (the four lanes l, l^16, l^32, l^48 share a row);
 //   * X is streamed twice (statistics, then operands): the second pass hits the L2 (64 KiB per wave), HBM sees the 67 MB once;
 //   * fp32 fidelity on an fp16 matrix core: activation and weight are each split into fp16 hi + lo and three MFMAs (hi*hi + lo*hi + hi*lo)
 //     accumulate in fp32 -- the dropped lo*lo term is 2^-22 relative, i.e. the result is the fp32 dot product to rounding, as before.
 // Under CFG a tile holds eight conditional rows and their eight unconditional twins, which land in lanes l and l ^ 32 of the result.
-// (D % 128 == 0: the four waves of a block take the 32-deep k-steps round-robin.)
+// (D % 32 == 0: the four waves of a block take the 32-deep k-steps round-robin; with D % 128 != 0 they hold unequal numbers of them, at D = 64 two hold none.)
 template <bool CFG, int NT>
 __global__ __launch_bounds__(256) void final_layer_mfma_kernel(const float* __restrict__ X, int M, int D, int tokens, const float* __restrict__ shift,
                                                                const float* __restrict__ scale, long mod_stride, const float* __restrict__ Wf,
@@ -604,7 +604,7 @@ __global__ __launch_bounds__(256) void final_layer_mfma_kernel(const float* __re
                                                                const float* base, const float* __restrict__ dt_ptr) {
   // one BLOCK per 16-row tile; its four waves split K (k-steps wv, wv + 4, ...) so that sixteen waves per CU cover the memory latency, and
   // combine their partial statistics / partial accumulators through the LDS in a fixed order
-  __shared__ float st_s[4][16][2];
+  __shared__ float st_s[4][16][3];
   __shared__ float acc_s[4][NT][64][4];
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, a = lane & 15, q = lane >> 4;
   const long tile = blockIdx.x;
@@ -612,28 +612,44 @@ __global__ __launch_bounds__(256) void final_layer_mfma_kernel(const float* __re
   const long m = CFG ? tile * 8 + (a & 7) + (a >> 3) * (long)Mh : tile * 16 + a;  // this lane's operand row
   const float* xr = X + m * D + 8 * q;
   const int nks = D >> 5;
-  // ---- pass 1: shifted one-pass statistics (shift = the row's first element)
-  const float c0 = X[m * D];
-  float sx = 0.f, sq = 0.f;
+  // ---- pass 1: centred statistics in one pass over X.  Every eight-value chunk gives its own mean and its sum of squares ABOUT that mean (the values are
+  // in registers); chunks, lanes and waves are merged as (count, mean, M2) triples, M2 += M2' + (mean' - mean)^2 n n' / (n + n').  Every term is
+  // non-negative, so nothing cancels wherever an outlier channel sits.
+  float cn = 0.f, mu = 0.f, m2 = 0.f;
 #pragma unroll 4
   for (int ks = wv; ks < nks; ks += 4) {
-    const f32x4 x0 = *(const f32x4*)(xr + 32 * ks) - c0, x1 = *(const f32x4*)(xr + 32 * ks + 4) - c0;
-    sx += (x0.x + x0.y) + (x0.z + x0.w) + (x1.x + x1.y) + (x1.z + x1.w);
-    sq += (x0.x * x0.x + x0.y * x0.y) + (x0.z * x0.z + x0.w * x0.w) + (x1.x * x1.x + x1.y * x1.y) + (x1.z * x1.z + x1.w * x1.w);
+    const f32x4 x0 = *(const f32x4*)(xr + 32 * ks), x1 = *(const f32x4*)(xr + 32 * ks + 4);
+    const float m8 = (((x0.x + x0.y) + (x0.z + x0.w)) + ((x1.x + x1.y) + (x1.z + x1.w))) * 0.125f;
+    const f32x4 d0 = x0 - m8, d1 = x1 - m8;
+    const float q8 = ((d0.x * d0.x + d0.y * d0.y) + (d0.z * d0.z + d0.w * d0.w)) + ((d1.x * d1.x + d1.y * d1.y) + (d1.z * d1.z + d1.w * d1.w));
+    const float dl = m8 - mu, nn = cn + 8.f, f = 8.f / nn;
+    mu += dl * f;
+    m2 += q8 + dl * dl * (cn * f);
+    cn = nn;
   }
-  sx += __shfl_xor(sx, 16, 64);
-  sq += __shfl_xor(sq, 16, 64);
-  sx += __shfl_xor(sx, 32, 64);
-  sq += __shfl_xor(sq, 32, 64);
+#pragma unroll
+  for (int mask = 16; mask <= 32; mask <<= 1) {  // the four lanes of a row hold equal counts
+    const float dl = __shfl_xor(mu, mask, 64) - mu;
+    m2 = (m2 + __shfl_xor(m2, mask, 64)) + dl * dl * (0.5f * cn);
+    mu += 0.5f * dl;
+    cn += cn;
+  }
   if (q == 0) {
-    st_s[wv][a][0] = sx;
-    st_s[wv][a][1] = sq;
+    st_s[wv][a][0] = cn;
+    st_s[wv][a][1] = mu;
+    st_s[wv][a][2] = m2;
   }
   __syncthreads();
-  sx = (st_s[0][a][0] + st_s[1][a][0]) + (st_s[2][a][0] + st_s[3][a][0]);
-  sq = (st_s[0][a][1] + st_s[1][a][1]) + (st_s[2][a][1] + st_s[3][a][1]);
-  const float dl = sx / (float)D, mean = c0 + dl;
-  const float rstd = rsqrtf(fmaxf(sq / (float)D - dl * dl, 0.f) + 1e-6f);
+  cn = st_s[0][a][0], mu = st_s[0][a][1], m2 = st_s[0][a][2];  // wave 0 always has a k-step; the others may hold fewer (D % 128 != 0) or none (D = 64)
+#pragma unroll
+  for (int w = 1; w < 4; ++w) {
+    const float nb = st_s[w][a][0], dl = st_s[w][a][1] - mu, nn = cn + nb, f = nb / nn;
+    mu += dl * f;
+    m2 += st_s[w][a][2] + dl * dl * (cn * f);
+    cn = nn;
+  }
+  const float mean = mu;
+  const float rstd = rsqrtf(m2 / (float)D + 1e-6f);
   const long mo = (m / tokens) * mod_stride + 8 * q;
   // ---- pass 2: operands + MFMAs (X again, now from the L2)
   f32x4_t acc[NT];

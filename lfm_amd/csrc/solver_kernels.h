@@ -75,6 +75,8 @@ extern "C" int lfm_rk_error_norm(const float* y0, const float* y1, const float* 
   if (n <= 0 || n % 4 || (((uintptr_t)y0 | (uintptr_t)y1) & 15)) return LFM_ERR_ALIGN;
   LinPtrs p;
   for (int i = 0; i < 8; ++i) p.k[i] = i < nk ? k_host_ptrs[i] : nullptr;
+  for (int i = 0; i < nk; ++i)  // every k is read as f32x4
+    if ((uintptr_t)p.k[i] & 15) return LFM_ERR_ALIGN;
   const int nb = (int)(cdiv(n / 4, 256) < RK_BLOCKS ? cdiv(n / 4, 256) : RK_BLOCKS);
   hipLaunchKernelGGL(rk_err_partial_kernel, dim3(nb), dim3(256), 0, (hipStream_t)stream, y0, y1, p, e_coef, dt, nk, n / 4, rtol, atol, scratch);
   LFM_CHECK_LAUNCH();
@@ -86,9 +88,11 @@ extern "C" int lfm_rk_error_norm(const float* y0, const float* y1, const float* 
 extern "C" int lfm_lincomb(float* out, const float* base, const float* const* k_host_ptrs, const float* coef, const float* scale, int nk,
                            long n, lfm_stream_t stream) {
   if (!out || !coef || nk < 0 || nk > 8 || (nk && !k_host_ptrs)) return LFM_ERR_ARG;
-  if (n % 4 || ((uintptr_t)out & 15)) return LFM_ERR_ALIGN;
+  if (n % 4 || (((uintptr_t)out | (uintptr_t)base) & 15)) return LFM_ERR_ALIGN;
   LinPtrs p;
   for (int i = 0; i < 8; ++i) p.k[i] = i < nk ? k_host_ptrs[i] : nullptr;
+  for (int i = 0; i < nk; ++i)  // base and every k are read as f32x4
+    if ((uintptr_t)p.k[i] & 15) return LFM_ERR_ALIGN;
   hipLaunchKernelGGL(lincomb_kernel, dim3(cdiv(n / 4, 256)), dim3(256), 0, (hipStream_t)stream, out, base, p, coef, scale, nk, n / 4);
   LFM_CHECK_LAUNCH();
   return LFM_OK;
