@@ -342,6 +342,15 @@ int lfm_conv3x3_f16(const void* in, const void* w, const float* bias, const void
 size_t lfm_conv3x3_workspace_bytes(int N, int H, int W, int Cin, int Cout);
 int lfm_conv3x3_f16_ws(const void* in, const void* w, const float* bias, const void* resid, void* out, int N, int H, int W, int Cin, int Cout,
                        int mode, void* workspace, size_t workspace_bytes, lfm_stream_t stream);
+/* The same with out = (conv3x3 + bias (+ resid)) * scale, the scale applied in fp32 to the finished sum before the fp16 store, on every path (halo
+ * kernel, implicit GEMM, split-K finish): the residual epilogue of EDM's UNetBlock with skip_scale = sqrt(0.5) (SongUNet / ddpm++, models/EDM.py:272-274).
+ * scale = 1 is bit-identical to lfm_conv3x3_f16_ws. */
+int lfm_conv3x3_scaled_f16_ws(const void* in, const void* w, const float* bias, const void* resid, float scale, void* out, int N, int H, int W, int Cin,
+                              int Cout, int mode, void* workspace, size_t workspace_bytes, lfm_stream_t stream);
+/* Which path lfm_conv3x3_f16_ws (and its scaled form) takes for this shape with 16-byte aligned operands and a workspace of workspace_bytes, under the
+ * calling thread's flags: 1 = the halo-tiled direct kernel, 2 = split-K slices + the finish kernel, 3 = one implicit GEMM; LFM_ERR_SHAPE for a shape that
+ * is refused.  No launch; usable without a GPU. */
+int lfm_conv3x3_plan(int N, int H, int W, int Cin, int Cout, int mode, size_t workspace_bytes);
 /* first conv (unet.py:475): fp32 NCHW [N,Cin<=16,H,W] -> fp16 NHWC [N,H,W,Cout]; w fp32 [Cout,Cin,3,3] */
 int lfm_conv3x3_in_f32(const float* x_nchw, const float* w, const float* bias, void* out_nhwc, int N, int H, int W, int Cin, int Cout,
                        lfm_stream_t stream);
@@ -355,6 +364,12 @@ int lfm_linear_f16(const void* A, long lda, const void* W, long ldw, void* C, lo
  * output-block ResBlock, whose input is th.cat([h, hs.pop()], dim=1) (unet.py:649 + :236).  K1 % 64 == 0, K2 % 8 == 0. */
 int lfm_linear2_f16(const void* A1, int K1, const void* A2, int K2, const void* W, long ldw, void* C, long ldc, int M, int N, const float* bias,
                     const void* resid, lfm_stream_t stream);
+/* lfm_linear_f16 / lfm_linear2_f16 with C = (A W^T + bias (+ resid)) * scale (fp32, before the fp16 store): the attention projection and the 1x1 skip of
+ * EDM's UNetBlock with skip_scale != 1 (models/EDM.py:290-291).  scale = 1 is bit-identical to the unscaled entry points. */
+int lfm_linear_scaled_f16(const void* A, long lda, const void* W, long ldw, void* C, long ldc, int M, int N, int K, const float* bias,
+                          const void* resid, float scale, lfm_stream_t stream);
+int lfm_linear2_scaled_f16(const void* A1, int K1, const void* A2, int K2, const void* W, long ldw, void* C, long ldc, int M, int N,
+                           const float* bias, const void* resid, float scale, lfm_stream_t stream);
 /* y = silu?( GroupNorm(groups <= 32)(x; gamma, beta, eps) * (1 + scale[n]) + shift[n] );  film = fp32 [N][scale(C) | shift(C)] rows film_stride apart,
  * or NULL (nn.py:17-19,93-100; scale-shift-norm unet.py:228-233).  scratch: lfm_groupnorm_scratch_bytes(N, C) bytes. */
 size_t lfm_groupnorm_scratch_bytes(int N, int C);
@@ -391,6 +406,15 @@ int lfm_unet_attention_plan(int N, int T, int heads, int ch);
 int lfm_time_embed(const float* t, int t_len, const float* w0, const float* b0, const float* w2, const float* b2, const float* label_table,
                    const int64_t* y, int label_rows, float* scratch_h1, float* emb, void* emb_silu_f16, int N, int F, int E,
                    lfm_stream_t stream);
+/* DDPM++ mapping network of SongUNet (models/EDM.py:663-675, PositionalEmbedding :490-505 with endpoint = True), all fp32:
+ *   in  = [sin(t f) | cos(t f)] (+ label_scale * label_table[y] + label_bias),  f_i = 10000^(-i / (F / 2 - 1)),  i < F / 2
+ *   emb = silu(W1 silu(W0 in + b0) + b1):  fp32 [N,E] and its fp16 copy (already SiLU'd: the blocks' affine GEMM reads it as it is).
+ * w0 [E,F], w1 [E,E] row-major; label_table = map_label.weight^T [label_rows][F], label_bias [F], label_scale = sqrt(label_dim); all three NULL / unused
+ * for an unconditional evaluation.  t has t_len = 1 or N entries; scratch_h1: N x E floats.  F even, F >= 4.  A label outside [0, label_rows) poisons
+ * its row with NaN. */
+int lfm_song_embed(const float* t, int t_len, const float* w0, const float* b0, const float* w1, const float* b1, const float* label_table,
+                   const float* label_bias, float label_scale, const int64_t* y, int label_rows, float* scratch_h1, float* emb, void* emb_f16, int N,
+                   int F, int E, lfm_stream_t stream);
 
 /* ------------------------------------------------------------------ solver helpers (device-resident time grid)
  * Advance the captured step:  s = *step;  t_cur[0] = ts[s];  t_next[0] = ts[s+1];  dt_cur[0] = dts[s];  *step = s+1.

@@ -228,14 +228,19 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo_kernel(const half_t* __re
 // out[n, H, W, Cout] = conv3x3(in) through `epi` (bias, residual, statistics); in = [n, H, W, Cin], or [n, H/2, W/2, Cin] with UPS = 1 (nearest-2x
 // upsample fused).  Returns 1 when the shape is not this kernel's (H, W multiples of 16; Cin a multiple of 64; Cout a multiple of 128; at least
 // one workgroup per CU), so that the caller takes the implicit GEMM.
+// is the shape this kernel's (the launcher's answer 1 otherwise; lfm_conv3x3_plan asks too)
+static inline bool conv3x3_halo_takes(int n, int H, int W, int Cin, int Cout) {
+  if (n <= 0 || (H & 15) || (W & 15) || (Cin & 63) || (Cout & 127)) return false;
+  if ((long)n * H * W >= (1L << 31) || (long)H * W * Cin >= (1L << 31)) return false;
+  const long total = (long)n * (W / 16) * (H / 16) * (Cout / 128);
+  return !((total < 256 && !(lfm_gemm_debug_flags() & LFM_DBG_CONV_HALO_SMALL)) || total >= (1L << 31));  // flag: small problems too (parity tests)
+}
 template <int UPS, class Epi>
 static inline int launch_conv3x3_halo(const half_t* in, const half_t* zeros, const half_t* Wt, int n, int H, int W, int Cin, int Cout, const Epi& epi,
                                       hipStream_t st) {
-  if (n <= 0 || (H & 15) || (W & 15) || (Cin & 63) || (Cout & 127)) return 1;
-  if ((long)n * H * W >= (1L << 31) || (long)H * W * Cin >= (1L << 31)) return 1;
+  if (!conv3x3_halo_takes(n, H, W, Cin, Cout)) return 1;
   const int tiles_x = W / 16, tiles_per_img = tiles_x * (H / 16), nb = Cout / 128;
   const long total = (long)n * tiles_per_img * nb;
-  if ((total < 256 && !(lfm_gemm_debug_flags() & LFM_DBG_CONV_HALO_SMALL)) || total >= (1L << 31)) return 1;  // flag: small problems too (parity tests)
   if (((uintptr_t)in | (uintptr_t)Wt | (uintptr_t)zeros) & 15) return LFM_ERR_ALIGN;
   if (!lfm_kernel_lds<&conv3x3_halo_kernel<Epi, UPS>>(CH_LDS_BYTES)) return LFM_ERR_LAUNCH;
   hipLaunchKernelGGL((conv3x3_halo_kernel<Epi, UPS>), dim3((unsigned)total), dim3(256), CH_LDS_BYTES, st, in, zeros, Wt, 9L * Cin, H, W, Cin, tiles_x,

@@ -63,11 +63,12 @@ struct ASrcConv {
 };
 
 // ------------------------------------------------------------------ epilogues
-struct EpiResidF16 {  // out = acc + bias (+ residual) -> fp16
+struct EpiResidF16 {  // out = (acc + bias (+ residual)) * scale -> fp16
   half_t* C;
   long ldc;
   const float* bias;    // may be null
   const half_t* resid;  // may be null; same layout as C
+  float scale = 1.0f;   // applied in fp32 to the finished sum (EDM UNetBlock skip_scale, models/EDM.py:272-274,290-291); x * 1.0f is exact: the default changes no bit
   struct Aux {
     f32x4 b;
     half4_t r;
@@ -80,15 +81,17 @@ struct EpiResidF16 {  // out = acc + bias (+ residual) -> fp16
   }
   __device__ __forceinline__ void store(int m, int n, f32x4 v, const Aux& a) const {
     v += a.b;
-    half4_t h = {(half_t)(v.x + (float)a.r.x), (half_t)(v.y + (float)a.r.y), (half_t)(v.z + (float)a.r.z), (half_t)(v.w + (float)a.r.w)};
+    half4_t h = {(half_t)((v.x + (float)a.r.x) * scale), (half_t)((v.y + (float)a.r.y) * scale), (half_t)((v.z + (float)a.r.z) * scale),
+                 (half_t)((v.w + (float)a.r.w) * scale)};
     *(half4_t*)(C + (long)m * ldc + n) = h;
   }
   __device__ __forceinline__ bool wide_ok() const { return (ldc & 7) == 0 && ((uintptr_t)C & 15) == 0 && (!resid || ((uintptr_t)resid & 15) == 0); }
   __device__ __forceinline__ half8_t round8(f32x4 lo, f32x4 hi, const Aux& al, const Aux& ah) const {  // eight columns of one row, as stored
     lo += al.b;
     hi += ah.b;
-    return (half8_t){(half_t)(lo.x + (float)al.r.x), (half_t)(lo.y + (float)al.r.y), (half_t)(lo.z + (float)al.r.z), (half_t)(lo.w + (float)al.r.w),
-                     (half_t)(hi.x + (float)ah.r.x), (half_t)(hi.y + (float)ah.r.y), (half_t)(hi.z + (float)ah.r.z), (half_t)(hi.w + (float)ah.r.w)};
+    return (half8_t){(half_t)((lo.x + (float)al.r.x) * scale), (half_t)((lo.y + (float)al.r.y) * scale), (half_t)((lo.z + (float)al.r.z) * scale),
+                     (half_t)((lo.w + (float)al.r.w) * scale), (half_t)((hi.x + (float)ah.r.x) * scale), (half_t)((hi.y + (float)ah.r.y) * scale),
+                     (half_t)((hi.z + (float)ah.r.z) * scale), (half_t)((hi.w + (float)ah.r.w) * scale)};
   }
   __device__ __forceinline__ void store8(int m, int n, f32x4 lo, f32x4 hi, const Aux& al, const Aux& ah) const {
     *(half8_t*)(C + (long)m * ldc + n) = round8(lo, hi, al, ah);

@@ -47,8 +47,8 @@ static int conv3x3_mode(const half_t* xi, const half_t* z, const half_t* wi, con
   return launch_gemm_auto(a, wi, 9L * Cin, M, Cout, 9 * Cin, epi, st);
 }
 
-extern "C" int lfm_conv3x3_f16_ws(const void* in, const void* w, const float* bias, const void* resid, void* out, int N, int H, int W, int Cin,
-                                  int Cout, int mode, void* workspace, size_t workspace_bytes, lfm_stream_t stream) {
+static int conv3x3_f16_impl(const void* in, const void* w, const float* bias, const void* resid, float scale, void* out, int N, int H, int W, int Cin,
+                            int Cout, int mode, void* workspace, size_t workspace_bytes, lfm_stream_t stream) {
   if (!in || !w || !out) return LFM_ERR_ARG;
   if (N <= 0 || H <= 0 || W <= 0 || Cin % 64 || Cout % 4 || mode < 0 || mode > 2) return LFM_ERR_SHAPE;
   if (mode == 1 && ((H | W) & 1)) return LFM_ERR_SHAPE;
@@ -56,7 +56,7 @@ extern "C" int lfm_conv3x3_f16_ws(const void* in, const void* w, const float* bi
   const half_t* z = zero_page();
   if (!z) return LFM_ERR_LAUNCH;
   const int M = N * H * W;
-  EpiResidF16 epi{(half_t*)out, Cout, bias, (const half_t*)resid};
+  EpiResidF16 epi{(half_t*)out, Cout, bias, (const half_t*)resid, scale};
   hipStream_t st = (hipStream_t)stream;
   const half_t* wi = (const half_t*)w;
   const half_t* xi = (const half_t*)in;
@@ -70,6 +70,29 @@ extern "C" int lfm_conv3x3_f16_ws(const void* in, const void* w, const float* bi
   if (mode == 0) return conv3x3_mode<0>(xi, z, wi, epi, H, W, Cin, Cout, M, ws, workspace_bytes, st);
   if (mode == 1) return conv3x3_mode<1>(xi, z, wi, epi, H, W, Cin, Cout, M, ws, workspace_bytes, st);
   return conv3x3_mode<2>(xi, z, wi, epi, H, W, Cin, Cout, M, ws, workspace_bytes, st);
+}
+
+extern "C" int lfm_conv3x3_f16_ws(const void* in, const void* w, const float* bias, const void* resid, void* out, int N, int H, int W, int Cin,
+                                  int Cout, int mode, void* workspace, size_t workspace_bytes, lfm_stream_t stream) {
+  return conv3x3_f16_impl(in, w, bias, resid, 1.0f, out, N, H, W, Cin, Cout, mode, workspace, workspace_bytes, stream);
+}
+// out = (conv + bias (+ resid)) * scale: the residual epilogue of EDM's UNetBlock with skip_scale = sqrt(0.5) (SongUNet, models/EDM.py:272-274).  The scale
+// rides in the epilogue struct, so the halo kernel, the implicit GEMM and the split-K finish kernel all apply it to the fp32 sum before the fp16 store.
+extern "C" int lfm_conv3x3_scaled_f16_ws(const void* in, const void* w, const float* bias, const void* resid, float scale, void* out, int N, int H, int W,
+                                         int Cin, int Cout, int mode, void* workspace, size_t workspace_bytes, lfm_stream_t stream) {
+  return conv3x3_f16_impl(in, w, bias, resid, scale, out, N, H, W, Cin, Cout, mode, workspace, workspace_bytes, stream);
+}
+
+// Which path lfm_conv3x3_f16_ws takes for this shape with 16-byte-aligned operands and a workspace of `workspace_bytes`: the same questions in the same order
+extern "C" int lfm_conv3x3_plan(int N, int H, int W, int Cin, int Cout, int mode, size_t workspace_bytes) {
+  if (N <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cin % 64 || Cout <= 0 || Cout % 4 || mode < 0 || mode > 2) return LFM_ERR_SHAPE;
+  if (mode == 1 && ((H | W) & 1)) return LFM_ERR_SHAPE;
+  if (mode != 2 && conv_halo_allowed() && conv3x3_halo_takes(N, H, W, Cin, Cout)) return 1;
+  const int M = N * H * W, K = 9 * Cin;
+  if (workspace_bytes && lfm_gemm_selected_v1_ok() != 0 &&
+      (splitk256_slices(M, Cout, K, workspace_bytes) || splitk_slices(M, Cout, K, workspace_bytes, CONV_SPLITK_MAX_TILES, CONV_SPLITK_MAX_WG) >= 2))
+    return 2;
+  return 3;
 }
 
 extern "C" int lfm_conv3x3_f16(const void* in, const void* w, const float* bias, const void* resid, void* out, int N, int H, int W, int Cin,
@@ -92,23 +115,40 @@ extern "C" int lfm_conv3x3_out_f32(const void* in, const void* w4, const float* 
   return launch_gemm_tn(ASrcConv<0>{(const half_t*)in, z, H, W, Cin, M}, (const half_t*)w4, 9L * Cin, M, 4, 9 * Cin, eo, (hipStream_t)stream);
 }
 
-extern "C" int lfm_linear_f16(const void* A, long lda, const void* W, long ldw, void* C, long ldc, int M, int N, int K, const float* bias,
-                              const void* resid, lfm_stream_t stream) {
+static int linear_f16_impl(const void* A, long lda, const void* W, long ldw, void* C, long ldc, int M, int N, int K, const float* bias, const void* resid,
+                           float scale, lfm_stream_t stream) {
   if (!A || !W || !C) return LFM_ERR_ARG;
   if ((lda % 8) || ((uintptr_t)A & 15)) return LFM_ERR_ALIGN;
   return launch_gemm_auto(ASrcRowMajor{(const half_t*)A, lda, M, 0}, (const half_t*)W, ldw, M, N, K,
-                          EpiResidF16{(half_t*)C, ldc, bias, (const half_t*)resid}, (hipStream_t)stream);
+                          EpiResidF16{(half_t*)C, ldc, bias, (const half_t*)resid, scale}, (hipStream_t)stream);
+}
+extern "C" int lfm_linear_f16(const void* A, long lda, const void* W, long ldw, void* C, long ldc, int M, int N, int K, const float* bias,
+                              const void* resid, lfm_stream_t stream) {
+  return linear_f16_impl(A, lda, W, ldw, C, ldc, M, N, K, bias, resid, 1.0f, stream);
+}
+// C = (A W^T + bias (+ resid)) * scale: the attention projection of EDM's UNetBlock with skip_scale != 1 (models/EDM.py:290-291) and its 1x1 skip
+extern "C" int lfm_linear_scaled_f16(const void* A, long lda, const void* W, long ldw, void* C, long ldc, int M, int N, int K, const float* bias,
+                                     const void* resid, float scale, lfm_stream_t stream) {
+  return linear_f16_impl(A, lda, W, ldw, C, ldc, M, N, K, bias, resid, scale, stream);
 }
 
 // C = [A1 | A2] W^T + bias (+ resid): the 1x1 skip convolution of a ResBlock whose input is the channel concat of two tensors (unet.py:649 + :236),
 // read in place: the K range [0, K1) comes from A1 [M, K1], [K1, K1 + K2) from A2 [M, K2].  K1 % 64 == 0 (a K-tile never straddles the seam).
-extern "C" int lfm_linear2_f16(const void* A1, int K1, const void* A2, int K2, const void* W, long ldw, void* C, long ldc, int M, int N,
-                               const float* bias, const void* resid, lfm_stream_t stream) {
+static int linear2_f16_impl(const void* A1, int K1, const void* A2, int K2, const void* W, long ldw, void* C, long ldc, int M, int N, const float* bias,
+                            const void* resid, float scale, lfm_stream_t stream) {
   if (!A1 || !A2 || !W || !C) return LFM_ERR_ARG;
   if (K1 <= 0 || K2 <= 0 || (K1 % 64) || (K2 % 8)) return LFM_ERR_SHAPE;
   if (((uintptr_t)A1 | (uintptr_t)A2) & 15) return LFM_ERR_ALIGN;
   return launch_gemm_auto(ASrcRowMajor2{(const half_t*)A1, (const half_t*)A2, K1, K2, M, 0}, (const half_t*)W, ldw, M, N, K1 + K2,
-                          EpiResidF16{(half_t*)C, ldc, bias, (const half_t*)resid}, (hipStream_t)stream);
+                          EpiResidF16{(half_t*)C, ldc, bias, (const half_t*)resid, scale}, (hipStream_t)stream);
+}
+extern "C" int lfm_linear2_f16(const void* A1, int K1, const void* A2, int K2, const void* W, long ldw, void* C, long ldc, int M, int N,
+                               const float* bias, const void* resid, lfm_stream_t stream) {
+  return linear2_f16_impl(A1, K1, A2, K2, W, ldw, C, ldc, M, N, bias, resid, 1.0f, stream);
+}
+extern "C" int lfm_linear2_scaled_f16(const void* A1, int K1, const void* A2, int K2, const void* W, long ldw, void* C, long ldc, int M, int N,
+                                      const float* bias, const void* resid, float scale, lfm_stream_t stream) {
+  return linear2_f16_impl(A1, K1, A2, K2, W, ldw, C, ldc, M, N, bias, resid, scale, stream);
 }
 
 // ------------------------------------------------------------------ first conv: fp32 NCHW (Cin <= 16) -> fp16 NHWC
@@ -928,6 +968,73 @@ extern "C" int lfm_time_embed(const float* t, int t_len, const float* w0, const 
   hipLaunchKernelGGL(time_embed1_kernel, dim3(cdiv(E, 4), N), dim3(256), 0, st, t, t_len, w0, b0, scratch_h1, F, E);
   LFM_CHECK_LAUNCH();
   hipLaunchKernelGGL(time_embed2_kernel, dim3(cdiv(E, 4), N), dim3(256), 0, st, scratch_h1, w2, b2, label_table, y, label_rows, emb, (half_t*)emb_silu_f16, E);
+  LFM_CHECK_LAUNCH();
+  return LFM_OK;
+}
+
+// ------------------------------------------------------------------ DDPM++ mapping network (SongUNet, models/EDM.py:663-675 + PositionalEmbedding :490-505)
+// in[k]  = pe[k] (+ sqrt(L) W_label[:, y][k] + b_label[k]),  pe = [sin(t f) | cos(t f)],  f_i = 10000^(-i / (F / 2 - 1))   (endpoint = True; the reference
+//          computes [cos | sin] and flips the halves);  emb = silu(W1 silu(W0 in + b0) + b1): fp32 and its fp16 copy, which the blocks' `affine` GEMM reads
+//          as it is (already SiLU'd).  All fp32.  label_table is W_label^T [label_rows][F]; a label outside [0, label_rows) poisons its row with NaN.
+// N x E values per evaluation: the correctly-rounded exp and a true division (silu_f's v_exp_f32 / v_rcp_f32 are ~2 ulp each, and this network has two
+// SiLUs in sequence where lfm_time_embed has one)
+__device__ __forceinline__ float silu_exact_f(float x) { return x / (1.0f + expf(-x)); }
+__global__ __launch_bounds__(256) void song_embed1_kernel(const float* __restrict__ t, int t_len, const float* __restrict__ w0, const float* __restrict__ b0,
+                                                          const float* __restrict__ label_table, const float* __restrict__ label_bias, float label_scale,
+                                                          const int64_t* __restrict__ y, int label_rows, float* __restrict__ h1, int F, int E) {
+  const int r = blockIdx.y, lane = threadIdx.x & 63;
+  const int j = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (j >= E) return;
+  const float tv = t[t_len == 1 ? 0 : r];
+  const int half = F / 2;
+  const float* w = w0 + (long)j * F;
+  const float* lab = nullptr;
+  bool poison = false;
+  if (label_table) {
+    const long yr = (long)y[r];
+    if (yr >= 0 && yr < label_rows) lab = label_table + yr * F;
+    else poison = true;
+  }
+  float s = 0.f;
+  for (int k = lane; k < 2 * half; k += 64) {
+    const int i = k < half ? k : k - half;
+    const float a = tv * expf(-9.210340371976184f * (float)i / (float)(half - 1));
+    float v = k < half ? sinf(a) : cosf(a);
+    if (lab) v += label_scale * lab[k] + label_bias[k];
+    s += w[k] * v;
+  }
+  s = wave_sum(s);
+  if (lane == 0) h1[(long)r * E + j] = poison ? __builtin_nanf("") : silu_exact_f(s + b0[j]);
+}
+__global__ __launch_bounds__(256) void song_embed2_kernel(const float* __restrict__ h1, const float* __restrict__ w1, const float* __restrict__ b1,
+                                                          float* __restrict__ emb, half_t* __restrict__ emb_f16, int E) {
+  const int r = blockIdx.y, lane = threadIdx.x & 63;
+  const int j = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (j >= E) return;
+  const float* w = w1 + (long)j * E;
+  const float* h = h1 + (long)r * E;
+  float s = 0.f;
+  for (int k = lane; k < E; k += 64) s += w[k] * h[k];
+  s = wave_sum(s);
+  if (lane == 0) {
+    const float v = silu_exact_f(s + b1[j]);
+    emb[(long)r * E + j] = v;
+    emb_f16[(long)r * E + j] = (half_t)v;
+  }
+}
+
+extern "C" int lfm_song_embed(const float* t, int t_len, const float* w0, const float* b0, const float* w1, const float* b1, const float* label_table,
+                              const float* label_bias, float label_scale, const int64_t* y, int label_rows, float* scratch_h1, float* emb,
+                              void* emb_f16, int N, int F, int E, lfm_stream_t stream) {
+  if (!t || !w0 || !b0 || !w1 || !b1 || !scratch_h1 || !emb || !emb_f16) return LFM_ERR_ARG;
+  if ((label_table != nullptr) != (y != nullptr) || (label_table != nullptr) != (label_bias != nullptr)) return LFM_ERR_ARG;
+  if (label_table && label_rows <= 0) return LFM_ERR_SHAPE;
+  if (N <= 0 || F < 4 || (F & 1) || E <= 0 || (t_len != 1 && t_len != N)) return LFM_ERR_SHAPE;  // F >= 4: the endpoint table divides by F / 2 - 1
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(song_embed1_kernel, dim3(cdiv(E, 4), N), dim3(256), 0, st, t, t_len, w0, b0, label_table, label_bias, label_scale, y, label_rows,
+                     scratch_h1, F, E);
+  LFM_CHECK_LAUNCH();
+  hipLaunchKernelGGL(song_embed2_kernel, dim3(cdiv(E, 4), N), dim3(256), 0, st, scratch_h1, w1, b1, emb, (half_t*)emb_f16, E);
   LFM_CHECK_LAUNCH();
   return LFM_OK;
 }

@@ -169,6 +169,16 @@ def lib():
     L.lfm_unet_attention_plan.argtypes = [I, I, I, I]
     L.lfm_time_embed.restype = I
     L.lfm_time_embed.argtypes = [V, I, V, V, V, V, V, V, I, V, V, V, I, I, I, V]
+    L.lfm_conv3x3_scaled_f16_ws.restype = I
+    L.lfm_conv3x3_scaled_f16_ws.argtypes = [V, V, V, V, F, V, I, I, I, I, I, I, V, C.c_size_t, V]
+    L.lfm_conv3x3_plan.restype = I
+    L.lfm_conv3x3_plan.argtypes = [I, I, I, I, I, I, C.c_size_t]
+    L.lfm_linear_scaled_f16.restype = I
+    L.lfm_linear_scaled_f16.argtypes = [V, LG, V, LG, V, LG, I, I, I, V, V, F, V]
+    L.lfm_linear2_scaled_f16.restype = I
+    L.lfm_linear2_scaled_f16.argtypes = [V, I, V, I, V, LG, V, LG, I, I, V, V, F, V]
+    L.lfm_song_embed.restype = I
+    L.lfm_song_embed.argtypes = [V, I, V, V, V, V, V, V, F, V, I, V, V, V, I, I, I, V]
     L.lfm_vae_groupnorm_f16.restype = I
     L.lfm_vae_groupnorm_f16.argtypes = [V, V, V, V, V, C.c_size_t, I, I, I, I, V]
     L.lfm_vae_conv3x3_gn_f16.restype = I
@@ -358,6 +368,15 @@ def attention_plan(batch, heads, head_dim, T):
     """The kernel id (1 .. 6, include/lfm_hip.h: lfm_attention_plan) dit_attention runs for this shape under the calling thread's flags and the library
     options, or LFM_ERR_SHAPE (-1) for a shape no kernel serves (no launch, no GPU needed)."""
     return lib().lfm_attention_plan(int(batch), int(heads), int(head_dim), int(T))
+
+
+CONV_PLAN_HALO, CONV_PLAN_SPLITK, CONV_PLAN_GEMM = 1, 2, 3  # lfm_conv3x3_plan
+
+
+def conv3x3_plan(N, H, W, Cin, Cout, mode=0, workspace_bytes=0):
+    """The path (1 halo-tiled kernel, 2 split-K + finish kernel, 3 one implicit GEMM; include/lfm_hip.h: lfm_conv3x3_plan) lfm_conv3x3_f16_ws takes for this
+    shape with 16-byte-aligned operands and that much workspace under the calling thread's flags, or LFM_ERR_SHAPE (-1) (no launch, no GPU needed)."""
+    return lib().lfm_conv3x3_plan(int(N), int(H), int(W), int(Cin), int(Cout), int(mode), int(workspace_bytes))
 
 
 def unet_attention_plan(N, T, heads, ch):

@@ -15,8 +15,16 @@ liblfm_hip.so as the origin-ADM UNet (``lfm_amd/models/unet.py``):
 * the class embedding ``map_label(one_hot(y))`` (no bias) is a column lookup of ``map_label.weight``; the label dropped for the
   unconditional half under CFG (``drop_half_label``, EDM.py:825-826) is an extra all-zero row.
 
-Built: ``use_context=False``, ``augment_dim=0``, channels that are multiples of 64 (the implicit-GEMM contract).  SongUNet
-(``ncsn++`` / ``ddpm++``) stays out of scope.
+Built: ``use_context=False``, ``augment_dim=0``, channels that are multiples of 64 (the implicit-GEMM contract).
+
+``SongUNet`` (``model_type == "ddpm++"``, reference :532-706) is built for the DDPM++ settings only -- positional embedding, standard encoder and
+decoder, the [1,1] resample filter, ``channel_mult_noise=1`` -- on the same host-sequenced ops (``_EDMUNet`` holds what the two classes share).  What
+differs from the ADM: the mapping network (``lfm_song_embed``: [sin | cos] table with endpoint, the label term with a bias added BEFORE the first linear, a
+SiLU after the second), the non-adaptive FiLM ``silu(norm1(x + affine(emb)))`` (``lfm_add_image_vec_f16`` + GroupNorm), one attention head over the whole
+width (at most 256 channels: the streamed attention kernel's limit), a 1x1 skip convolution after every resample (``resample_proj``), and
+``skip_scale = sqrt(0.5)`` on both residual sums, applied in fp32 by the scaled epilogues (``lfm_conv3x3_scaled_f16_ws``, ``lfm_linear_scaled_f16``,
+``lfm_linear2_scaled_f16``).  It has no ``forward_with_cfg``, as in the reference.  ``ncsn++`` stays refused: the reference cannot construct it either
+(``config.num_blocks`` is not a flag).
 """
 import numpy as np
 import torch
@@ -73,29 +81,283 @@ class GroupNorm(nn.Module):  # EDM.py:139-151
 
 class UNetBlock(nn.Module):  # EDM.py:188-292 (parameter container)
     def __init__(self, in_channels, out_channels, emb_channels, up=False, down=False, attention=False, num_heads=None,
-                 channels_per_head=64, dropout=0, skip_scale=1, eps=1e-5, init=None, init_zero=None):
+                 channels_per_head=64, dropout=0, skip_scale=1, eps=1e-5, resample_proj=False, adaptive_scale=True, init=None, init_zero=None,
+                 init_attn=None, scaled_epilogue=False):
         super().__init__()
         init, init_zero = init or {}, init_zero or dict(init_weight=0)
         self.in_channels, self.out_channels, self.up, self.down = in_channels, out_channels, up, down
         self.num_heads = 0 if not attention else (num_heads if num_heads is not None else out_channels // channels_per_head)
-        self.skip_scale = skip_scale
-        if skip_scale != 1:
-            raise NotImplementedError("skip_scale != 1 is not built (DhariwalUNet uses 1)")
+        self.skip_scale, self.eps, self.adaptive_scale = float(skip_scale), eps, adaptive_scale
+        if skip_scale != 1 and not scaled_epilogue:  # only SongUNet sequences its residual sums over the scaled epilogues
+            raise NotImplementedError("skip_scale != 1 is built for SongUNet only (DhariwalUNet uses 1)")
         self.norm0 = GroupNorm(in_channels, eps=eps)
         self.conv0 = Conv2d(in_channels, out_channels, 3, up=up, down=down, **init)
-        self.affine = Linear(emb_channels, out_channels * 2, **init)
+        self.affine = Linear(emb_channels, out_channels * (2 if adaptive_scale else 1), **init)
         self.norm1 = GroupNorm(out_channels, eps=eps)
         self.conv1 = Conv2d(out_channels, out_channels, 3, **init_zero)
         self.skip = None
         if out_channels != in_channels or up or down:
-            self.skip = Conv2d(in_channels, out_channels, 1 if out_channels != in_channels else 0, up=up, down=down, **init)
+            self.skip = Conv2d(in_channels, out_channels, 1 if resample_proj or out_channels != in_channels else 0, up=up, down=down, **init)
         if self.num_heads:
             self.norm2 = GroupNorm(out_channels, eps=eps)
-            self.qkv = Conv2d(out_channels, out_channels * 3, 1, **init)
+            self.qkv = Conv2d(out_channels, out_channels * 3, 1, **(init_attn if init_attn is not None else init))
             self.proj = Conv2d(out_channels, out_channels, 1, **init_zero)
 
 
-class DhariwalUNet(nn.Module):
+class _EDMUNet(nn.Module):
+    """What DhariwalUNet and SongUNet share: weight packing, device scratch, the host-sequenced UNetBlock and the encoder / decoder walk.  A subclass builds
+    the parameter tree and provides ``_out_modules`` (the output GroupNorm and convolution), ``_pack_mapping`` and ``_embed`` (its mapping network)."""
+
+    _what = "EDM UNet"
+
+    def _init_state(self):
+        self._packed = None
+        self._scratch = None
+        self._gen = 0
+
+    # ---- packing ------------------------------------------------------------------------------------------------------
+    def _apply(self, fn, *a, **k):
+        before = [(p.data_ptr(), p.dtype, p.device) for p in self.parameters()]
+        out = super()._apply(fn, *a, **k)
+        if before != [(p.data_ptr(), p.dtype, p.device) for p in self.parameters()]:  # only a real move / cast invalidates
+            self._packed = None
+            self._scratch = None
+            self._conv_ws = None
+            self._gen = getattr(self, "_gen", 0) + 1
+        return out
+
+    def load_state_dict(self, *a, **k):
+        self._packed = None
+        self._gen = getattr(self, "_gen", 0) + 1
+        return super().load_state_dict(*a, **k)
+
+    @torch.no_grad()
+    def _pack(self):
+        out_norm, out_conv = self._out_modules()
+        dev = out_conv.weight.device
+        hip.require_gpu(out_conv.weight, self._what)
+        f32 = lambda t: t.detach().to(dev, torch.float32).contiguous()  # noqa: E731
+        f16 = lambda t: t.detach().to(dev, torch.float16).contiguous()  # noqa: E731
+
+        def conv3(m):
+            w = m.weight
+            if w.shape[1] % 64:
+                raise hip.LfmHipError(f"3x3 conv with Cin={w.shape[1]}: the implicit-GEMM path needs Cin % 64 == 0")
+            return f16(w.permute(0, 2, 3, 1).reshape(w.shape[0], -1)), f32(m.bias)
+
+        def conv1(m):
+            return f16(m.weight.reshape(m.weight.shape[0], -1)), f32(m.bias)
+
+        P = {}
+        for group in (self.enc, self.dec):
+            pre = "enc." if group is self.enc else "dec."
+            for name, b in group.items():
+                if b is out_norm or b is out_conv:  # SongUNet keeps its output layers inside `dec` (aux_norm / aux_conv): packed below
+                    continue
+                if isinstance(b, Conv2d):
+                    P[pre + name] = (f32(b.weight), f32(b.bias))
+                    continue
+                d = dict(gn0=(f32(b.norm0.weight), f32(b.norm0.bias)), c0=conv3(b.conv0), aff=(f16(b.affine.weight), f32(b.affine.bias)),
+                         gn1=(f32(b.norm1.weight), f32(b.norm1.bias)), c1=conv3(b.conv1),
+                         skip=conv1(b.skip) if (b.skip is not None and b.skip.weight is not None) else None)
+                if b.num_heads:
+                    C, ch = b.out_channels, b.out_channels // b.num_heads
+                    # reference row (head, c, which) -> our row (head, which, c)
+                    perm = torch.arange(3 * C).reshape(b.num_heads, ch, 3).permute(0, 2, 1).reshape(-1)
+                    d.update(gn2=(f32(b.norm2.weight), f32(b.norm2.bias)),
+                             qkv=(f16(b.qkv.weight.reshape(3 * C, C)[perm]), f32(b.qkv.bias[perm])), proj=conv1(b.proj))
+                P[pre + name] = d
+        # every block's `affine` projection of the embedding (EDM.py:263-265) in ONE GEMM per evaluation: weights stacked row-wise, a block reads its
+        # [scale | shift] columns of the result (28 launches of ~16 us each at the ffhq_adm size otherwise: profiles/r04_config6_kernel_stats.csv)
+        offs, ws_, bs_, off = {}, [], [], 0
+        for key, d in P.items():
+            if isinstance(d, dict):
+                offs[key] = (off, d["aff"][0].shape[0])
+                ws_.append(d["aff"][0])
+                bs_.append(d["aff"][1])
+                off += d["aff"][0].shape[0]
+        P["aff_all"] = (torch.cat(ws_, 0).contiguous(), torch.cat(bs_, 0).contiguous(), offs)
+        self._pack_mapping(P, f32, dev)
+        P["gn_out"] = (f32(out_norm.weight), f32(out_norm.bias))
+        wo = out_conv.weight
+        if wo.shape[0] > 4:
+            raise hip.LfmHipError("output conv with more than 4 channels is not built")
+        w4 = torch.zeros(4, wo.shape[1], 3, 3, device=dev)
+        w4[: wo.shape[0]] = wo
+        b4 = torch.zeros(4, device=dev)
+        b4[: wo.shape[0]] = out_conv.bias
+        P["conv_out"] = (f16(w4.permute(0, 2, 3, 1).reshape(4, -1)), f32(b4))
+        self._packed = P
+        self._gen += 1
+        return P
+
+    # ---- ops --------------------------------------------------------------------------------------------------------------
+    def _gn(self, x, N, HW, C, gb, film, silu, eps=1e-5):
+        groups = min(32, C // 4)  # EDM GroupNorm (EDM.py:139-143)
+        y = torch.empty_like(x)
+        need = hip.lib().lfm_groupnorm_scratch_bytes(N, C)
+        if self._scratch is None or self._scratch.numel() < need or self._scratch.device != x.device:
+            self._scratch = torch.empty(max(need, 1 << 20), dtype=torch.uint8, device=x.device)
+            self._gen += 1
+        hip.check(hip.lib().lfm_groupnorm_f16(hip.ptr(x), hip.ptr(y), hip.ptr(gb[0]), hip.ptr(gb[1]), hip.ptr(film),
+                                              film.stride(0) if film is not None else 0, hip.ptr(self._scratch), N, HW, C, groups, eps,
+                                              1 if silu else 0, hip.stream_ptr(x.device)), "lfm_groupnorm_f16")
+        return y
+
+    def _conv(self, x, wb, N, H, W, Cin, Cout, mode=0, resid=None, scale=1.0):
+        out = torch.empty(N * H * W, Cout, dtype=torch.float16, device=x.device)
+        L = hip.lib()
+        need = L.lfm_conv3x3_workspace_bytes(N, H, W, Cin, Cout)  # split-K slabs of the small-M / huge-K low-resolution levels
+        if need and (getattr(self, "_conv_ws", None) is None or self._conv_ws.numel() < need or self._conv_ws.device != x.device):
+            self._conv_ws = torch.empty(need, dtype=torch.uint8, device=x.device)
+            self._gen += 1
+        ws = self._conv_ws if need else None
+        if scale != 1.0:  # (acc + bias + resid) * skip_scale in the epilogue (SongUNet)
+            hip.check(L.lfm_conv3x3_scaled_f16_ws(hip.ptr(x), hip.ptr(wb[0]), hip.ptr(wb[1]), hip.ptr(resid), scale, hip.ptr(out), N, H, W, Cin, Cout, mode,
+                                                  hip.ptr(ws), ws.numel() if ws is not None else 0, hip.stream_ptr(x.device)), "lfm_conv3x3_scaled_f16_ws")
+            return out
+        hip.check(L.lfm_conv3x3_f16_ws(hip.ptr(x), hip.ptr(wb[0]), hip.ptr(wb[1]), hip.ptr(resid), hip.ptr(out), N, H, W, Cin, Cout, mode,
+                                       hip.ptr(ws), ws.numel() if ws is not None else 0, hip.stream_ptr(x.device)), "lfm_conv3x3_f16_ws")
+        return out
+
+    def _linear(self, x, wb, resid=None, scale=1.0):
+        M, K = x.shape
+        Nout = wb[0].shape[0]
+        out = torch.empty(M, Nout, dtype=torch.float16, device=x.device)
+        if scale != 1.0:
+            hip.check(hip.lib().lfm_linear_scaled_f16(hip.ptr(x), x.stride(0), hip.ptr(wb[0]), wb[0].stride(0), hip.ptr(out), Nout, M, Nout, K,
+                                                      hip.ptr(wb[1]), hip.ptr(resid), scale, hip.stream_ptr(x.device)), "lfm_linear_scaled_f16")
+            return out
+        hip.check(hip.lib().lfm_linear_f16(hip.ptr(x), x.stride(0), hip.ptr(wb[0]), wb[0].stride(0), hip.ptr(out), Nout, M, Nout, K,
+                                           hip.ptr(wb[1]), hip.ptr(resid), hip.stream_ptr(x.device)), "lfm_linear_f16")
+        return out
+
+    def _pool(self, x, N, Ho, Wo, C):
+        y = torch.empty(N * Ho * Wo, C, dtype=torch.float16, device=x.device)
+        hip.check(hip.lib().lfm_avgpool2_f16(hip.ptr(x), hip.ptr(y), N, Ho, Wo, C, hip.stream_ptr(x.device)), "lfm_avgpool2_f16")
+        return y
+
+    def _gn2(self, xa, xb, N, HW, gb, silu, eps=1e-5):
+        """GroupNorm of the channel concat [xa | xb] read in place (``torch.cat([x, skips.pop()], dim=1)``, EDM.py:840-842, is never materialised)."""
+        Ca, Cb = xa.shape[1], xb.shape[1]
+        y = torch.empty(xa.shape[0], Ca + Cb, dtype=torch.float16, device=xa.device)
+        need = hip.lib().lfm_groupnorm_scratch_bytes(N, Ca + Cb)
+        if self._scratch is None or self._scratch.numel() < need or self._scratch.device != xa.device:
+            self._scratch = torch.empty(max(need, 1 << 20), dtype=torch.uint8, device=xa.device)
+            self._gen += 1
+        hip.check(hip.lib().lfm_groupnorm2_f16(hip.ptr(xa), Ca, hip.ptr(xb), Cb, hip.ptr(y), hip.ptr(gb[0]), hip.ptr(gb[1]), None, 0, hip.ptr(self._scratch),
+                                               N, HW, min(32, (Ca + Cb) // 4), eps, 1 if silu else 0, hip.stream_ptr(xa.device)), "lfm_groupnorm2_f16")
+        return y
+
+    def _linear2(self, xa, xb, wb):
+        M, Nout = xa.shape[0], wb[0].shape[0]
+        out = torch.empty(M, Nout, dtype=torch.float16, device=xa.device)
+        hip.check(hip.lib().lfm_linear2_f16(hip.ptr(xa), xa.shape[1], hip.ptr(xb), xb.shape[1], hip.ptr(wb[0]), wb[0].stride(0), hip.ptr(out), Nout, M, Nout,
+                                            hip.ptr(wb[1]), None, hip.stream_ptr(xa.device)), "lfm_linear2_f16")
+        return out
+
+    def _cat(self, pair):
+        h, s = pair
+        cat = torch.empty(h.shape[0], h.shape[1] + s.shape[1], dtype=torch.float16, device=h.device)
+        hip.check(hip.lib().lfm_concat_channels_f16(hip.ptr(h), hip.ptr(s), hip.ptr(cat), h.shape[0], h.shape[1], s.shape[1], hip.stream_ptr(h.device)),
+                  "lfm_concat_channels_f16")
+        return cat
+
+    def _block(self, name, b, x, N, H, W, film_all):
+        """UNetBlock.forward (EDM.py:258-292).  Returns (out, H, W).  `x` may be the pair (h, skip) of a decoder block: its channel concat is then read in place
+        by the block's two consumers -- the first GroupNorm and the 1x1 skip convolution -- as in the origin-ADM UNet (round 6; the concat kernel was 2 % of an
+        evaluation at the ffhq_adm size)."""
+        p = self._packed[name]
+        Cin, Cout, eps, ss = b.in_channels, b.out_channels, b.eps, b.skip_scale
+        pair = None
+        if isinstance(x, tuple):
+            if b.down or b.up or p["skip"] is None or x[0].shape[1] % 64 or x[1].shape[1] % 8:
+                x = self._cat(x)  # resampled / identity-skip inputs need the tensor itself
+            else:
+                pair = x
+        orig = x
+        t = self._gn2(pair[0], pair[1], N, H * W, p["gn0"], True, eps) if pair is not None else self._gn(x, N, H * W, Cin, p["gn0"], None, True, eps)
+        if b.down:
+            H, W = H // 2, W // 2
+            t = self._pool(t, N, H, W, Cin)
+            orig = self._pool(orig, N, H, W, Cin)
+            h = self._conv(t, p["c0"], N, H, W, Cin, Cout)
+        elif b.up:
+            H, W = H * 2, W * 2
+            h = self._conv(t, p["c0"], N, H, W, Cin, Cout, mode=1)
+        else:
+            h = self._conv(t, p["c0"], N, H, W, Cin, Cout)
+        fo, fw = self._packed["aff_all"][2][name]
+        film = film_all[:, fo:fo + fw]  # fp32 [N, 2*Cout] = [scale | shift] (or [N, Cout]): this block's columns of the one affine GEMM (row stride = all blocks' columns)
+        if b.adaptive_scale:
+            t = self._gn(h, N, H * W, Cout, p["gn1"], film, True, eps)
+        else:  # silu(norm1(x + params)) (EDM.py:270): the statistics are those of the sum
+            hs = torch.empty_like(h)
+            hip.check(hip.lib().lfm_add_image_vec_f16(hip.ptr(h), hip.ptr(film), film_all.stride(0), hip.ptr(hs), N, H * W, Cout, hip.stream_ptr(h.device)),
+                      "lfm_add_image_vec_f16")
+            t = self._gn(hs, N, H * W, Cout, p["gn1"], None, True, eps)
+        if b.up:  # skip(orig): nearest 2x upsample of the input (conv_transpose with the all-ones 2x2 filter), then the 1x1 convolution where there is one
+            up = torch.empty(N * H * W, Cin, dtype=torch.float16, device=x.device)
+            hip.check(hip.lib().lfm_upsample2_f16(hip.ptr(orig), hip.ptr(up), N, H, W, Cin, hip.stream_ptr(x.device)), "lfm_upsample2_f16")
+            orig = up
+        if pair is not None:
+            skip = self._linear2(pair[0], pair[1], p["skip"])
+        else:
+            skip = orig if p["skip"] is None else self._linear(orig, p["skip"])
+        x = self._conv(t, p["c1"], N, H, W, Cout, Cout, resid=skip, scale=ss)
+        if b.num_heads:
+            T, ch = H * W, Cout // b.num_heads
+            t = self._gn(x, N, T, Cout, p["gn2"], None, False, eps)
+            qkv = self._linear(t, p["qkv"])
+            a = torch.empty(N * T, Cout, dtype=torch.float16, device=x.device)
+            hip.unet_attention(qkv, a, N, T, b.num_heads, ch)
+            x = self._linear(a, p["proj"], resid=x, scale=ss)
+        return x, H, W
+
+    # ---- forward ----------------------------------------------------------------------------------------------------------
+    @torch.no_grad()
+    def _forward(self, noise_labels, x, y, drop_half_label):
+        hip.require_gpu(x, self._what + ".forward")
+        if self.training:
+            raise hip.LfmHipError(f"the HIP {self._what} is inference-only: call .eval()")
+        if self._packed is None:
+            self._pack()
+        L, dev, P = hip.lib(), x.device, self._packed
+        x = x.contiguous().float()
+        N, Cin, H, W = x.shape
+        t = torch.as_tensor(noise_labels, device=dev).float().reshape(-1).contiguous()
+        if t.numel() not in (1, N):
+            raise ValueError(f"noise_labels must have 1 or {N} elements")
+        emb_f16 = self._embed(t, N, y, drop_half_label, dev)  # fp16 [N, E]: what every block's `affine` reads
+        film_all = hip.gemm_f16(emb_f16, P["aff_all"][0], P["aff_all"][1], epilogue=2)  # fp32 [N, all blocks' affine columns]
+        skips, h = [], None
+        for name, b in self.enc.items():
+            if isinstance(b, Conv2d):
+                wb = P["enc." + name]
+                h = torch.empty(N * H * W, b.out_channels, dtype=torch.float16, device=dev)
+                hip.check(L.lfm_conv3x3_in_f32(hip.ptr(x), hip.ptr(wb[0]), hip.ptr(wb[1]), hip.ptr(h), N, H, W, Cin, b.out_channels,
+                                               hip.stream_ptr(dev)), "lfm_conv3x3_in_f32")
+            else:
+                h, H, W = self._block("enc." + name, b, h, N, H, W, film_all)
+            skips.append((h, h.shape[1]))
+        for name, b in self.dec.items():
+            if not isinstance(b, UNetBlock):  # SongUNet's aux_norm / aux_conv: the output layers below
+                continue
+            if h.shape[1] != b.in_channels:
+                s, _ = skips.pop()
+                h = (h, s)  # torch.cat([x, skips.pop()], dim=1) (EDM.py:840-842): consumed in place by the block where its shape allows it
+            h, H, W = self._block("dec." + name, b, h, N, H, W, film_all)
+        t1 = self._gn(h, N, H * W, h.shape[1], P["gn_out"], None, True, self._out_modules()[0].eps)
+        out = torch.empty(N, self.out_channels, H, W, device=dev)
+        co = P["conv_out"]
+        hip.check(L.lfm_conv3x3_out_f32(hip.ptr(t1), hip.ptr(co[0]), hip.ptr(co[1]), hip.ptr(out), N, H, W, h.shape[1], self.out_channels,
+                                        hip.stream_ptr(dev)), "lfm_conv3x3_out_f32")
+        return out
+
+
+class DhariwalUNet(_EDMUNet):
+    _what = "DhariwalUNet"
+
     def __init__(self, img_resolution, in_channels, out_channels, label_dim=0, augment_dim=0, model_channels=192, channel_mult=(1, 2, 3, 4),
                  channel_mult_emb=4, num_blocks=3, attn_resolutions=(32, 16, 8), dropout=0.10, label_dropout=0, use_context=False):
         super().__init__()
@@ -138,211 +400,20 @@ class DhariwalUNet(nn.Module):
                 self.dec[f"{res}x{res}_block{idx}"] = UNetBlock(cin, cout, attention=(res in attn_resolutions), **bk)
         self.out_norm = GroupNorm(cout)
         self.out_conv = Conv2d(cout, out_channels, 3, **init_zero)
-        self._packed = None
-        self._scratch = None
-        self._gen = 0
+        self._init_state()
 
-    # ---- packing ------------------------------------------------------------------------------------------------------
-    def _apply(self, fn, *a, **k):
-        before = [(p.data_ptr(), p.dtype, p.device) for p in self.parameters()]
-        out = super()._apply(fn, *a, **k)
-        if before != [(p.data_ptr(), p.dtype, p.device) for p in self.parameters()]:  # only a real move / cast invalidates
-            self._packed = None
-            self._scratch = None
-            self._conv_ws = None
-            self._gen = getattr(self, "_gen", 0) + 1
-        return out
+    def _out_modules(self):
+        return self.out_norm, self.out_conv
 
-    def load_state_dict(self, *a, **k):
-        self._packed = None
-        self._gen = getattr(self, "_gen", 0) + 1
-        return super().load_state_dict(*a, **k)
-
-    @torch.no_grad()
-    def _pack(self):
-        dev = self.out_conv.weight.device
-        hip.require_gpu(self.out_conv.weight, "DhariwalUNet")
-        f32 = lambda t: t.detach().to(dev, torch.float32).contiguous()  # noqa: E731
-        f16 = lambda t: t.detach().to(dev, torch.float16).contiguous()  # noqa: E731
-
-        def conv3(m):
-            w = m.weight
-            if w.shape[1] % 64:
-                raise hip.LfmHipError(f"3x3 conv with Cin={w.shape[1]}: the implicit-GEMM path needs Cin % 64 == 0")
-            return f16(w.permute(0, 2, 3, 1).reshape(w.shape[0], -1)), f32(m.bias)
-
-        def conv1(m):
-            return f16(m.weight.reshape(m.weight.shape[0], -1)), f32(m.bias)
-
-        P = {}
-        for group in (self.enc, self.dec):
-            pre = "enc." if group is self.enc else "dec."
-            for name, b in group.items():
-                if isinstance(b, Conv2d):
-                    P[pre + name] = (f32(b.weight), f32(b.bias))
-                    continue
-                d = dict(gn0=(f32(b.norm0.weight), f32(b.norm0.bias)), c0=conv3(b.conv0), aff=(f16(b.affine.weight), f32(b.affine.bias)),
-                         gn1=(f32(b.norm1.weight), f32(b.norm1.bias)), c1=conv3(b.conv1),
-                         skip=conv1(b.skip) if (b.skip is not None and b.skip.weight is not None) else None)
-                if b.num_heads:
-                    C, ch = b.out_channels, b.out_channels // b.num_heads
-                    # reference row (head, c, which) -> our row (head, which, c)
-                    perm = torch.arange(3 * C).reshape(b.num_heads, ch, 3).permute(0, 2, 1).reshape(-1)
-                    d.update(gn2=(f32(b.norm2.weight), f32(b.norm2.bias)),
-                             qkv=(f16(b.qkv.weight.reshape(3 * C, C)[perm]), f32(b.qkv.bias[perm])), proj=conv1(b.proj))
-                P[pre + name] = d
-        # every block's `affine` projection of the embedding (EDM.py:263-265) in ONE GEMM per evaluation: weights stacked row-wise, a block reads its
-        # [scale | shift] columns of the result (28 launches of ~16 us each at the ffhq_adm size otherwise: profiles/r04_config6_kernel_stats.csv)
-        offs, ws_, bs_, off = {}, [], [], 0
-        for key, d in P.items():
-            if isinstance(d, dict):
-                offs[key] = (off, d["aff"][0].shape[0])
-                ws_.append(d["aff"][0])
-                bs_.append(d["aff"][1])
-                off += d["aff"][0].shape[0]
-        P["aff_all"] = (torch.cat(ws_, 0).contiguous(), torch.cat(bs_, 0).contiguous(), offs)
+    def _pack_mapping(self, P, f32, dev):
         P["time"] = (f32(self.map_layer0.weight), f32(self.map_layer0.bias), f32(self.map_layer1.weight), f32(self.map_layer1.bias))
         if self.map_label is not None:  # [label_dim + 1, E]: column lookup + one all-zero row for the dropped label
             P["label"] = torch.cat([f32(self.map_label.weight).t(), torch.zeros(1, self.emb_channels, device=dev)], 0).contiguous()
         else:
             P["label"] = None
-        P["gn_out"] = (f32(self.out_norm.weight), f32(self.out_norm.bias))
-        wo = self.out_conv.weight
-        if wo.shape[0] > 4:
-            raise hip.LfmHipError("output conv with more than 4 channels is not built")
-        w4 = torch.zeros(4, wo.shape[1], 3, 3, device=dev)
-        w4[: wo.shape[0]] = wo
-        b4 = torch.zeros(4, device=dev)
-        b4[: wo.shape[0]] = self.out_conv.bias
-        P["conv_out"] = (f16(w4.permute(0, 2, 3, 1).reshape(4, -1)), f32(b4))
-        self._packed = P
-        self._gen += 1
-        return P
 
-    # ---- ops --------------------------------------------------------------------------------------------------------------
-    def _gn(self, x, N, HW, C, gb, film, silu, eps=1e-5):
-        groups = min(32, C // 4)  # EDM GroupNorm (EDM.py:139-143)
-        y = torch.empty_like(x)
-        need = hip.lib().lfm_groupnorm_scratch_bytes(N, C)
-        if self._scratch is None or self._scratch.numel() < need or self._scratch.device != x.device:
-            self._scratch = torch.empty(max(need, 1 << 20), dtype=torch.uint8, device=x.device)
-            self._gen += 1
-        hip.check(hip.lib().lfm_groupnorm_f16(hip.ptr(x), hip.ptr(y), hip.ptr(gb[0]), hip.ptr(gb[1]), hip.ptr(film),
-                                              film.stride(0) if film is not None else 0, hip.ptr(self._scratch), N, HW, C, groups, eps,
-                                              1 if silu else 0, hip.stream_ptr(x.device)), "lfm_groupnorm_f16")
-        return y
-
-    def _conv(self, x, wb, N, H, W, Cin, Cout, mode=0, resid=None):
-        out = torch.empty(N * H * W, Cout, dtype=torch.float16, device=x.device)
-        L = hip.lib()
-        need = L.lfm_conv3x3_workspace_bytes(N, H, W, Cin, Cout)  # split-K slabs of the small-M / huge-K low-resolution levels
-        if need and (getattr(self, "_conv_ws", None) is None or self._conv_ws.numel() < need or self._conv_ws.device != x.device):
-            self._conv_ws = torch.empty(need, dtype=torch.uint8, device=x.device)
-            self._gen += 1
-        ws = self._conv_ws if need else None
-        hip.check(L.lfm_conv3x3_f16_ws(hip.ptr(x), hip.ptr(wb[0]), hip.ptr(wb[1]), hip.ptr(resid), hip.ptr(out), N, H, W, Cin, Cout, mode,
-                                       hip.ptr(ws), ws.numel() if ws is not None else 0, hip.stream_ptr(x.device)), "lfm_conv3x3_f16_ws")
-        return out
-
-    def _linear(self, x, wb, resid=None):
-        M, K = x.shape
-        Nout = wb[0].shape[0]
-        out = torch.empty(M, Nout, dtype=torch.float16, device=x.device)
-        hip.check(hip.lib().lfm_linear_f16(hip.ptr(x), x.stride(0), hip.ptr(wb[0]), wb[0].stride(0), hip.ptr(out), Nout, M, Nout, K,
-                                           hip.ptr(wb[1]), hip.ptr(resid), hip.stream_ptr(x.device)), "lfm_linear_f16")
-        return out
-
-    def _pool(self, x, N, Ho, Wo, C):
-        y = torch.empty(N * Ho * Wo, C, dtype=torch.float16, device=x.device)
-        hip.check(hip.lib().lfm_avgpool2_f16(hip.ptr(x), hip.ptr(y), N, Ho, Wo, C, hip.stream_ptr(x.device)), "lfm_avgpool2_f16")
-        return y
-
-    def _gn2(self, xa, xb, N, HW, gb, silu, eps=1e-5):
-        """GroupNorm of the channel concat [xa | xb] read in place (``torch.cat([x, skips.pop()], dim=1)``, EDM.py:840-842, is never materialised)."""
-        Ca, Cb = xa.shape[1], xb.shape[1]
-        y = torch.empty(xa.shape[0], Ca + Cb, dtype=torch.float16, device=xa.device)
-        need = hip.lib().lfm_groupnorm_scratch_bytes(N, Ca + Cb)
-        if self._scratch is None or self._scratch.numel() < need or self._scratch.device != xa.device:
-            self._scratch = torch.empty(max(need, 1 << 20), dtype=torch.uint8, device=xa.device)
-            self._gen += 1
-        hip.check(hip.lib().lfm_groupnorm2_f16(hip.ptr(xa), Ca, hip.ptr(xb), Cb, hip.ptr(y), hip.ptr(gb[0]), hip.ptr(gb[1]), None, 0, hip.ptr(self._scratch),
-                                               N, HW, min(32, (Ca + Cb) // 4), eps, 1 if silu else 0, hip.stream_ptr(xa.device)), "lfm_groupnorm2_f16")
-        return y
-
-    def _linear2(self, xa, xb, wb):
-        M, Nout = xa.shape[0], wb[0].shape[0]
-        out = torch.empty(M, Nout, dtype=torch.float16, device=xa.device)
-        hip.check(hip.lib().lfm_linear2_f16(hip.ptr(xa), xa.shape[1], hip.ptr(xb), xb.shape[1], hip.ptr(wb[0]), wb[0].stride(0), hip.ptr(out), Nout, M, Nout,
-                                            hip.ptr(wb[1]), None, hip.stream_ptr(xa.device)), "lfm_linear2_f16")
-        return out
-
-    def _cat(self, pair):
-        h, s = pair
-        cat = torch.empty(h.shape[0], h.shape[1] + s.shape[1], dtype=torch.float16, device=h.device)
-        hip.check(hip.lib().lfm_concat_channels_f16(hip.ptr(h), hip.ptr(s), hip.ptr(cat), h.shape[0], h.shape[1], s.shape[1], hip.stream_ptr(h.device)),
-                  "lfm_concat_channels_f16")
-        return cat
-
-    def _block(self, name, b, x, N, H, W, film_all):
-        """UNetBlock.forward (EDM.py:258-292).  Returns (out, H, W).  `x` may be the pair (h, skip) of a decoder block: its channel concat is then read in place
-        by the block's two consumers -- the first GroupNorm and the 1x1 skip convolution -- as in the origin-ADM UNet (round 6; the concat kernel was 2 % of an
-        evaluation at the ffhq_adm size)."""
-        p = self._packed[name]
-        Cin, Cout = b.in_channels, b.out_channels
-        pair = None
-        if isinstance(x, tuple):
-            if b.down or b.up or p["skip"] is None or x[0].shape[1] % 64 or x[1].shape[1] % 8:
-                x = self._cat(x)  # resampled / identity-skip inputs need the tensor itself
-            else:
-                pair = x
-        orig = x
-        t = self._gn2(pair[0], pair[1], N, H * W, p["gn0"], True) if pair is not None else self._gn(x, N, H * W, Cin, p["gn0"], None, True)
-        if b.down:
-            H, W = H // 2, W // 2
-            t = self._pool(t, N, H, W, Cin)
-            orig = self._pool(orig, N, H, W, Cin)
-            h = self._conv(t, p["c0"], N, H, W, Cin, Cout)
-        elif b.up:
-            H, W = H * 2, W * 2
-            h = self._conv(t, p["c0"], N, H, W, Cin, Cout, mode=1)
-        else:
-            h = self._conv(t, p["c0"], N, H, W, Cin, Cout)
-        fo, fw = self._packed["aff_all"][2][name]
-        film = film_all[:, fo:fo + fw]  # fp32 [N, 2*Cout] = [scale | shift]: this block's columns of the one affine GEMM (row stride = all blocks' columns)
-        t = self._gn(h, N, H * W, Cout, p["gn1"], film, True)
-        if b.up:  # skip(orig) with kernel 0 = nearest 2x upsample of the input (conv_transpose with the all-ones 2x2 filter)
-            up = torch.empty(N * H * W, Cin, dtype=torch.float16, device=x.device)
-            hip.check(hip.lib().lfm_upsample2_f16(hip.ptr(orig), hip.ptr(up), N, H, W, Cin, hip.stream_ptr(x.device)), "lfm_upsample2_f16")
-            orig = up
-        if pair is not None:
-            skip = self._linear2(pair[0], pair[1], p["skip"])
-        else:
-            skip = orig if p["skip"] is None else self._linear(orig, p["skip"])
-        x = self._conv(t, p["c1"], N, H, W, Cout, Cout, resid=skip)
-        if b.num_heads:
-            T, ch = H * W, Cout // b.num_heads
-            t = self._gn(x, N, T, Cout, p["gn2"], None, False)
-            qkv = self._linear(t, p["qkv"])
-            a = torch.empty(N * T, Cout, dtype=torch.float16, device=x.device)
-            hip.unet_attention(qkv, a, N, T, b.num_heads, ch)
-            x = self._linear(a, p["proj"], resid=x)
-        return x, H, W
-
-    # ---- forward ----------------------------------------------------------------------------------------------------------
-    @torch.no_grad()
-    def _forward(self, noise_labels, x, y, drop_half_label):
-        hip.require_gpu(x, "DhariwalUNet.forward")
-        if self.training:
-            raise hip.LfmHipError("the HIP DhariwalUNet is inference-only: call .eval()")
-        if self._packed is None:
-            self._pack()
-        L, dev, P = hip.lib(), x.device, self._packed
-        x = x.contiguous().float()
-        N, Cin, H, W = x.shape
-        t = torch.as_tensor(noise_labels, device=dev).float().reshape(-1).contiguous()
-        if t.numel() not in (1, N):
-            raise ValueError(f"noise_labels must have 1 or {N} elements")
-        E, F = self.emb_channels, self.model_channels
+    def _embed(self, t, N, y, drop_half_label, dev):
+        P, E, F = self._packed, self.emb_channels, self.model_channels
         yy = None
         if P["label"] is not None and y is not None:
             yy = y.to(dev, torch.long).clone()
@@ -355,35 +426,23 @@ class DhariwalUNet(nn.Module):
         emb_silu = torch.empty(N, E, device=dev, dtype=torch.float16)
         h1 = torch.empty(N, E, device=dev)
         tw = P["time"]
-        hip.check(L.lfm_time_embed(hip.ptr(t), t.numel(), hip.ptr(tw[0]), hip.ptr(tw[1]), hip.ptr(tw[2]), hip.ptr(tw[3]),
-                                   hip.ptr(P["label"] if yy is not None else None), hip.ptr(yy), n_labels, hip.ptr(h1), hip.ptr(emb),
-                                   hip.ptr(emb_silu), N, F, E, hip.stream_ptr(dev)), "lfm_time_embed")
-        film_all = hip.gemm_f16(emb_silu, P["aff_all"][0], P["aff_all"][1], epilogue=2)  # fp32 [N, sum of 2*Cout over the blocks]
-        skips, h = [], None
-        for name, b in self.enc.items():
-            if isinstance(b, Conv2d):
-                wb = P["enc." + name]
-                h = torch.empty(N * H * W, b.out_channels, dtype=torch.float16, device=dev)
-                hip.check(L.lfm_conv3x3_in_f32(hip.ptr(x), hip.ptr(wb[0]), hip.ptr(wb[1]), hip.ptr(h), N, H, W, Cin, b.out_channels,
-                                               hip.stream_ptr(dev)), "lfm_conv3x3_in_f32")
-            else:
-                h, H, W = self._block("enc." + name, b, h, N, H, W, film_all)
-            skips.append((h, h.shape[1]))
-        for name, b in self.dec.items():
-            if h.shape[1] != b.in_channels:
-                s, _ = skips.pop()
-                h = (h, s)  # torch.cat([x, skips.pop()], dim=1) (EDM.py:840-842): consumed in place by the block where its shape allows it
-            h, H, W = self._block("dec." + name, b, h, N, H, W, film_all)
-        t1 = self._gn(h, N, H * W, h.shape[1], P["gn_out"], None, True)
-        out = torch.empty(N, self.out_channels, H, W, device=dev)
-        co = P["conv_out"]
-        hip.check(L.lfm_conv3x3_out_f32(hip.ptr(t1), hip.ptr(co[0]), hip.ptr(co[1]), hip.ptr(out), N, H, W, h.shape[1], self.out_channels,
-                                        hip.stream_ptr(dev)), "lfm_conv3x3_out_f32")
-        return out
+        hip.check(hip.lib().lfm_time_embed(hip.ptr(t), t.numel(), hip.ptr(tw[0]), hip.ptr(tw[1]), hip.ptr(tw[2]), hip.ptr(tw[3]),
+                                           hip.ptr(P["label"] if yy is not None else None), hip.ptr(yy), n_labels, hip.ptr(h1), hip.ptr(emb),
+                                           hip.ptr(emb_silu), N, F, E, hip.stream_ptr(dev)), "lfm_time_embed")
+        return emb_silu
 
     def forward(self, noise_labels, x, y=None, augment_labels=None, drop_half_label=False, **kwargs):
         """v = model(t, x, y) (EDM.py:808-845)."""
         return self._forward(noise_labels, x, y, drop_half_label)
+
+    def _cfg_coef(self, cfg_scale, dev):
+        """[s, 1 - s] on the device, made once per (scale, device): a stream capture refuses the host-to-device copy of a fresh one (the captured solver
+        warms up before it captures, so the buffer exists by then).  Twins share the table: it is read-only."""
+        table = self.__dict__.setdefault("_cfg_coefs", {})
+        key = (float(cfg_scale), dev)
+        if key not in table:
+            table[key] = torch.tensor([cfg_scale, 1.0 - cfg_scale], device=dev)  # uncond + s*(cond - uncond)
+        return table[key]
 
     def forward_with_cfg(self, noise_labels, x, y=None, augment_labels=None, cfg_scale=1.0, **kwargs):
         """EDM.py:847-861: x[:N/2] evaluated with labels y (first half) and with the label dropped (second half)."""
@@ -392,18 +451,133 @@ class DhariwalUNet(nn.Module):
         xin[n2:].copy_(xin[:n2])  # combined = cat([half, half])
         out = self._forward(noise_labels, xin, y, True)
         cond, uncond = out[:n2], out[n2:]
-        coef = torch.tensor([cfg_scale, 1.0 - cfg_scale], device=x.device)  # uncond + s*(cond - uncond)
+        coef = self._cfg_coef(cfg_scale, x.device)
         res = torch.empty_like(out)
         hip.lincomb(res[:n2], None, [cond, uncond], coef)
         hip.lincomb(res[n2:], None, [cond, uncond], coef)
         return res
 
 
+class SongUNet(_EDMUNet):
+    """DDPM++ (reference EDM.py:532-706 as ``get_edm_network`` builds it for ``model_type == "ddpm++"``, :886-905)."""
+
+    _what = "SongUNet"
+
+    def __init__(self, img_resolution, in_channels, out_channels, label_dim=0, augment_dim=0, model_channels=128, channel_mult=(1, 2, 2, 2),
+                 channel_mult_emb=4, num_blocks=4, attn_resolutions=(16,), dropout=0.10, label_dropout=0, embedding_type="positional",
+                 channel_mult_noise=1, encoder_type="standard", decoder_type="standard", resample_filter=(1, 1)):
+        super().__init__()
+        for what, got, built in (("embedding_type", embedding_type, "positional"), ("channel_mult_noise", channel_mult_noise, 1),
+                                 ("encoder_type", encoder_type, "standard"), ("decoder_type", decoder_type, "standard"),
+                                 ("resample_filter", tuple(resample_filter), (1, 1)), ("augment_dim", augment_dim, 0)):
+            if got != built:
+                raise NotImplementedError(f"SongUNet: {what}={got!r} is not built; only the ddpm++ settings are ({what}={built!r})")
+        widths = [model_channels * m for m in channel_mult]
+        if any(w % 64 for w in widths):
+            raise NotImplementedError(f"SongUNet: channel counts {widths} must all be multiples of 64 (the implicit-GEMM convolutions' contract)")
+        attn_widths = [w for level, w in enumerate(widths) if (img_resolution >> level) in attn_resolutions] + [widths[-1]]  # in0 always attends
+        if max(attn_widths) > 256:
+            raise NotImplementedError(f"SongUNet: attention is one head over the whole width, and {max(attn_widths)} channels exceed the 256 per head "
+                                      "that the streamed attention kernel serves")
+        if in_channels > 16 or out_channels > 4:
+            raise NotImplementedError("SongUNet: at most 16 input and 4 output channels are built (the fp32 boundary convolutions)")
+        self.label_dim, self.label_dropout = label_dim, label_dropout
+        self.img_resolution, self.in_channels, self.out_channels, self.model_channels = img_resolution, in_channels, out_channels, model_channels
+        emb_channels = model_channels * channel_mult_emb
+        noise_channels = model_channels * channel_mult_noise
+        self.emb_channels = emb_channels
+        init = dict(init_mode="xavier_uniform")
+        init_zero = dict(init_mode="xavier_uniform", init_weight=1e-5)
+        init_attn = dict(init_mode="xavier_uniform", init_weight=np.sqrt(0.2))
+        bk = dict(emb_channels=emb_channels, num_heads=1, dropout=dropout, skip_scale=np.sqrt(0.5), eps=1e-6, resample_proj=True, adaptive_scale=False,
+                  init=init, init_zero=init_zero, init_attn=init_attn, scaled_epilogue=True)
+        self.map_label = Linear(label_dim, noise_channels, **init) if label_dim else None
+        self.map_layer0 = Linear(noise_channels, emb_channels, **init)
+        self.map_layer1 = Linear(emb_channels, emb_channels, **init)
+        self.enc = nn.ModuleDict()
+        cout = in_channels
+        for level, mult in enumerate(channel_mult):
+            res = img_resolution >> level
+            if level == 0:
+                cin, cout = cout, model_channels
+                self.enc[f"{res}x{res}_conv"] = Conv2d(cin, cout, 3, **init)
+            else:
+                self.enc[f"{res}x{res}_down"] = UNetBlock(cout, cout, down=True, **bk)
+            for idx in range(num_blocks):
+                cin, cout = cout, model_channels * mult
+                self.enc[f"{res}x{res}_block{idx}"] = UNetBlock(cin, cout, attention=(res in attn_resolutions), **bk)
+        skips = [b.out_channels for b in self.enc.values()]
+        self.dec = nn.ModuleDict()
+        for level, mult in reversed(list(enumerate(channel_mult))):
+            res = img_resolution >> level
+            if level == len(channel_mult) - 1:
+                self.dec[f"{res}x{res}_in0"] = UNetBlock(cout, cout, attention=True, **bk)
+                self.dec[f"{res}x{res}_in1"] = UNetBlock(cout, cout, **bk)
+            else:
+                self.dec[f"{res}x{res}_up"] = UNetBlock(cout, cout, up=True, **bk)
+            for idx in range(num_blocks + 1):
+                cin = cout + skips.pop()
+                cout = model_channels * mult
+                self.dec[f"{res}x{res}_block{idx}"] = UNetBlock(cin, cout, attention=(idx == num_blocks and res in attn_resolutions), **bk)
+            if level == 0:
+                self.dec[f"{res}x{res}_aux_norm"] = GroupNorm(cout, eps=1e-6)
+                self.dec[f"{res}x{res}_aux_conv"] = Conv2d(cout, out_channels, 3, **init_zero)
+        self._init_state()
+
+    @torch.no_grad()
+    def redraw_small_(self, seed=4321, std=0.02):
+        """Synthetic-weight runs (``--random_weights``): the "zero" convolutions are initialised at weight 1e-5, not 0, so the drivers' re-draw of all-zero
+        tensors passes them by and the model would output ~6e-6.  Re-draw every tensor that small from seeded N(0, std), in name order."""
+        g = torch.Generator().manual_seed(seed)
+        for _, p in sorted(self.named_parameters()):
+            if p.numel() and bool(p.any()) and float(p.abs().max()) < 1e-4:
+                p.copy_(torch.randn(p.shape, generator=g) * std)
+        self._packed = None
+        self._gen += 1
+        return self
+
+    def _out_modules(self):
+        r = self.img_resolution
+        return self.dec[f"{r}x{r}_aux_norm"], self.dec[f"{r}x{r}_aux_conv"]
+
+    def _pack_mapping(self, P, f32, dev):
+        P["time"] = (f32(self.map_layer0.weight), f32(self.map_layer0.bias), f32(self.map_layer1.weight), f32(self.map_layer1.bias))
+        # map_label(one_hot(y) * sqrt(L)) = sqrt(L) * W[:, y] + b: rows of W^T, the scale and the bias go to the kernel as they are (all fp32)
+        P["label"] = (f32(self.map_label.weight).t().contiguous(), f32(self.map_label.bias)) if self.map_label is not None else None
+
+    def _embed(self, t, N, y, drop_half_label, dev):
+        P, E, F = self._packed, self.emb_channels, self.model_channels
+        lab, yy = None, None
+        if P["label"] is not None and y is not None:  # y=None on a conditional model: the label term is left out (the label_dim=0 model on the same weights)
+            lab, yy = P["label"], y.to(dev, torch.long).contiguous()
+            hip.check_labels(yy, self.label_dim, "SongUNet")
+        emb = torch.empty(N, E, device=dev)
+        emb_f16 = torch.empty(N, E, device=dev, dtype=torch.float16)
+        h1 = torch.empty(N, E, device=dev)
+        tw = P["time"]
+        hip.check(hip.lib().lfm_song_embed(hip.ptr(t), t.numel(), hip.ptr(tw[0]), hip.ptr(tw[1]), hip.ptr(tw[2]), hip.ptr(tw[3]),
+                                           hip.ptr(lab[0] if lab else None), hip.ptr(lab[1] if lab else None), float(np.sqrt(max(self.label_dim, 1))),
+                                           hip.ptr(yy), self.label_dim, hip.ptr(h1), hip.ptr(emb), hip.ptr(emb_f16), N, F, E, hip.stream_ptr(dev)),
+                  "lfm_song_embed")
+        return emb_f16
+
+    def forward(self, noise_labels, x, y=None, augment_labels=None, **kwargs):
+        """v = model(t, x, y) (EDM.py:663-706)."""
+        return self._forward(noise_labels, x, y, False)
+
+
 def get_edm_network(config):
-    """Reference models/EDM.py:864-939: only the ``adm`` branch is on the sampling path of the reference's test_args."""
+    """Reference models/EDM.py:864-939: ``adm`` -> DhariwalUNet, ``ddpm++`` -> SongUNet, each with the reference's argument list."""
+    common = dict(img_resolution=config.image_size // config.f, in_channels=config.num_in_channels, out_channels=config.num_out_channels,
+                  label_dim=config.label_dim, augment_dim=0, model_channels=config.nf, channel_mult=config.ch_mult, channel_mult_emb=4,
+                  num_blocks=config.num_res_blocks, attn_resolutions=config.attn_resolutions, dropout=config.dropout,
+                  label_dropout=config.label_dropout)
+    if config.model_type == "ddpm++":
+        m = SongUNet(embedding_type="positional", channel_mult_noise=1, encoder_type="standard", decoder_type="standard", resample_filter=[1, 1], **common)
+        if getattr(config, "random_weights", False):
+            m.redraw_small_()
+        return m
     if config.model_type != "adm":
-        raise NotImplementedError(f"model_type {config.model_type!r}: SongUNet (ncsn++/ddpm++) and adm_context are out of scope (SURVEY.md §2)")
-    return DhariwalUNet(img_resolution=config.image_size // config.f, in_channels=config.num_in_channels, out_channels=config.num_out_channels,
-                        label_dim=config.label_dim, augment_dim=0, model_channels=config.nf, channel_mult=config.ch_mult, channel_mult_emb=4,
-                        num_blocks=config.num_res_blocks, attn_resolutions=config.attn_resolutions, dropout=config.dropout,
-                        label_dropout=config.label_dropout)
+        raise NotImplementedError(f"model_type {config.model_type!r}: ncsn++ (the reference reads config.num_blocks, which is not a flag) and adm_context "
+                                  "are out of scope (SURVEY.md §2)")
+    return DhariwalUNet(**common)

@@ -380,11 +380,11 @@ def torchdiffeq_euler_grid(step_size, device=None):
 # ============================================================================ fused, graph-captured fixed grid
 def fused_fixed_grid_available(model, x):
     from .models.DiT import DiT
-    from .models.EDM import DhariwalUNet
+    from .models.EDM import DhariwalUNet, SongUNet
     from .models.unet import UNetModel
 
     inner = getattr(model, "model", None) if type(model).__name__ == "WrapperCondFlow" else model  # downstream-task conditioning wrapper
-    return isinstance(inner, (DiT, UNetModel, DhariwalUNet)) and x.is_cuda and not inner.training
+    return isinstance(inner, (DiT, UNetModel, DhariwalUNet, SongUNet)) and x.is_cuda and not inner.training
 
 
 class GraphedFixedGrid:
@@ -396,13 +396,16 @@ class GraphedFixedGrid:
 
     def __init__(self, model, batch, y=None, cfg_scale=1.0, use_cfg=False, graph=True, resolution=None):
         from .models.DiT import DiT
+        from .models.EDM import DhariwalUNet
 
         self.is_dit = isinstance(model, DiT)
         dev = next(model.parameters()).device
         C = model.in_channels
         R = model.img_resolution if self.is_dit else (resolution or model.image_size)
-        if use_cfg and not self.is_dit:
-            raise NotImplementedError("classifier-free guidance needs forward_with_cfg, which the origin-ADM UNet does not have")
+        # guidance: fused into the DiT forward; DhariwalUNet.forward_with_cfg (host-sequenced, captured like its forward); nothing else has one
+        self.host_cfg = bool(use_cfg) and isinstance(model, DhariwalUNet)
+        if use_cfg and not self.is_dit and not self.host_cfg:
+            raise NotImplementedError(f"classifier-free guidance needs forward_with_cfg, which {type(model).__name__} does not have")
         self.model, self.batch, self.dev = model, batch, dev
         self.y = None if y is None else y.to(dev, torch.long).clone()  # own the buffer the captured graph reads (never alias the caller's)
         self.use_cfg, self.cfg_scale = bool(use_cfg), float(cfg_scale)
@@ -486,7 +489,10 @@ class GraphedFixedGrid:
     def _velocity(self, t, x, out=None, grid_offset=None):
         if self.is_dit:
             return self.model._run(t, x, self.y, self.use_cfg, self.cfg_scale, out=out, cond=None if grid_offset is None else self._cond(grid_offset))
-        v = self.model(t, x, self.y)  # host-sequenced UNet: its launches are captured like any others
+        if self.host_cfg:  # the labels are read from self.y at replay: _fused refills that buffer, the graph holds its address
+            v = self.model.forward_with_cfg(t, x, self.y, cfg_scale=self.cfg_scale)
+        else:
+            v = self.model(t, x, self.y)  # host-sequenced UNet: its launches are captured like any others
         if out is not None:
             out.copy_(v)
             return out
@@ -590,7 +596,7 @@ def concurrency_twin(module):
     """A second handle on the SAME weights with its own device scratch (workspace, captured solver graphs), so that two batches can be in flight on two
     HIP streams: a sampling job's batches are independent (test_flow_latent_ddp.py:116-146), and two chip-filling evaluations launched side by side run
     ~5 % faster than one after the other -- while one stream's workgroups sit in their HBM-bound GEMM epilogues, the other's are in their MFMA main loops
-    (profiles/r04_two_batches_in_flight.txt).  Works for the DiT family, the VAE and the two UNets (modules whose scratch is `_ws` / `_scratch` / `_conv_ws` / `_fused_solvers`).  Take the twin AFTER
+    (profiles/r04_two_batches_in_flight.txt).  Works for the DiT family, the VAE and the UNets (modules whose scratch is `_ws` / `_scratch` / `_conv_ws` / `_fused_solvers`).  Take the twin AFTER
     the weights are final: it shares the packed weight buffers of the original and does not follow a later load_state_dict.  The stream a twin (or the
     original) is then driven on must first wait for the stream its setup ran on (packing, set_grid's conditioning tables): `s.wait_stream(current)`."""
     import copy
