@@ -13,6 +13,7 @@ import torch
 import torch.nn as nn
 
 from .. import hip
+from ._unet_host import PackedModule
 
 
 # --------------------------------------------------------------------------- parameter containers
@@ -87,10 +88,13 @@ def get_2d_sincos_pos_embed(embed_dim, grid_size):
 
 
 # --------------------------------------------------------------------------- the model
-class DiT(nn.Module):
+class DiT(PackedModule):
+    _scratch_attrs = ("_ws",)  # any real parameter move / cast drops it with the packed fp16 operands, and a reload drops those (_unet_host.py)
+
     def __init__(self, img_resolution=32, patch_size=2, in_channels=4, hidden_size=1152, depth=28, num_heads=16,
                  mlp_ratio=4.0, label_dropout=0.1, num_classes=1000, learn_sigma=False):
         super().__init__()
+        self._init_host_state()
         if learn_sigma:
             raise NotImplementedError("learn_sigma=True is never used by the LFM sampling path")
         # what the HIP kernels are built for (csrc/dit.hip::check_shape) -- refuse at construction, not at the first forward
@@ -120,9 +124,6 @@ class DiT(nn.Module):
         self.blocks = nn.ModuleList([DiTBlock(hidden_size, num_heads, mlp_ratio=mlp_ratio) for _ in range(depth)])
         self.final_layer = FinalLayer(hidden_size, patch_size, self.out_channels)
         self.initialize_weights()
-        self._packed = None
-        self._ws = None
-        self._gen = 0  # bumped whenever device buffers a captured graph may point to are replaced
 
     # ---- init: same distributions as reference DiT.py:193-228 (incl. the adaLN-Zero / zero output layer)
     def initialize_weights(self):
@@ -145,23 +146,6 @@ class DiT(nn.Module):
         nn.init.zeros_(self.final_layer.adaLN_modulation[-1].bias)
         nn.init.zeros_(self.final_layer.linear.weight)
         nn.init.zeros_(self.final_layer.linear.bias)
-
-    # ---- any parameter movement / reload invalidates the packed fp16 operands
-    def _apply(self, fn, *a, **k):
-        # invalidate the packed operands / workspace / captured graphs only if a parameter really moved or changed dtype
-        # (NFECount(model).to(device) on an already-placed model must not re-pack 0.9 GB of weights per call)
-        before = [(p.data_ptr(), p.dtype, p.device) for p in self.parameters()]
-        out = super()._apply(fn, *a, **k)
-        if before != [(p.data_ptr(), p.dtype, p.device) for p in self.parameters()]:
-            self._packed = None
-            self._gen = getattr(self, "_gen", 0) + 1
-            self._ws = None
-        return out
-
-    def load_state_dict(self, *a, **k):
-        self._packed = None
-        self._gen = getattr(self, "_gen", 0) + 1
-        return super().load_state_dict(*a, **k)
 
     def shape_struct(self):
         return hip.DitShape(self.depth, self.hidden_size, self.num_heads, self.patch_size, self.in_channels, self.img_resolution,

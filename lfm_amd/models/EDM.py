@@ -31,6 +31,7 @@ import torch
 import torch.nn as nn
 
 from .. import hip
+from ._unet_host import HipUNetHost, f16, f32, pack_conv1, pack_conv3, pack_gn, stack_rows
 
 
 def _weight_init(shape, mode, fan_in, fan_out):  # EDM.py:27-36
@@ -104,171 +105,46 @@ class UNetBlock(nn.Module):  # EDM.py:188-292 (parameter container)
             self.proj = Conv2d(out_channels, out_channels, 1, **init_zero)
 
 
-class _EDMUNet(nn.Module):
-    """What DhariwalUNet and SongUNet share: weight packing, device scratch, the host-sequenced UNetBlock and the encoder / decoder walk.  A subclass builds
-    the parameter tree and provides ``_out_modules`` (the output GroupNorm and convolution), ``_pack_mapping`` and ``_embed`` (its mapping network)."""
+class _EDMUNet(HipUNetHost):
+    """What DhariwalUNet and SongUNet share on top of the UNets' host layer (``_unet_host.py``): what is packed, the host-sequenced UNetBlock and the encoder /
+    decoder walk.  A subclass builds the parameter tree and provides ``_out_modules`` (the output GroupNorm and convolution), ``_pack_mapping`` and ``_embed``
+    (its mapping network)."""
 
     _what = "EDM UNet"
 
-    def _init_state(self):
-        self._packed = None
-        self._scratch = None
-        self._gen = 0
-
     # ---- packing ------------------------------------------------------------------------------------------------------
-    def _apply(self, fn, *a, **k):
-        before = [(p.data_ptr(), p.dtype, p.device) for p in self.parameters()]
-        out = super()._apply(fn, *a, **k)
-        if before != [(p.data_ptr(), p.dtype, p.device) for p in self.parameters()]:  # only a real move / cast invalidates
-            self._packed = None
-            self._scratch = None
-            self._conv_ws = None
-            self._gen = getattr(self, "_gen", 0) + 1
-        return out
-
-    def load_state_dict(self, *a, **k):
-        self._packed = None
-        self._gen = getattr(self, "_gen", 0) + 1
-        return super().load_state_dict(*a, **k)
-
-    @torch.no_grad()
-    def _pack(self):
+    def _pack_blocks(self, P, dev):
         out_norm, out_conv = self._out_modules()
-        dev = out_conv.weight.device
-        hip.require_gpu(out_conv.weight, self._what)
-        f32 = lambda t: t.detach().to(dev, torch.float32).contiguous()  # noqa: E731
-        f16 = lambda t: t.detach().to(dev, torch.float16).contiguous()  # noqa: E731
-
-        def conv3(m):
-            w = m.weight
-            if w.shape[1] % 64:
-                raise hip.LfmHipError(f"3x3 conv with Cin={w.shape[1]}: the implicit-GEMM path needs Cin % 64 == 0")
-            return f16(w.permute(0, 2, 3, 1).reshape(w.shape[0], -1)), f32(m.bias)
-
-        def conv1(m):
-            return f16(m.weight.reshape(m.weight.shape[0], -1)), f32(m.bias)
-
-        P = {}
+        aff = {}
         for group in (self.enc, self.dec):
             pre = "enc." if group is self.enc else "dec."
             for name, b in group.items():
-                if b is out_norm or b is out_conv:  # SongUNet keeps its output layers inside `dec` (aux_norm / aux_conv): packed below
+                if b is out_norm or b is out_conv:  # SongUNet keeps its output layers inside `dec` (aux_norm / aux_conv): packed by the host layer
                     continue
                 if isinstance(b, Conv2d):
-                    P[pre + name] = (f32(b.weight), f32(b.bias))
+                    P[pre + name] = (f32(b.weight, dev), f32(b.bias, dev))
                     continue
-                d = dict(gn0=(f32(b.norm0.weight), f32(b.norm0.bias)), c0=conv3(b.conv0), aff=(f16(b.affine.weight), f32(b.affine.bias)),
-                         gn1=(f32(b.norm1.weight), f32(b.norm1.bias)), c1=conv3(b.conv1),
-                         skip=conv1(b.skip) if (b.skip is not None and b.skip.weight is not None) else None)
+                d = dict(gn0=pack_gn(b.norm0, dev), c0=pack_conv3(b.conv0, dev), gn1=pack_gn(b.norm1, dev), c1=pack_conv3(b.conv1, dev),
+                         skip=pack_conv1(b.skip, dev) if (b.skip is not None and b.skip.weight is not None) else None)
                 if b.num_heads:
                     C, ch = b.out_channels, b.out_channels // b.num_heads
                     # reference row (head, c, which) -> our row (head, which, c)
                     perm = torch.arange(3 * C).reshape(b.num_heads, ch, 3).permute(0, 2, 1).reshape(-1)
-                    d.update(gn2=(f32(b.norm2.weight), f32(b.norm2.bias)),
-                             qkv=(f16(b.qkv.weight.reshape(3 * C, C)[perm]), f32(b.qkv.bias[perm])), proj=conv1(b.proj))
+                    d.update(gn_attn=pack_gn(b.norm2, dev), qkv=(f16(b.qkv.weight.reshape(3 * C, C)[perm], dev), f32(b.qkv.bias[perm], dev)),
+                             proj=pack_conv1(b.proj, dev))
                 P[pre + name] = d
-        # every block's `affine` projection of the embedding (EDM.py:263-265) in ONE GEMM per evaluation: weights stacked row-wise, a block reads its
-        # [scale | shift] columns of the result (28 launches of ~16 us each at the ffhq_adm size otherwise: profiles/r04_config6_kernel_stats.csv)
-        offs, ws_, bs_, off = {}, [], [], 0
-        for key, d in P.items():
-            if isinstance(d, dict):
-                offs[key] = (off, d["aff"][0].shape[0])
-                ws_.append(d["aff"][0])
-                bs_.append(d["aff"][1])
-                off += d["aff"][0].shape[0]
-        P["aff_all"] = (torch.cat(ws_, 0).contiguous(), torch.cat(bs_, 0).contiguous(), offs)
-        self._pack_mapping(P, f32, dev)
-        P["gn_out"] = (f32(out_norm.weight), f32(out_norm.bias))
-        wo = out_conv.weight
-        if wo.shape[0] > 4:
-            raise hip.LfmHipError("output conv with more than 4 channels is not built")
-        w4 = torch.zeros(4, wo.shape[1], 3, 3, device=dev)
-        w4[: wo.shape[0]] = wo
-        b4 = torch.zeros(4, device=dev)
-        b4[: wo.shape[0]] = out_conv.bias
-        P["conv_out"] = (f16(w4.permute(0, 2, 3, 1).reshape(4, -1)), f32(b4))
-        self._packed = P
-        self._gen += 1
-        return P
+                aff[pre + name] = (f16(b.affine.weight, dev), f32(b.affine.bias, dev))
+        P["aff_all"] = stack_rows(aff)  # every block's `affine` projection of the embedding (EDM.py:263-265)
+        self._pack_mapping(P, dev)
 
-    # ---- ops --------------------------------------------------------------------------------------------------------------
-    def _gn(self, x, N, HW, C, gb, film, silu, eps=1e-5):
-        groups = min(32, C // 4)  # EDM GroupNorm (EDM.py:139-143)
-        y = torch.empty_like(x)
-        need = hip.lib().lfm_groupnorm_scratch_bytes(N, C)
-        if self._scratch is None or self._scratch.numel() < need or self._scratch.device != x.device:
-            self._scratch = torch.empty(max(need, 1 << 20), dtype=torch.uint8, device=x.device)
-            self._gen += 1
-        hip.check(hip.lib().lfm_groupnorm_f16(hip.ptr(x), hip.ptr(y), hip.ptr(gb[0]), hip.ptr(gb[1]), hip.ptr(film),
-                                              film.stride(0) if film is not None else 0, hip.ptr(self._scratch), N, HW, C, groups, eps,
-                                              1 if silu else 0, hip.stream_ptr(x.device)), "lfm_groupnorm_f16")
-        return y
-
-    def _conv(self, x, wb, N, H, W, Cin, Cout, mode=0, resid=None, scale=1.0):
-        out = torch.empty(N * H * W, Cout, dtype=torch.float16, device=x.device)
-        L = hip.lib()
-        need = L.lfm_conv3x3_workspace_bytes(N, H, W, Cin, Cout)  # split-K slabs of the small-M / huge-K low-resolution levels
-        if need and (getattr(self, "_conv_ws", None) is None or self._conv_ws.numel() < need or self._conv_ws.device != x.device):
-            self._conv_ws = torch.empty(need, dtype=torch.uint8, device=x.device)
-            self._gen += 1
-        ws = self._conv_ws if need else None
-        if scale != 1.0:  # (acc + bias + resid) * skip_scale in the epilogue (SongUNet)
-            hip.check(L.lfm_conv3x3_scaled_f16_ws(hip.ptr(x), hip.ptr(wb[0]), hip.ptr(wb[1]), hip.ptr(resid), scale, hip.ptr(out), N, H, W, Cin, Cout, mode,
-                                                  hip.ptr(ws), ws.numel() if ws is not None else 0, hip.stream_ptr(x.device)), "lfm_conv3x3_scaled_f16_ws")
-            return out
-        hip.check(L.lfm_conv3x3_f16_ws(hip.ptr(x), hip.ptr(wb[0]), hip.ptr(wb[1]), hip.ptr(resid), hip.ptr(out), N, H, W, Cin, Cout, mode,
-                                       hip.ptr(ws), ws.numel() if ws is not None else 0, hip.stream_ptr(x.device)), "lfm_conv3x3_f16_ws")
-        return out
-
-    def _linear(self, x, wb, resid=None, scale=1.0):
-        M, K = x.shape
-        Nout = wb[0].shape[0]
-        out = torch.empty(M, Nout, dtype=torch.float16, device=x.device)
-        if scale != 1.0:
-            hip.check(hip.lib().lfm_linear_scaled_f16(hip.ptr(x), x.stride(0), hip.ptr(wb[0]), wb[0].stride(0), hip.ptr(out), Nout, M, Nout, K,
-                                                      hip.ptr(wb[1]), hip.ptr(resid), scale, hip.stream_ptr(x.device)), "lfm_linear_scaled_f16")
-            return out
-        hip.check(hip.lib().lfm_linear_f16(hip.ptr(x), x.stride(0), hip.ptr(wb[0]), wb[0].stride(0), hip.ptr(out), Nout, M, Nout, K,
-                                           hip.ptr(wb[1]), hip.ptr(resid), hip.stream_ptr(x.device)), "lfm_linear_f16")
-        return out
-
-    def _pool(self, x, N, Ho, Wo, C):
-        y = torch.empty(N * Ho * Wo, C, dtype=torch.float16, device=x.device)
-        hip.check(hip.lib().lfm_avgpool2_f16(hip.ptr(x), hip.ptr(y), N, Ho, Wo, C, hip.stream_ptr(x.device)), "lfm_avgpool2_f16")
-        return y
-
-    def _gn2(self, xa, xb, N, HW, gb, silu, eps=1e-5):
-        """GroupNorm of the channel concat [xa | xb] read in place (``torch.cat([x, skips.pop()], dim=1)``, EDM.py:840-842, is never materialised)."""
-        Ca, Cb = xa.shape[1], xb.shape[1]
-        y = torch.empty(xa.shape[0], Ca + Cb, dtype=torch.float16, device=xa.device)
-        need = hip.lib().lfm_groupnorm_scratch_bytes(N, Ca + Cb)
-        if self._scratch is None or self._scratch.numel() < need or self._scratch.device != xa.device:
-            self._scratch = torch.empty(max(need, 1 << 20), dtype=torch.uint8, device=xa.device)
-            self._gen += 1
-        hip.check(hip.lib().lfm_groupnorm2_f16(hip.ptr(xa), Ca, hip.ptr(xb), Cb, hip.ptr(y), hip.ptr(gb[0]), hip.ptr(gb[1]), None, 0, hip.ptr(self._scratch),
-                                               N, HW, min(32, (Ca + Cb) // 4), eps, 1 if silu else 0, hip.stream_ptr(xa.device)), "lfm_groupnorm2_f16")
-        return y
-
-    def _linear2(self, xa, xb, wb):
-        M, Nout = xa.shape[0], wb[0].shape[0]
-        out = torch.empty(M, Nout, dtype=torch.float16, device=xa.device)
-        hip.check(hip.lib().lfm_linear2_f16(hip.ptr(xa), xa.shape[1], hip.ptr(xb), xb.shape[1], hip.ptr(wb[0]), wb[0].stride(0), hip.ptr(out), Nout, M, Nout,
-                                            hip.ptr(wb[1]), None, hip.stream_ptr(xa.device)), "lfm_linear2_f16")
-        return out
-
-    def _cat(self, pair):
-        h, s = pair
-        cat = torch.empty(h.shape[0], h.shape[1] + s.shape[1], dtype=torch.float16, device=h.device)
-        hip.check(hip.lib().lfm_concat_channels_f16(hip.ptr(h), hip.ptr(s), hip.ptr(cat), h.shape[0], h.shape[1], s.shape[1], hip.stream_ptr(h.device)),
-                  "lfm_concat_channels_f16")
-        return cat
-
+    # ---- blocks -----------------------------------------------------------------------------------------------------------
     def _block(self, name, b, x, N, H, W, film_all):
         """UNetBlock.forward (EDM.py:258-292).  Returns (out, H, W).  `x` may be the pair (h, skip) of a decoder block: its channel concat is then read in place
         by the block's two consumers -- the first GroupNorm and the 1x1 skip convolution -- as in the origin-ADM UNet (round 6; the concat kernel was 2 % of an
         evaluation at the ffhq_adm size)."""
         p = self._packed[name]
         Cin, Cout, eps, ss = b.in_channels, b.out_channels, b.eps, b.skip_scale
+        g0, g1 = b.norm0.num_groups, b.norm1.num_groups  # min(32, C // 4) (EDM.py:139-143)
         pair = None
         if isinstance(x, tuple):
             if b.down or b.up or p["skip"] is None or x[0].shape[1] % 64 or x[1].shape[1] % 8:
@@ -276,83 +152,60 @@ class _EDMUNet(nn.Module):
             else:
                 pair = x
         orig = x
-        t = self._gn2(pair[0], pair[1], N, H * W, p["gn0"], True, eps) if pair is not None else self._gn(x, N, H * W, Cin, p["gn0"], None, True, eps)
-        if b.down:
-            H, W = H // 2, W // 2
-            t = self._pool(t, N, H, W, Cin)
-            orig = self._pool(orig, N, H, W, Cin)
-            h = self._conv(t, p["c0"], N, H, W, Cin, Cout)
-        elif b.up:
-            H, W = H * 2, W * 2
-            h = self._conv(t, p["c0"], N, H, W, Cin, Cout, mode=1)
+        if pair is not None:
+            t = self._gn2(pair[0], pair[1], N, H * W, p["gn0"], None, True, g0, eps)
         else:
-            h = self._conv(t, p["c0"], N, H, W, Cin, Cout)
+            t = self._gn(x, N, H * W, Cin, p["gn0"], None, True, g0, eps)
+        if b.down:  # Conv2d(down=True): a 2x2 mean, then the 3x3 convolution (EDM.py:96-125), on both branches
+            H, W = H // 2, W // 2
+            t = self._resample(t, N, H, W, Cin, False)
+            orig = self._resample(orig, N, H, W, Cin, False)
+        elif b.up:  # Conv2d(up=True): nearest 2x fused into the convolution
+            H, W = H * 2, W * 2
+        h = self._conv(t, p["c0"], N, H, W, Cin, Cout, mode=1 if b.up else 0)
         fo, fw = self._packed["aff_all"][2][name]
         film = film_all[:, fo:fo + fw]  # fp32 [N, 2*Cout] = [scale | shift] (or [N, Cout]): this block's columns of the one affine GEMM (row stride = all blocks' columns)
         if b.adaptive_scale:
-            t = self._gn(h, N, H * W, Cout, p["gn1"], film, True, eps)
+            t = self._gn(h, N, H * W, Cout, p["gn1"], film, True, g1, eps)
         else:  # silu(norm1(x + params)) (EDM.py:270): the statistics are those of the sum
-            hs = torch.empty_like(h)
-            hip.check(hip.lib().lfm_add_image_vec_f16(hip.ptr(h), hip.ptr(film), film_all.stride(0), hip.ptr(hs), N, H * W, Cout, hip.stream_ptr(h.device)),
-                      "lfm_add_image_vec_f16")
-            t = self._gn(hs, N, H * W, Cout, p["gn1"], None, True, eps)
+            hs = self._add_image_vec(h, film, N, H * W, Cout)
+            t = self._gn(hs, N, H * W, Cout, p["gn1"], None, True, g1, eps)
         if b.up:  # skip(orig): nearest 2x upsample of the input (conv_transpose with the all-ones 2x2 filter), then the 1x1 convolution where there is one
-            up = torch.empty(N * H * W, Cin, dtype=torch.float16, device=x.device)
-            hip.check(hip.lib().lfm_upsample2_f16(hip.ptr(orig), hip.ptr(up), N, H, W, Cin, hip.stream_ptr(x.device)), "lfm_upsample2_f16")
-            orig = up
+            orig = self._resample(orig, N, H, W, Cin, True)
         if pair is not None:
             skip = self._linear2(pair[0], pair[1], p["skip"])
         else:
             skip = orig if p["skip"] is None else self._linear(orig, p["skip"])
-        x = self._conv(t, p["c1"], N, H, W, Cout, Cout, resid=skip, scale=ss)
+        x = self._conv(t, p["c1"], N, H, W, Cout, Cout, resid=skip, scale=ss)  # (acc + bias + resid) * skip_scale in the epilogue
         if b.num_heads:
-            T, ch = H * W, Cout // b.num_heads
-            t = self._gn(x, N, T, Cout, p["gn2"], None, False, eps)
-            qkv = self._linear(t, p["qkv"])
-            a = torch.empty(N * T, Cout, dtype=torch.float16, device=x.device)
-            hip.unet_attention(qkv, a, N, T, b.num_heads, ch)
-            x = self._linear(a, p["proj"], resid=x, scale=ss)
+            del t  # dead from here on: its block of a captured graph's memory pool goes to the attention's tensors
+            x = self._attention(x, p, N, H * W, b.num_heads, Cout, b.norm2.num_groups, eps, ss)
         return x, H, W
 
     # ---- forward ----------------------------------------------------------------------------------------------------------
     @torch.no_grad()
     def _forward(self, noise_labels, x, y, drop_half_label):
-        hip.require_gpu(x, self._what + ".forward")
-        if self.training:
-            raise hip.LfmHipError(f"the HIP {self._what} is inference-only: call .eval()")
-        if self._packed is None:
-            self._pack()
-        L, dev, P = hip.lib(), x.device, self._packed
-        x = x.contiguous().float()
+        x, t = self._prologue(noise_labels, x, "noise_labels")
+        P = self._packed
         N, Cin, H, W = x.shape
-        t = torch.as_tensor(noise_labels, device=dev).float().reshape(-1).contiguous()
-        if t.numel() not in (1, N):
-            raise ValueError(f"noise_labels must have 1 or {N} elements")
-        emb_f16 = self._embed(t, N, y, drop_half_label, dev)  # fp16 [N, E]: what every block's `affine` reads
+        emb_f16 = self._embed(t, N, y, drop_half_label, x.device)  # fp16 [N, E]: what every block's `affine` reads
         film_all = hip.gemm_f16(emb_f16, P["aff_all"][0], P["aff_all"][1], epilogue=2)  # fp32 [N, all blocks' affine columns]
         skips, h = [], None
         for name, b in self.enc.items():
             if isinstance(b, Conv2d):
-                wb = P["enc." + name]
-                h = torch.empty(N * H * W, b.out_channels, dtype=torch.float16, device=dev)
-                hip.check(L.lfm_conv3x3_in_f32(hip.ptr(x), hip.ptr(wb[0]), hip.ptr(wb[1]), hip.ptr(h), N, H, W, Cin, b.out_channels,
-                                               hip.stream_ptr(dev)), "lfm_conv3x3_in_f32")
+                h = self._conv_in(x, P["enc." + name], N, H, W, Cin)
             else:
                 h, H, W = self._block("enc." + name, b, h, N, H, W, film_all)
-            skips.append((h, h.shape[1]))
+            skips.append(h)
         for name, b in self.dec.items():
             if not isinstance(b, UNetBlock):  # SongUNet's aux_norm / aux_conv: the output layers below
                 continue
             if h.shape[1] != b.in_channels:
-                s, _ = skips.pop()
+                s = skips.pop()
                 h = (h, s)  # torch.cat([x, skips.pop()], dim=1) (EDM.py:840-842): consumed in place by the block where its shape allows it
             h, H, W = self._block("dec." + name, b, h, N, H, W, film_all)
-        t1 = self._gn(h, N, H * W, h.shape[1], P["gn_out"], None, True, self._out_modules()[0].eps)
-        out = torch.empty(N, self.out_channels, H, W, device=dev)
-        co = P["conv_out"]
-        hip.check(L.lfm_conv3x3_out_f32(hip.ptr(t1), hip.ptr(co[0]), hip.ptr(co[1]), hip.ptr(out), N, H, W, h.shape[1], self.out_channels,
-                                        hip.stream_ptr(dev)), "lfm_conv3x3_out_f32")
-        return out
+        out_norm = self._out_modules()[0]
+        return self._out(h, N, H, W, out_norm.num_groups, out_norm.eps)
 
 
 class DhariwalUNet(_EDMUNet):
@@ -361,6 +214,7 @@ class DhariwalUNet(_EDMUNet):
     def __init__(self, img_resolution, in_channels, out_channels, label_dim=0, augment_dim=0, model_channels=192, channel_mult=(1, 2, 3, 4),
                  channel_mult_emb=4, num_blocks=3, attn_resolutions=(32, 16, 8), dropout=0.10, label_dropout=0, use_context=False):
         super().__init__()
+        self._init_host_state()
         if use_context or augment_dim:
             raise NotImplementedError("use_context / augment_dim are not used by the sampling path and are not built")
         self.label_dim, self.label_dropout = label_dim, label_dropout
@@ -400,36 +254,24 @@ class DhariwalUNet(_EDMUNet):
                 self.dec[f"{res}x{res}_block{idx}"] = UNetBlock(cin, cout, attention=(res in attn_resolutions), **bk)
         self.out_norm = GroupNorm(cout)
         self.out_conv = Conv2d(cout, out_channels, 3, **init_zero)
-        self._init_state()
 
     def _out_modules(self):
         return self.out_norm, self.out_conv
 
-    def _pack_mapping(self, P, f32, dev):
-        P["time"] = (f32(self.map_layer0.weight), f32(self.map_layer0.bias), f32(self.map_layer1.weight), f32(self.map_layer1.bias))
+    def _pack_mapping(self, P, dev):
+        P["time"] = tuple(f32(t, dev) for t in (self.map_layer0.weight, self.map_layer0.bias, self.map_layer1.weight, self.map_layer1.bias))
         if self.map_label is not None:  # [label_dim + 1, E]: column lookup + one all-zero row for the dropped label
-            P["label"] = torch.cat([f32(self.map_label.weight).t(), torch.zeros(1, self.emb_channels, device=dev)], 0).contiguous()
+            P["label"] = torch.cat([f32(self.map_label.weight, dev).t(), torch.zeros(1, self.emb_channels, device=dev)], 0).contiguous()
         else:
             P["label"] = None
 
     def _embed(self, t, N, y, drop_half_label, dev):
-        P, E, F = self._packed, self.emb_channels, self.model_channels
         yy = None
-        if P["label"] is not None and y is not None:
+        if self._packed["label"] is not None and y is not None:
             yy = y.to(dev, torch.long).clone()
             if drop_half_label:
                 yy[N // 2:] = self.label_dim  # the all-zero row (EDM.py:825-826)
-        n_labels = 0 if P["label"] is None else int(P["label"].shape[0])
-        if yy is not None:
-            hip.check_labels(yy, n_labels, "DhariwalUNet")
-        emb = torch.empty(N, E, device=dev)
-        emb_silu = torch.empty(N, E, device=dev, dtype=torch.float16)
-        h1 = torch.empty(N, E, device=dev)
-        tw = P["time"]
-        hip.check(hip.lib().lfm_time_embed(hip.ptr(t), t.numel(), hip.ptr(tw[0]), hip.ptr(tw[1]), hip.ptr(tw[2]), hip.ptr(tw[3]),
-                                           hip.ptr(P["label"] if yy is not None else None), hip.ptr(yy), n_labels, hip.ptr(h1), hip.ptr(emb),
-                                           hip.ptr(emb_silu), N, F, E, hip.stream_ptr(dev)), "lfm_time_embed")
-        return emb_silu
+        return self._time_embed(t, N, yy, self.model_channels, self.emb_channels)
 
     def forward(self, noise_labels, x, y=None, augment_labels=None, drop_half_label=False, **kwargs):
         """v = model(t, x, y) (EDM.py:808-845)."""
@@ -467,6 +309,7 @@ class SongUNet(_EDMUNet):
                  channel_mult_emb=4, num_blocks=4, attn_resolutions=(16,), dropout=0.10, label_dropout=0, embedding_type="positional",
                  channel_mult_noise=1, encoder_type="standard", decoder_type="standard", resample_filter=(1, 1)):
         super().__init__()
+        self._init_host_state()
         for what, got, built in (("embedding_type", embedding_type, "positional"), ("channel_mult_noise", channel_mult_noise, 1),
                                  ("encoder_type", encoder_type, "standard"), ("decoder_type", decoder_type, "standard"),
                                  ("resample_filter", tuple(resample_filter), (1, 1)), ("augment_dim", augment_dim, 0)):
@@ -522,7 +365,6 @@ class SongUNet(_EDMUNet):
             if level == 0:
                 self.dec[f"{res}x{res}_aux_norm"] = GroupNorm(cout, eps=1e-6)
                 self.dec[f"{res}x{res}_aux_conv"] = Conv2d(cout, out_channels, 3, **init_zero)
-        self._init_state()
 
     @torch.no_grad()
     def redraw_small_(self, seed=4321, std=0.02):
@@ -540,10 +382,10 @@ class SongUNet(_EDMUNet):
         r = self.img_resolution
         return self.dec[f"{r}x{r}_aux_norm"], self.dec[f"{r}x{r}_aux_conv"]
 
-    def _pack_mapping(self, P, f32, dev):
-        P["time"] = (f32(self.map_layer0.weight), f32(self.map_layer0.bias), f32(self.map_layer1.weight), f32(self.map_layer1.bias))
+    def _pack_mapping(self, P, dev):
+        P["time"] = tuple(f32(t, dev) for t in (self.map_layer0.weight, self.map_layer0.bias, self.map_layer1.weight, self.map_layer1.bias))
         # map_label(one_hot(y) * sqrt(L)) = sqrt(L) * W[:, y] + b: rows of W^T, the scale and the bias go to the kernel as they are (all fp32)
-        P["label"] = (f32(self.map_label.weight).t().contiguous(), f32(self.map_label.bias)) if self.map_label is not None else None
+        P["label"] = (f32(self.map_label.weight, dev).t().contiguous(), f32(self.map_label.bias, dev)) if self.map_label is not None else None
 
     def _embed(self, t, N, y, drop_half_label, dev):
         P, E, F = self._packed, self.emb_channels, self.model_channels

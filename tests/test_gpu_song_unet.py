@@ -247,24 +247,6 @@ def test_song_wide_one_256_channel_head_on_the_streamed_kernel(golden_dir):
     assert max(errs.values()) < 3e-3, errs
 
 
-def test_song_unet_twin_on_a_second_stream_is_bit_identical(tiny):
-    from lfm_amd.solvers import concurrency_twin
-
-    rec, m = tiny
-    dev = torch.device("cuda:0")
-    x, y, t = rec["x"].to(dev), rec["y"].to(dev), rec["tN"].to(dev)
-    want = m(t, x, y).clone()
-    twin = concurrency_twin(m)
-    assert twin._packed is m._packed and twin._scratch is None
-    s = torch.cuda.Stream(dev)
-    s.wait_stream(torch.cuda.current_stream(dev))
-    with torch.cuda.stream(s):
-        got = twin(t, x, y)
-    s.synchronize()
-    assert torch.equal(got, want)
-    assert twin._scratch is not None and twin._scratch is not m._scratch
-
-
 # ------------------------------------------------------------------------------------------------ guided adm on the fixed grids
 @pytest.fixture(scope="module")
 def guided(golden_dir):

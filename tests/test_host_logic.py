@@ -307,6 +307,71 @@ def test_apply_without_a_move_keeps_the_packed_operands():
     assert m._packed is None and m._gen == gen + 1
 
 
+def _tiny_unet(which, golden_dir):
+    """The three UNet backbones at their smallest: two levels of 64 / 128 channels on a 16x16 grid (a few million parameters)."""
+    import json
+
+    import song_cases as sc
+    from lfm_amd.models.EDM import DhariwalUNet, SongUNet
+    from lfm_amd.models.unet import UNetModel
+
+    if which == "SongUNet":
+        return SongUNet(**sc.TINY_CFG).eval()
+    rec = json.load(open(os.path.join(golden_dir, "unet_state_keys.json")))[which]
+    return (DhariwalUNet if which == "DhariwalUNet" else UNetModel)(**rec["cfg"]).eval()
+
+
+_UNETS = ["UNetModel", "DhariwalUNet", "SongUNet"]
+
+
+@pytest.mark.parametrize("which", _UNETS)
+def test_unet_host_state_is_invalidated_by_a_real_move_or_a_reload_only(golden_dir, which):
+    """The UNets' shared host layer (lfm_amd/models/_unet_host.py): every backbone has the whole host state from construction on; .to(same device) /
+    .float() on fp32 weights keep it; a real cast drops the packed operands and both scratch buffers and bumps _gen once; load_state_dict drops the
+    packed operands and bumps _gen once."""
+    m = _tiny_unet(which, golden_dir)
+    assert all(name in m.__dict__ for name in ("_packed", "_scratch", "_conv_ws", "_gen"))
+    assert m._packed is None and m._scratch is None and m._conv_ws is None
+    scratch, conv_ws = torch.zeros(8, dtype=torch.uint8), torch.zeros(4, dtype=torch.uint8)
+    m._packed, m._scratch, m._conv_ws, gen = "sentinel", scratch, conv_ws, m._gen
+    m.to("cpu")
+    m.float()
+    assert m._packed == "sentinel" and m._scratch is scratch and m._conv_ws is conv_ws and m._gen == gen
+    m.double()
+    assert m._packed is None and m._scratch is None and m._conv_ws is None and m._gen == gen + 1
+    m._packed = "sentinel"
+    m.load_state_dict(m.state_dict())
+    assert m._packed is None and m._gen == gen + 2
+    assert len(list(m.buffers())) == sum(k.endswith("resample_filter") for k in m.state_dict())  # the host layer registers nothing
+
+
+@pytest.mark.parametrize("which", _UNETS)
+def test_concurrency_twin_of_a_unet_shares_weights_not_scratch(golden_dir, which):
+    from lfm_amd.solvers import concurrency_twin
+
+    m = _tiny_unet(which, golden_dir)
+    scratch, conv_ws = torch.zeros(8, dtype=torch.uint8), torch.zeros(4, dtype=torch.uint8)
+    m._scratch, m._conv_ws = scratch, conv_ws
+    t = concurrency_twin(m)
+    assert t is not m and type(t) is type(m)
+    assert all(a is b for a, b in zip(m.parameters(), t.parameters()))
+    assert t._scratch is None and t._conv_ws is None
+    t._scratch, t._conv_ws = torch.zeros(2, dtype=torch.uint8), torch.zeros(2, dtype=torch.uint8)
+    assert m._scratch is scratch and m._conv_ws is conv_ws
+    t._gen += 5
+    assert m._gen != t._gen
+
+
+@pytest.mark.parametrize("which", ["UNetModel", "UNetModel_updown", "DhariwalUNet"])
+def test_unet_state_dict_keys_are_the_recorded_ones(golden_dir, which):
+    """tests/golden/unet_state_keys.json: the sorted state-dict keys of tiny models, recorded before the backbones were moved onto the shared host layer (a base
+    class must add no parameter, buffer or submodule).  SongUNet's list is in song_tiny.pt (test_song_unet_host.py)."""
+    import json
+
+    rec = json.load(open(os.path.join(golden_dir, "unet_state_keys.json")))[which]
+    assert sorted(_tiny_unet(which, golden_dir).state_dict().keys()) == rec["keys"]
+
+
 # ----------------------------------------------------------------------------- training pair (train_flow_latent.py:143-155)
 def test_flow_matching_pair_defines_the_sampled_ode():
     from lfm_amd.train_flow_latent import SIGMA_MIN, flow_matching_loss, flow_matching_pair
