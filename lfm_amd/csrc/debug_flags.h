@@ -21,7 +21,7 @@ constexpr int LFM_DBG_GEMM_ALWAYS_V4 = 8192;     // chip-filling shapes always t
 constexpr int LFM_DBG_GEMM_SPLITK128 = 65536;    // deep small-map split-K on 128x128 slices instead of 256x256 ones; shares LN_BPERMUTE
 constexpr int LFM_DBG_GEMM_ABL_SHIFT = 21;       // measurement build, lfm_gemm_f16 GELU epilogue: main-loop ablation of kernel 5 (1..7; 8 | 7 = variant 8) and of
 constexpr int LFM_DBG_GEMM_ABL_MASK = 15;        //   kernel 6 (1..4, 8 = DMA placement); shares TRACE_COL, DIT_PATCH_ROUND1, VAE_SEPARATE_STATS, QKV_PER_ITEM, CONV_IMPLICIT_GEMM, CONV_HALO_SMALL
-constexpr int LFM_DBG_GEMM_OPT_SHIFT = 25;       // measurement build, lfm_gemm_f16 GELU epilogue: OPT variants 1..3 of kernel 5, variant 1 of kernel 6;
+constexpr int LFM_DBG_GEMM_OPT_SHIFT = 25;       // measurement build, lfm_gemm_f16 GELU epilogue: OPT variant 1 of kernels 5 and 6 (2, 3: LFM_ERR_ARG on 5);
 constexpr int LFM_DBG_GEMM_OPT_MASK = 3;         //   shares ATT_MODE, QKV_NO_KEY_LOOP, QKV_TWO_KTILES
 
 // ---- TRACE: the s_memtime-stamped build of kernel 5 (measurement build, gemm256h_kernel.h)

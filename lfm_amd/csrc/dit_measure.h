@@ -216,8 +216,7 @@ static int gemm_f16_launch(const ASrcRowMajor& a, const half_t* W, long ldw, int
     if (K % G256Q_BK == 0 && (sel == 5 || sel == 6) && opt) {  // OPT variants
       if (sel == 6) return launch_gemm256w_tn<ASrcRowMajor, Epi, 0, 0, 1>(a, W, ldw, M, N, K, e, st);
       if (opt == 1) return launch_gemm256h_tn<ASrcRowMajor, Epi, false, 0, 1>(a, W, ldw, M, N, K, e, st);
-      if (opt == 2) return launch_gemm256h_tn<ASrcRowMajor, Epi, false, 0, 2>(a, W, ldw, M, N, K, e, st);
-      return launch_gemm256h_tn<ASrcRowMajor, Epi, false, 0, 3>(a, W, ldw, M, N, K, e, st);
+      return LFM_ERR_ARG;  // (kernel 5 has no further OPT variant: bit 1 went with round 4's rejected DMA-before-reads placement)
     }
     if (K % G256Q_BK == 0 && sel == 6 && abl) {  // kernel 6: main-loop ablations 1..4, DMA placement 8
       switch (abl) {

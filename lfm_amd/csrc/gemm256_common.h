@@ -1,6 +1,6 @@
 // Shared pieces of the 256-row MFMA GEMM kernels (256x128 "two workgroups per CU", gemm256n_kernel.h; 256x256 quadrant-phased on
 // v_mfma_f32_16x16x32_f16, gemm256h_kernel.h): tile order, epilogue traits, the LDS-transposed row-major epilogue for the 32x32x16 accumulator
-// map, the barrier macro, the LDS image constants of the quadrant-phased ring.
+// map, the barrier macro.  (The quadrant-phased operand ring and its K loop: gemm256q_ring.h.)
 // History (DESIGN.md section 3 keeps the measurements): the first two 256x256 generations -- a four-stage ping-pong ring of 32-deep K-tiles
 // (round 1) and its quadrant-phased successor on 32x32x16 MFMAs with 64-deep K-tiles (round 1 / 2) -- were superseded by the 16x16x32 kernel
 // and removed in round 3; no reference shape dispatched to them (every K on the path is a multiple of 64).
@@ -278,24 +278,7 @@ __device__ __forceinline__ void g256_epilogue(f32x16 (&acc)[4][2], char* smem, E
     __builtin_amdgcn_sched_barrier(0);  \
   } while (0)
 
-// ---- LDS image of the quadrant-phased 256x256 kernel: 64-deep K-tiles = 128-byte rows, staged in four 16-KiB pieces (A.sub0 / A.sub1 = rows
-// {0..63} / {64..127} of both groups' 128-row halves, B.sub0 / B.sub1 = columns {0..31} / {32..63} of every wave's 64-column block); two K-tiles
-// = 128 KiB.  Chunk c of row r sits at c ^ ((r >> 1) & 7), applied to the DMA source address and to the fragment read.
-#define G256Q_BK 64
-#define G256Q_PIECE 16384
-#define G256Q_SLOT_A0 0
-#define G256Q_SLOT_B0 (1 * G256Q_PIECE)
-#define G256Q_SLOT_B1 (2 * G256Q_PIECE)
-#define G256Q_SLOT_A1 (3 * G256Q_PIECE)
-#define G256Q_BUF_BYTES (4 * G256Q_PIECE)
-#define G256Q_LDS_BYTES (2 * G256Q_BUF_BYTES)
-
 // Measurement only (lfm_gemm_select flag TRACE_GEMM with kernel 5): s_memtime stamps of the epilogue, parked here and read back with lfm_gemm_trace_read().
 // One copy per translation unit; dit.hip's is read back.
 #define G256Q_TRACE_MAX 2048
 static __device__ unsigned long long g256q_trace[2][G256Q_TRACE_MAX];
-
-template <int V>
-struct g256q_ic {
-  static constexpr int value = V;
-};

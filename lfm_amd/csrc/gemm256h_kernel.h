@@ -5,7 +5,8 @@
 // stream that v1-v4 use sustains 1660 (both 2450 on zeros): the small shape moves 20 % fewer register-file bytes per flop (4
 // accumulator registers per instruction instead of 16).  Energy per flop is the lever under a power cap, so this generation keeps
 // v3's structure unchanged -- LDS image, piece-granular LDS-DMA ring, quadrant phases, one barrier per phase, counted waits,
-// ping-pong wave groups, tile order (gemm256q_kernel.h) -- and changes only the instruction and what follows from its fragment maps:
+// ping-pong wave groups (all of it in gemm256q_ring.h, with the phase table and the hazard rule), tile order -- and changes
+// only the instruction and what follows from its fragment maps:
 //
 //   operand fragments  lane l holds 8 consecutive k of row (l & 15) at k-group (l >> 4): one ds_read_b128 of logical chunk
 //                      4*ks + (l >> 4) of a 128-byte LDS row (ks = 0, 1 per 64-deep K-tile); the same 12 / 4 / 8 / 0 reads per phase as v3;
@@ -14,6 +15,7 @@
 //   epilogue           the same LDS-transposed row-major hand-over (shared Epi interface), with the scratch filled from the new map.
 #pragma once
 #include "gemm256n_kernel.h"
+#include "gemm256q_ring.h"
 
 typedef float f32x4_t __attribute__((ext_vector_type(4)));
 
@@ -253,12 +255,7 @@ __device__ __forceinline__ void g256h_epilogue_mod(f32x4_t (&acc)[8][4], char* s
 // Consumer prologue of the folded LayerNorm-modulate: (a, b) = (rstd, -rstd (mu - c)) of the tile's 256 rows -> LDS rs[256][2] (above the operand
 // ring); tile column 0 publishes mu[m] as the next producer's centring constant.  Two halves around the K loop's first DMAs: the loads are issued
 // BEFORE them (vmcnt returns in order: a load issued behind the twelve prologue DMAs would make its consumer wait for all of them -- measured
-// +1.3 us per tile), the arithmetic runs while they fly.
-#define G256H_MAX_PARTS 5  // residual width <= 1280
-struct G256hRowStatRegs {
-  f32x2 p[G256H_MAX_PARTS];
-  float c;
-};
+// +1.3 us per tile), the arithmetic (g256h_rowstat, gemm256q_ring.h) runs while they fly.
 template <class Epi>
 __device__ __forceinline__ G256hRowStatRegs g256h_rowstat_load(const Epi& epi, int m0, int M) {
   G256hRowStatRegs r;
@@ -275,16 +272,8 @@ template <class Epi>
 __device__ __forceinline__ void g256h_rowstat_finish(Epi& epi, const G256hRowStatRegs& r, char* smem, int m0, int M, int tile_n) {
   float* rs = (float*)(smem + G256Q_LDS_BYTES);
   if (threadIdx.x < 256) {
-    float sx = 0.f, sq = 0.f;
-#pragma unroll
-    for (int t = 0; t < G256H_MAX_PARTS; ++t) {  // fixed order
-      sx += r.p[t].x;
-      sq += r.p[t].y;
-    }
-    const float mu = sx * epi.st.inv_n, dl = mu - r.c;
-    const float var = fmaxf(sq * epi.st.inv_n - dl * dl, 0.f);
-    const float rstd = rsqrtf(var + epi.st.eps);
-    *(f32x2*)(rs + 2 * threadIdx.x) = (f32x2){rstd, -rstd * dl};
+    float mu;
+    *(f32x2*)(rs + 2 * threadIdx.x) = g256h_rowstat(r, epi.st.inv_n, epi.st.eps, mu);
     if (tile_n == 0 && m0 + (int)threadIdx.x < M) epi.st.cen_out[m0 + threadIdx.x] = mu;
   }
   epi.rs = rs;
@@ -441,12 +430,9 @@ __device__ __forceinline__ void g256h_epilogue(f32x4_t (&acc)[8][4], char* smem,
 // 3 = neither (the bare MFMA stream + barriers), 4 = static priority (s_setprio 1 for the second wave group, no per-phase flips),
 // 5 = 3 without the per-phase barriers (the bare MFMA stream), 6 = 3 with one barrier per K-tile instead of per phase,
 // 7 = 5 with the accumulators pinned (inline-asm MFMA, D = C), 8 = the full kernel with pinned accumulators
-// OPT (round 4): bit 0 = LDS-DMAs through buffer resources (ASrc::buffer_form sources; byte offsets < 2^31, checked at launch), bit 1 = a LOAD part
-// issues its first LDS-DMA BEFORE its fragment reads and the second one after them (a wave's VMEM instructions serialise at ~110 cycles each --
-// tools/ubench/ldsdma_rate.hip, one wave: 105-116 cycles per 1-KiB instruction in every addressing form -- so the second of two back-to-back issues
-// waits for the first; the reads in between cover that wait).
-// Measured (tools/dma_opt_probe.py, profiles/r04_dma_opt_probe.txt; bit-identical results): bit 0 -0.6 .. -2.1 us on the main loops of both 256x256 kernels
-// (252 -> 218 VGPRs in this one) = the default; bit 1 +1.5 .. +3 us = rejected.
+// OPT (round 4): bit 0 = LDS-DMAs through buffer resources (ASrc::buffer_form sources; byte offsets < 2^31, checked at launch).
+// Measured (tools/dma_opt_probe.py, profiles/r04_dma_opt_probe.txt; bit-identical results): -0.6 .. -2.1 us on the main loops of both 256x256 kernels
+// (252 -> 218 VGPRs in this one) = the default.  (Bit 1 of that round -- a LOAD part's first LDS-DMA ahead of its fragment reads -- cost +1.5 .. +3 us and is gone.)
 // OPT bit 2 (round 6): the pieces' LDS-DMAs placed against the LOAD parts' fragment reads (none | B1 | A1 | A0 B0 instead of B1 | A1 | A0 | B0; counted vmcnt 4 4 4 6):
 // -0.2 % per DiT-L/2 forward, bit-identical (profiles/r06_dma_phase_balance.txt) -- not the default.
 #ifndef G256H_DEFAULT_OPT
@@ -458,6 +444,9 @@ __global__ __launch_bounds__(512) void gemm256h_tn_kernel(ASrc asrc, const half_
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int g = wave >> 2, wn = wave & 3;
+  static_assert((OPT & 2) == 0, "OPT bit 1 (a LOAD part's first LDS-DMA ahead of its fragment reads, round 4: rejected) no longer exists");
+  constexpr bool NO_DMA = ABL == 1 || ABL == 3 || (ABL >= 5 && ABL <= 7);  // (no LDS-DMA after the prologue)
+  constexpr bool READS = !(ABL == 2 || ABL == 3 || (ABL >= 5 && ABL <= 7));
 
   int tile_m, tile_n;
   g256_tile_order(blockIdx.x, gridDim.x, tiles_n, dbg, tile_m, tile_n);
@@ -468,10 +457,10 @@ __global__ __launch_bounds__(512) void gemm256h_tn_kernel(ASrc asrc, const half_
   asrc.init(bz, bsA);
   W += (long)bz * bsW;
 
-  // ---- DMA sources: identical to v3 (piece = 128 local rows x 128 B; thread tid stages chunks tid and 512 + tid)
+  // ---- DMA sources.  A.sub_s local row lr -> tile row (lr >> 6) * 128 + s * 64 + (lr & 63), B.sub_s local row lr -> tile column (lr >> 5) * 64 + s * 32 + (lr & 31)
   typename ASrc::Row arow[2][2];  // [sub][pass]
   const half_t* wrow[2][2];
-  const int cswz = ((tid & 7) ^ ((tid >> 4) & 7)) * 8;
+  const int cswz = g256q_cswz(tid);
 #pragma unroll
   for (int s = 0; s < 2; ++s)
 #pragma unroll
@@ -481,7 +470,7 @@ __global__ __launch_bounds__(512) void gemm256h_tn_kernel(ASrc asrc, const half_
       wrow[s][p] = W + (long)(n < N ? n : N - 1) * ldw + cswz;
     }
   const int nk = K / G256Q_BK;
-  const int dma_off = wave * 1024;
+  const int dma_off = g256q_dma_off(wave);
   bool dma_on = true;  // (ABL 1 / 3 turn it off after the prologue)
   constexpr bool BUFDMA = (OPT & 1) != 0 && asrc_has_buffer<ASrc>::value;
   __amdgpu_buffer_rsrc_t rsa, rsw;
@@ -498,25 +487,25 @@ __global__ __launch_bounds__(512) void gemm256h_tn_kernel(ASrc asrc, const half_
         wvoff[s][p] = ((unsigned)(n < N ? n : N - 1) * (unsigned)ldw + (unsigned)cswz) * 2u;
       }
   }
-  // the two LDS-DMAs of a piece: P = 0 / 1 / 2 = both / the first / the second
-  auto issue_a = [&](int s, char* slot, int P = 0) {
-    if ((ABL == 1 || ABL == 3 || (ABL >= 5 && ABL <= 7)) && !dma_on) return;
+  // the two LDS-DMAs of a piece (A: of the A-source's current K-tile, begin_tile)
+  auto issue_a = [&](int s, char* slot) {
+    if (NO_DMA && !dma_on) return;
     if constexpr (BUFDMA) {
-      if (P != 2) glds16_buf(rsa, avoff[s][0], asrc.soff(), slot + dma_off);
-      if (P != 1) glds16_buf(rsa, avoff[s][1], asrc.soff(), slot + 8192 + dma_off);
+      glds16_buf(rsa, avoff[s][0], asrc.soff(), slot + dma_off);
+      glds16_buf(rsa, avoff[s][1], asrc.soff(), slot + 8192 + dma_off);
     } else {
-      if (P != 2) glds16(asrc.ptr(arow[s][0], cswz), slot + dma_off);
-      if (P != 1) glds16(asrc.ptr(arow[s][1], cswz), slot + 8192 + dma_off);
+      glds16(asrc.ptr(arow[s][0], cswz), slot + dma_off);
+      glds16(asrc.ptr(arow[s][1], cswz), slot + 8192 + dma_off);
     }
   };
-  auto issue_b = [&](int s, int kt, char* slot, int P = 0) {
-    if ((ABL == 1 || ABL == 3 || (ABL >= 5 && ABL <= 7)) && !dma_on) return;
+  auto issue_b = [&](int s, int kt, char* slot) {
+    if (NO_DMA && !dma_on) return;
     if constexpr (BUFDMA) {
-      if (P != 2) glds16_buf(rsw, wvoff[s][0], (unsigned)kt * (G256Q_BK * 2), slot + dma_off);
-      if (P != 1) glds16_buf(rsw, wvoff[s][1], (unsigned)kt * (G256Q_BK * 2), slot + 8192 + dma_off);
+      glds16_buf(rsw, wvoff[s][0], (unsigned)kt * (G256Q_BK * 2), slot + dma_off);
+      glds16_buf(rsw, wvoff[s][1], (unsigned)kt * (G256Q_BK * 2), slot + 8192 + dma_off);
     } else {
-      if (P != 2) glds16(wrow[s][0] + kt * G256Q_BK, slot + dma_off);
-      if (P != 1) glds16(wrow[s][1] + kt * G256Q_BK, slot + 8192 + dma_off);
+      glds16(wrow[s][0] + kt * G256Q_BK, slot + dma_off);
+      glds16(wrow[s][1] + kt * G256Q_BK, slot + 8192 + dma_off);
     }
   };
 
@@ -526,104 +515,56 @@ __global__ __launch_bounds__(512) void gemm256h_tn_kernel(ASrc asrc, const half_
 #pragma unroll
     for (int j = 0; j < 4; ++j) acc[i][j] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
 
-  // fragment reads: lane (r = lane&15, q = lane>>4) reads logical chunk 4*ks + q of local row base + r; key(row) = (row>>1)&7 and the
-  // 16-row tile bases are multiples of 16, so the key depends on the lane only
-  const int rkey = ((lane & 15) >> 1) & 7, q4 = lane >> 4;
-  int a_addr[2], w_addr[2];
-#pragma unroll
-  for (int ks = 0; ks < 2; ++ks) {
-    a_addr[ks] = (g * 64 + (lane & 15)) * 128 + (((ks * 4 + q4) ^ rkey) << 4);   // + i4 * 2048 (16 rows)
-    w_addr[ks] = (wn * 32 + (lane & 15)) * 128 + (((ks * 4 + q4) ^ rkey) << 4);  // + j2 * 2048
-  }
+  int a_addr[2], w_addr[2];  // + i4 * 2048 (16 rows) / + j2 * 2048
+  g256q_frag_addr(a_addr, g * 64, lane);
+  g256q_frag_addr(w_addr, wn * 32, lane);
   half8_t af[4][2], wf[4][2];  // A: [16-row tile of the current sub][k32 step];  W: [16-column tile 0..3 (sub0: 0,1; sub1: 2,3)][k32 step]
-  auto lds_read = [&](half8_t& dst, int addr, auto OFFC) {
-    constexpr int OFF = decltype(OFFC)::value;
-    if constexpr (ABL == 2 || ABL == 3 || (ABL >= 5 && ABL <= 7)) asm volatile("" : "+v"(dst));  // (ablation: the fragment keeps whatever it held)
-    else asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(OFF) : "memory");
-  };
-#define G256H_VMCNT(n) asm volatile("s_waitcnt vmcnt(" #n ")" ::: "memory")
-#define G256H_LGKM(n) asm volatile("s_waitcnt lgkmcnt(" #n ")" ::: "memory")
 
-  // LOAD part of phase PH of K-tile t: fragment reads in consumption order (k32-step major), one piece staged, counted wait (v3, SCHED 1)
+  // LOAD part of phase PH of K-tile t: fragment reads in consumption order (k32-step major), one piece staged, counted wait
+  // pieces per part, and the waits behind them (gemm256q_ring.h):  B1(t+1) | A1(t+1) | A0(t+2) | B0(t+2),  in flight 3 3 3 3 | 3 3 2 1 | 0 0 0 0 pieces
+  constexpr int VM_S2[4] = {6, 6, 6, 6}, VM_S1[4] = {6, 6, 4, 2};
+  // (round 6 experiment, OPT & 4) placed against the parts' fragment reads (12 | 4 | 8 | 0):  none | B1(t+1) | A1(t+1) | A0(t+2) B0(t+2)
+  constexpr int VM4_S2[4] = {4, 4, 4, 6}, VM4_S1[4] = {4, 4, 4, 2};
   auto load_part = [&](auto PHC, auto BUFC, int t, bool s1, bool s2) {
     constexpr int PH = decltype(PHC)::value, BUF = decltype(BUFC)::value, HI = BUF * G256Q_BUF_BYTES;
     char* cur = smem + BUF * G256Q_BUF_BYTES;
     char* oth = smem + (BUF ^ 1) * G256Q_BUF_BYTES;
-    auto stage = [&](int P) {  // this phase's piece (P: which of its two LDS-DMAs)
-      if constexpr ((OPT & 4) != 0) {  // (round 6 experiment) pieces placed against the parts' fragment reads (12 | 4 | 8 | 0): none | B1(t+1) | A1(t+1) | A0(t+2) B0(t+2)
-        if constexpr (PH == 1) {
-          if (s1) issue_b(1, t + 1, oth + G256Q_SLOT_B1);
-        } else if constexpr (PH == 2) {
-          if (s1) issue_a(1, oth + G256Q_SLOT_A1);
-        } else if constexpr (PH == 3) {
-          if (s2) {
-            asrc.begin_tile(t + 2, G256Q_BK);
-            issue_a(0, cur + G256Q_SLOT_A0);
-            issue_b(0, t + 2, cur + G256Q_SLOT_B0);
-          }
-        }
-        return;
-      }
-      if constexpr (PH == 0) {
-        if (s1) issue_b(1, t + 1, oth + G256Q_SLOT_B1, P);
-      } else if constexpr (PH == 1) {
-        if (s1) issue_a(1, oth + G256Q_SLOT_A1, P);
-      } else if constexpr (PH == 2) {
-        if (s2) {
-          if (P != 2) asrc.begin_tile(t + 2, G256Q_BK);
-          issue_a(0, cur + G256Q_SLOT_A0, P);
-        }
-      } else {
-        if (s2) issue_b(0, t + 2, cur + G256Q_SLOT_B0, P);
-      }
-    };
-    if constexpr ((OPT & 2) != 0) {
-      stage(1);
-      __builtin_amdgcn_sched_barrier(0);
-    }
     if constexpr (PH == 0) {
 #pragma unroll
       for (int ks = 0; ks < 2; ++ks) {
-        lds_read(wf[0][ks], w_addr[ks] + HI, g256q_ic<G256Q_SLOT_B0>{});
-        lds_read(wf[1][ks], w_addr[ks] + HI, g256q_ic<G256Q_SLOT_B0 + 2048>{});
-        lds_read(af[0][ks], a_addr[ks] + HI, g256q_ic<G256Q_SLOT_A0>{});
-        lds_read(af[1][ks], a_addr[ks] + HI, g256q_ic<G256Q_SLOT_A0 + 2048>{});
-        lds_read(af[2][ks], a_addr[ks] + HI, g256q_ic<G256Q_SLOT_A0 + 4096>{});
-        lds_read(af[3][ks], a_addr[ks] + HI, g256q_ic<G256Q_SLOT_A0 + 6144>{});
+        g256q_lds_read<G256Q_SLOT_B0, READS>(wf[0][ks], w_addr[ks] + HI);
+        g256q_lds_read<G256Q_SLOT_B0 + 2048, READS>(wf[1][ks], w_addr[ks] + HI);
+        g256q_read_a<G256Q_SLOT_A0, READS>(af, a_addr[ks] + HI, ks);
       }
     } else if constexpr (PH == 1) {
 #pragma unroll
       for (int ks = 0; ks < 2; ++ks) {
-        lds_read(wf[2][ks], w_addr[ks] + HI, g256q_ic<G256Q_SLOT_B1>{});
-        lds_read(wf[3][ks], w_addr[ks] + HI, g256q_ic<G256Q_SLOT_B1 + 2048>{});
+        g256q_lds_read<G256Q_SLOT_B1, READS>(wf[2][ks], w_addr[ks] + HI);
+        g256q_lds_read<G256Q_SLOT_B1 + 2048, READS>(wf[3][ks], w_addr[ks] + HI);
       }
     } else if constexpr (PH == 2) {
 #pragma unroll
-      for (int ks = 0; ks < 2; ++ks) {
-        lds_read(af[0][ks], a_addr[ks] + HI, g256q_ic<G256Q_SLOT_A1>{});
-        lds_read(af[1][ks], a_addr[ks] + HI, g256q_ic<G256Q_SLOT_A1 + 2048>{});
-        lds_read(af[2][ks], a_addr[ks] + HI, g256q_ic<G256Q_SLOT_A1 + 4096>{});
-        lds_read(af[3][ks], a_addr[ks] + HI, g256q_ic<G256Q_SLOT_A1 + 6144>{});
-      }
+      for (int ks = 0; ks < 2; ++ks) g256q_read_a<G256Q_SLOT_A1, READS>(af, a_addr[ks] + HI, ks);
     }
     __builtin_amdgcn_sched_barrier(0);
-    stage((OPT & 2) != 0 ? 2 : 0);
-    if constexpr (ABL == 1 || ABL == 3 || (ABL >= 5 && ABL <= 7)) {
-      G256H_VMCNT(0);
-    } else if constexpr ((OPT & 4) != 0) {  // issue order per K-tile: B1 B1 | A1 A1 | A0 A0 B0 B0; the LOAD part after next reads what has landed here
-      if (s1) {
-        if constexpr (PH < 3) G256H_VMCNT(4);
-        else if (s2) G256H_VMCNT(6);
-        else G256H_VMCNT(2);
-      } else G256H_VMCNT(0);
-    } else if (s2) G256H_VMCNT(6);  // pieces allowed in flight: 3 3 3 3 | 3 3 2 1 | 0 0 0 0
-    else if (s1) {
-      if constexpr (PH < 2) G256H_VMCNT(6);
-      else if constexpr (PH == 2) G256H_VMCNT(4);
-      else G256H_VMCNT(2);
-    } else G256H_VMCNT(0);
+    constexpr bool BAL = (OPT & 4) != 0;  // the experiment's placement: every piece one part later, A0 and B0 together
+    if constexpr (PH == (BAL ? 1 : 0)) {
+      if (s1) issue_b(1, t + 1, oth + G256Q_SLOT_B1);
+    } else if constexpr (PH == (BAL ? 2 : 1)) {
+      if (s1) issue_a(1, oth + G256Q_SLOT_A1);
+    } else if (s2) {
+      if constexpr (PH == (BAL ? 3 : 2)) {
+        asrc.begin_tile(t + 2, G256Q_BK);
+        issue_a(0, cur + G256Q_SLOT_A0);
+      }
+      if constexpr (PH == 3) issue_b(0, t + 2, cur + G256Q_SLOT_B0);
+    }
+    if constexpr (NO_DMA) G256Q_VMCNT(0);
+    else if constexpr (BAL) g256q_load_wait<VM4_S2[PH], VM4_S1[PH]>(s1, s2);
+    else g256q_load_wait<VM_S2[PH], VM_S1[PH]>(s1, s2);
   };
-  // MFMA part of phase PH: one 64 x 32 quadrant x K = 64 = 16 MFMAs of 16x16x32, every group of 2 behind a counted lgkmcnt
+  // MFMA part of phase PH: one 64 x 32 quadrant x K = 64 = 16 MFMAs of 16x16x32, every group of 2 behind a counted lgkmcnt.  SW: operands swapped (tiles an
+  // epilogue wants transposed -- EpiQKV's V third -- come out as C^T blocks for free)
   auto mfma_part = [&](auto PHC, auto SWC) {
     constexpr int PH = decltype(PHC)::value;
     constexpr bool SW = decltype(SWC)::value != 0;
@@ -633,36 +574,7 @@ __global__ __launch_bounds__(512) void gemm256h_tn_kernel(ASrc asrc, const half_
     for (int ks = 0; ks < 2; ++ks)
 #pragma unroll
       for (int i4 = 0; i4 < 4; ++i4) {
-        if constexpr (PH == 0) {  // 12 reads, per k32 step: W0 W1 A0 A1 A2 A3
-          if (ks == 0) {
-            if (i4 == 0) G256H_LGKM(9);
-            else if (i4 == 1) G256H_LGKM(8);
-            else if (i4 == 2) G256H_LGKM(7);
-            else G256H_LGKM(6);
-          } else {
-            if (i4 == 0) G256H_LGKM(3);
-            else if (i4 == 1) G256H_LGKM(2);
-            else if (i4 == 2) G256H_LGKM(1);
-            else G256H_LGKM(0);
-          }
-        } else if constexpr (PH == 1) {  // 4 reads: W2 W3 (ks 0), W2 W3 (ks 1)
-          if (i4 == 0) {
-            if (ks == 0) G256H_LGKM(2);
-            else G256H_LGKM(0);
-          }
-        } else if constexpr (PH == 2) {  // 8 reads: A0..A3 (ks 0), A0..A3 (ks 1)
-          if (ks == 0) {
-            if (i4 == 0) G256H_LGKM(7);
-            else if (i4 == 1) G256H_LGKM(6);
-            else if (i4 == 2) G256H_LGKM(5);
-            else G256H_LGKM(4);
-          } else {
-            if (i4 == 0) G256H_LGKM(3);
-            else if (i4 == 1) G256H_LGKM(2);
-            else if (i4 == 2) G256H_LGKM(1);
-            else G256H_LGKM(0);
-          }
-        }
+        g256q_lgkm_ladder<PH, 4>(ks, i4);
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int j2 = 0; j2 < 2; ++j2) {
@@ -694,13 +606,13 @@ __global__ __launch_bounds__(512) void gemm256h_tn_kernel(ASrc asrc, const half_
     issue_b(0, 1, smem + G256Q_BUF_BYTES + G256Q_SLOT_B0);
   }
   if constexpr (epi_has_rowstat<Epi>::value) g256h_rowstat_finish(epi, rsr, smem, m0, M, tile_n);
-  if (nk > 1) G256H_VMCNT(6);
-  else G256H_VMCNT(2);
-  if constexpr (ABL == 1 || ABL == 3 || (ABL >= 5 && ABL <= 7)) {
-    G256H_VMCNT(0);
+  if (nk > 1) G256Q_VMCNT(6);
+  else G256Q_VMCNT(2);
+  if constexpr (NO_DMA) {
+    G256Q_VMCNT(0);
     dma_on = false;
   }
-  if constexpr (ABL == 2 || ABL == 3 || (ABL >= 5 && ABL <= 7)) {  // defined fragment contents for the ablated reads
+  if constexpr (!READS) {  // defined fragment contents for the ablated reads
 #pragma unroll
     for (int i = 0; i < 4; ++i)
 #pragma unroll
@@ -713,57 +625,30 @@ __global__ __launch_bounds__(512) void gemm256h_tn_kernel(ASrc asrc, const half_
     if (g == 1) __builtin_amdgcn_s_setprio(1);
   }
   G256_BARRIER();
-  // ONE barrier per phase: group 0 runs MFMA(p), LOAD(p+1); group 1 runs LOAD(p), MFMA(p) (hazard analysis: gemm256q_kernel.h)
-  auto run = [&](auto GC, auto SWC) {
-    constexpr int G = decltype(GC)::value;
-    if constexpr (G == 0) load_part(g256q_ic<0>{}, g256q_ic<0>{}, 0, 1 < nk, 2 < nk);
-    G256_BARRIER();
-    auto tile = [&](auto BUFC, int t) {
-      constexpr int BUF = decltype(BUFC)::value;
-      const bool s1 = t + 1 < nk, s2 = t + 2 < nk, s3 = t + 3 < nk;
-      auto phase = [&](auto PHC) {
-        constexpr int PH = decltype(PHC)::value;
-        if constexpr (G == 0) {
-          mfma_part(PHC, SWC);
-          if constexpr (PH < 3) load_part(g256q_ic<PH + 1>{}, BUFC, t, s1, s2);
-          else if (s1) load_part(g256q_ic<0>{}, g256q_ic<(BUF ^ 1)>{}, t + 1, s2, s3);
-        } else {
-          load_part(PHC, BUFC, t, s1, s2);
-          mfma_part(PHC, SWC);
-        }
-        if constexpr (ABL == 5 || ABL == 7) {
-        } else if constexpr (ABL == 6) {
-          if constexpr (PH == 3) G256_BARRIER();
-        } else {
-          G256_BARRIER();
-        }
-      };
-      phase(g256q_ic<0>{});
-      phase(g256q_ic<1>{});
-      phase(g256q_ic<2>{});
-      phase(g256q_ic<3>{});
-    };
-    int t = 0;
-    for (; t + 1 < nk; t += 2) {
-      tile(g256q_ic<0>{}, t);
-      tile(g256q_ic<1>{}, t + 1);
+  // the ping-pong K loop (gemm256q_ring.h); one barrier per phase, except in the barrier ablations
+  auto end_phase = [&](auto PHC) {
+    if constexpr (ABL == 5 || ABL == 7) {
+    } else if constexpr (ABL == 6) {
+      if constexpr (decltype(PHC)::value == 3) G256_BARRIER();
+    } else {
+      G256_BARRIER();
     }
-    if (t < nk) tile(g256q_ic<0>{}, t);
   };
+  // (the calls are written out: wrapped in one more lambda over SW, the ASrcConv instantiations -- 256 VGPRs -- spill 14 registers instead of 8)
+  auto mfma_n = [&](auto PHC) { mfma_part(PHC, g256q_ic<0>{}); };
+  auto mfma_s = [&](auto PHC) { mfma_part(PHC, g256q_ic<1>{}); };
   if constexpr (epi_has_transposed<Epi>::value) {
     if (swapped) {
-      if (g == 0) run(g256q_ic<0>{}, g256q_ic<1>{});
-      else run(g256q_ic<1>{}, g256q_ic<1>{});
+      if (g == 0) g256q_run<0>(nk, load_part, mfma_s, end_phase);
+      else g256q_run<1>(nk, load_part, mfma_s, end_phase);
     } else {
-      if (g == 0) run(g256q_ic<0>{}, g256q_ic<0>{});
-      else run(g256q_ic<1>{}, g256q_ic<0>{});
+      if (g == 0) g256q_run<0>(nk, load_part, mfma_n, end_phase);
+      else g256q_run<1>(nk, load_part, mfma_n, end_phase);
     }
   } else {
-    if (g == 0) run(g256q_ic<0>{}, g256q_ic<0>{});
-    else run(g256q_ic<1>{}, g256q_ic<0>{});
+    if (g == 0) g256q_run<0>(nk, load_part, mfma_n, end_phase);
+    else g256q_run<1>(nk, load_part, mfma_n, end_phase);
   }
-#undef G256H_VMCNT
-#undef G256H_LGKM
   if constexpr (ABL == 7 || ABL == 8) asm volatile("s_nop 7\n\ts_nop 7\n\ts_nop 7" ::: "memory");  // inline-asm MFMAs: their results must have landed
   g256h_epilogue<G256_BN, TRACE>(acc, smem, epi, m0, n0, M, N, g, wn, lane, wave, bz, bsC, dbg, swapped);
 }

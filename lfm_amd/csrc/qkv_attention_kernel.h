@@ -4,7 +4,7 @@
 // Why (round 6): as two kernels the block writes Q | K | V^T to HBM (100.7 MB at 64 images of DiT-L/2) in an epilogue that no MFMA overlaps and reads them
 // back in an attention kernel whose memory and compute phases overlap by two thirds only (profiles/r06_final_bench_kernel_stats.csv: 101.6 + 29.5 us).  One
 // 256-token image x one head is exactly one 256-row tile x 192 columns of the QKV GEMM, and its Q, K, V^T (96 KiB of fp16) fit the LDS the operand ring
-// leaves behind: a workgroup = (image, head) runs the K loop of gemm256h_kernel.h on a 256 x 192 tile, applies the folded-LayerNorm row affine
+// leaves behind: a workgroup = (image, head) runs the K loop of gemm256q_ring.h on a 256 x 192 tile, applies the folded-LayerNorm row affine
 // a[m] acc + (b[m] u[n] + v[n]) straight from the accumulators into the LDS images the attention kernel would have staged (K [256][64], V^T [64][256] in the
 // vt_pos token order, Q beside them) and then runs the key loop of dit_attention_kernel<256, 1, 64> on them.  HBM sees A' (through the L2: 16 heads share an
 // image's panel), W and O: 266 MB -> ~75 MB per block.
@@ -13,7 +13,7 @@
 // fma_v as in EpiQKVMod, the softmax block is att_softmax_block, S^T / O^T MFMAs and the normalisation as in the per-item kernel => O is BIT-IDENTICAL to
 // launch_gemm256h_tn<EpiQKVMod> + attention_launch (tests/test_gpu_dit.py::test_fused_qkv_attention_matches_two_kernels).
 //
-// K loop = gemm256h_kernel.h's (quadrant phases, piece-granular LDS-DMA ring, ping-pong wave groups, one barrier per phase, counted waits) with a 192-column
+// K loop = the shared one of gemm256q_ring.h (phase table, hazard rule, ping-pong skeleton, counted waits; the same text the 256x256 GEMM runs) with a 192-column
 // tile: wave (g, wn) owns rows g*128.. x 48 columns of the head, gathered by the DMA source addresses of the W rows -- accumulator tiles j = 0, 1: 32 dims of
 // Q (waves wn = 0, 1) or of K (wn = 2, 3), interleaved in fours so that a lane's two tiles are EIGHT CONSECUTIVE dims of a row (one 16-byte write in the
 // hand-over); tile j = 2: V dims 16 wn .. + 15.  Piece B0 = the Q and K rows (128 rows, 16 KiB, as before), piece B1 = the V rows (64 rows, 8 KiB: ONE LDS-DMA
@@ -62,7 +62,7 @@ __global__ __launch_bounds__(512) void qkv_attention_kernel(const half_t* __rest
   int m0 = tile_m * G256_BM;
 
   // ---- DMA sources (piece = rows x 128 B; thread tid stages 16-byte chunk tid of an 8-KiB issue; chunk c of LDS row r holds logical chunk c ^ ((r >> 1) & 7))
-  const int cswz = ((tid & 7) ^ ((tid >> 4) & 7)) * 8;
+  const int cswz = g256q_cswz(tid);
   const __amdgpu_buffer_rsrc_t rsa = __builtin_amdgcn_make_buffer_rsrc((void*)A, 0, -1, 0x00020000);
   const __amdgpu_buffer_rsrc_t rsw = __builtin_amdgcn_make_buffer_rsrc((void*)W, 0, -1, 0x00020000);
   unsigned avoff[2][2], wvoff0[2], wvoff1;
@@ -85,7 +85,7 @@ __global__ __launch_bounds__(512) void qkv_attention_kernel(const half_t* __rest
 #else
   const int nk = K / G256Q_BK;
 #endif
-  const int dma_off = wave * 1024;
+  const int dma_off = g256q_dma_off(wave);
   auto issue_a = [&](int s, int kt, char* slot) {
     glds16_buf(rsa, avoff[s][0], (unsigned)kt * (G256Q_BK * 2), slot + dma_off);
     glds16_buf(rsa, avoff[s][1], (unsigned)kt * (G256Q_BK * 2), slot + 8192 + dma_off);
@@ -99,21 +99,11 @@ __global__ __launch_bounds__(512) void qkv_attention_kernel(const half_t* __rest
   f32x4_t acc[8][3];
 
   const int l15 = lane & 15, l4 = lane >> 4;
-  const int rkey = (l15 >> 1) & 7;
-  int a_addr[2], w_addr[2], w1_addr[2];
-#pragma unroll
-  for (int ks = 0; ks < 2; ++ks) {
-    a_addr[ks] = (g * 64 + l15) * 128 + (((ks * 4 + l4) ^ rkey) << 4);   // + i4 * 2048
-    w_addr[ks] = (wn * 32 + l15) * 128 + (((ks * 4 + l4) ^ rkey) << 4);  // + j * 2048 (tiles j = 0, 1)
-    w1_addr[ks] = (wn * 16 + l15) * 128 + (((ks * 4 + l4) ^ rkey) << 4);
-  }
+  int a_addr[2], w_addr[2], w1_addr[2];  // + i4 * 2048 / + j * 2048 (tiles j = 0, 1) / tile 2
+  g256q_frag_addr(a_addr, g * 64, lane);
+  g256q_frag_addr(w_addr, wn * 32, lane);
+  g256q_frag_addr(w1_addr, wn * 16, lane);
   half8_t af[4][2], wf[3][2];
-  auto lds_read = [&](half8_t& dst, int addr, auto OFFC) {
-    constexpr int OFF = decltype(OFFC)::value;
-    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(OFF) : "memory");
-  };
-#define QKVA_VMCNT(n) asm volatile("s_waitcnt vmcnt(" #n ")" ::: "memory")
-#define QKVA_LGKM(n) asm volatile("s_waitcnt lgkmcnt(" #n ")" ::: "memory")
 
   // LOAD part of phase PH of K-tile t: fragment reads in consumption order, one piece staged, counted wait (three pieces stay in flight)
   auto load_part = [&](auto PHC, auto BUFC, int t, bool s1, bool s2) {
@@ -123,24 +113,16 @@ __global__ __launch_bounds__(512) void qkv_attention_kernel(const half_t* __rest
     if constexpr (PH == 0) {
 #pragma unroll
       for (int ks = 0; ks < 2; ++ks) {
-        lds_read(wf[0][ks], w_addr[ks] + HI, g256q_ic<G256Q_SLOT_B0>{});
-        lds_read(wf[1][ks], w_addr[ks] + HI, g256q_ic<G256Q_SLOT_B0 + 2048>{});
-        lds_read(af[0][ks], a_addr[ks] + HI, g256q_ic<G256Q_SLOT_A0>{});
-        lds_read(af[1][ks], a_addr[ks] + HI, g256q_ic<G256Q_SLOT_A0 + 2048>{});
-        lds_read(af[2][ks], a_addr[ks] + HI, g256q_ic<G256Q_SLOT_A0 + 4096>{});
-        lds_read(af[3][ks], a_addr[ks] + HI, g256q_ic<G256Q_SLOT_A0 + 6144>{});
+        g256q_lds_read<G256Q_SLOT_B0>(wf[0][ks], w_addr[ks] + HI);
+        g256q_lds_read<G256Q_SLOT_B0 + 2048>(wf[1][ks], w_addr[ks] + HI);
+        g256q_read_a<G256Q_SLOT_A0>(af, a_addr[ks] + HI, ks);
       }
     } else if constexpr (PH == 1) {
 #pragma unroll
-      for (int ks = 0; ks < 2; ++ks) lds_read(wf[2][ks], w1_addr[ks] + HI, g256q_ic<G256Q_SLOT_B1>{});
+      for (int ks = 0; ks < 2; ++ks) g256q_lds_read<G256Q_SLOT_B1>(wf[2][ks], w1_addr[ks] + HI);
     } else if constexpr (PH == 2) {
 #pragma unroll
-      for (int ks = 0; ks < 2; ++ks) {
-        lds_read(af[0][ks], a_addr[ks] + HI, g256q_ic<G256Q_SLOT_A1>{});
-        lds_read(af[1][ks], a_addr[ks] + HI, g256q_ic<G256Q_SLOT_A1 + 2048>{});
-        lds_read(af[2][ks], a_addr[ks] + HI, g256q_ic<G256Q_SLOT_A1 + 4096>{});
-        lds_read(af[3][ks], a_addr[ks] + HI, g256q_ic<G256Q_SLOT_A1 + 6144>{});
-      }
+      for (int ks = 0; ks < 2; ++ks) g256q_read_a<G256Q_SLOT_A1>(af, a_addr[ks] + HI, ks);
     }
     __builtin_amdgcn_sched_barrier(0);
     // Which LDS-DMAs go out in which LOAD part is balanced against the part's fragment reads (12 | 2 | 8 | 0): none | B1(t+1) A1(t+1) A1(t+1) | A0(t+2) | A0(t+2)
@@ -162,19 +144,11 @@ __global__ __launch_bounds__(512) void qkv_attention_kernel(const half_t* __rest
         issue_b0(t + 2, cur + G256Q_SLOT_B0);
       }
     }
-    // counted waits: what the LOAD part after next reads has landed (a barrier lies in between); newer DMAs may still fly.  Issue order per K-tile:
-    // B1 A1 A1 | A0 | A0 B0 B0
-    if (s2) {
-      if constexpr (PH == 0) QKVA_VMCNT(4);       // A1(t) landed; A0(t+1) x2, B0(t+1) x2 may fly
-      else if constexpr (PH == 1) QKVA_VMCNT(5);  // A0(t+1) landed; B0(t+1) x2, B1(t+1), A1(t+1) x2
-      else if constexpr (PH == 2) QKVA_VMCNT(4);  // B0(t+1) landed; B1(t+1), A1(t+1) x2, A0(t+2)
-      else QKVA_VMCNT(6);                         // B1(t+1) landed; A1(t+1) x2, A0(t+2) x2, B0(t+2) x2
-    } else if (s1) {
-      if constexpr (PH == 0) QKVA_VMCNT(4);
-      else if constexpr (PH == 1) QKVA_VMCNT(5);
-      else if constexpr (PH == 2) QKVA_VMCNT(3);  // B0(t+1) landed; B1(t+1), A1(t+1) x2
-      else QKVA_VMCNT(2);                         // B1(t+1) landed; A1(t+1) x2
-    } else QKVA_VMCNT(0);
+    // counted waits (gemm256q_ring.h: what the LOAD part after next reads has landed; newer DMAs may still fly).  Issue order per K-tile: B1 A1 A1 | A0 | A0 B0 B0
+    //   LOAD 0: A1(t) landed; A0(t+1) x2, B0(t+1) x2 may fly            LOAD 1: A0(t+1) landed; B0(t+1) x2, B1(t+1), A1(t+1) x2
+    //   LOAD 2: B0(t+1) landed; B1(t+1), A1(t+1) x2 [, A0(t+2)]         LOAD 3: B1(t+1) landed; A1(t+1) x2 [, A0(t+2) x2, B0(t+2) x2]
+    constexpr int VM_S2[4] = {4, 5, 4, 6}, VM_S1[4] = {4, 5, 3, 2};
+    g256q_load_wait<VM_S2[PH], VM_S1[PH]>(s1, s2);
   };
   // MFMA part of phase PH: A sub (64 rows) x {Q, K tiles | V tile} x K = 64
   auto mfma_part = [&](auto PHC) {
@@ -186,36 +160,7 @@ __global__ __launch_bounds__(512) void qkv_attention_kernel(const half_t* __rest
     for (int ks = 0; ks < 2; ++ks)
 #pragma unroll
       for (int i4 = 0; i4 < 4; ++i4) {
-        if constexpr (PH == 0) {  // 12 reads, per k32 step: W0 W1 A0 A1 A2 A3
-          if (ks == 0) {
-            if (i4 == 0) QKVA_LGKM(9);
-            else if (i4 == 1) QKVA_LGKM(8);
-            else if (i4 == 2) QKVA_LGKM(7);
-            else QKVA_LGKM(6);
-          } else {
-            if (i4 == 0) QKVA_LGKM(3);
-            else if (i4 == 1) QKVA_LGKM(2);
-            else if (i4 == 2) QKVA_LGKM(1);
-            else QKVA_LGKM(0);
-          }
-        } else if constexpr (PH == 1) {  // 2 reads: W2 (ks 0), W2 (ks 1)
-          if (i4 == 0) {
-            if (ks == 0) QKVA_LGKM(1);
-            else QKVA_LGKM(0);
-          }
-        } else if constexpr (PH == 2) {  // 8 reads: A0..A3 (ks 0), A0..A3 (ks 1)
-          if (ks == 0) {
-            if (i4 == 0) QKVA_LGKM(7);
-            else if (i4 == 1) QKVA_LGKM(6);
-            else if (i4 == 2) QKVA_LGKM(5);
-            else QKVA_LGKM(4);
-          } else {
-            if (i4 == 0) QKVA_LGKM(3);
-            else if (i4 == 1) QKVA_LGKM(2);
-            else if (i4 == 2) QKVA_LGKM(1);
-            else QKVA_LGKM(0);
-          }
-        }
+        g256q_lgkm_ladder<PH, 2>(ks, i4);
         __builtin_amdgcn_sched_barrier(0);
         if constexpr (VT) {  // operands swapped: acc[i][2][r] = C[m = 16 i + 4 l4 + r][V dim 16 wn + l15]
           acc[I0 + i4][2] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[i4][ks], wf[2][ks], acc[I0 + i4][2], 0, 0, 0);
@@ -247,56 +192,17 @@ __global__ __launch_bounds__(512) void qkv_attention_kernel(const half_t* __rest
   issue_a(1, 0, smem + G256Q_SLOT_A1);
   issue_a(0, 1, smem + G256Q_BUF_BYTES + G256Q_SLOT_A0);
   issue_b0(1, smem + G256Q_BUF_BYTES + G256Q_SLOT_B0);
-  // (a, b) = (rstd, -rstd (mu - c)) of an item's 256 rows (g256h_rowstat_finish with its own destination): the upper 8 KiB of the first ring half's B1 slot, which
-  // no LDS-DMA ever touches (piece B1 is 8 KiB of a 16-KiB slot) -- written for item k + 1 at the end of item k, read at item k + 1's hand-over
+  // (a, b) = (rstd, -rstd (mu - c)) of an item's 256 rows (g256h_rowstat, as in g256h_rowstat_finish, with its own destination): the upper 8 KiB of the first ring
+  // half's B1 slot, which no LDS-DMA ever touches (piece B1 is 8 KiB of a 16-KiB slot) -- written for item k + 1 at the end of item k, read at item k + 1's hand-over
   float* const rs = (float*)(smem + G256Q_SLOT_B1 + 8192);
   auto rowstat_finish = [&](const G256hRowStatRegs& r, int m0_, int head_) {
     if (threadIdx.x < 256) {
-      float sx = 0.f, sq = 0.f;
-#pragma unroll
-      for (int t = 0; t < G256H_MAX_PARTS; ++t) {  // fixed order
-        sx += r.p[t].x;
-        sq += r.p[t].y;
-      }
-      const float mu = sx * ep.st.inv_n, dl = mu - r.c;
-      const float var = fmaxf(sq * ep.st.inv_n - dl * dl, 0.f);
-      const float rstd = rsqrtf(var + ep.st.eps);
-      *(f32x2*)(rs + 2 * threadIdx.x) = (f32x2){rstd, -rstd * dl};
+      float mu;
+      *(f32x2*)(rs + 2 * threadIdx.x) = g256h_rowstat(r, ep.st.inv_n, ep.st.eps, mu);
       if (head_ == 0 && m0_ + (int)threadIdx.x < M) ep.st.cen_out[m0_ + threadIdx.x] = mu;  // head 0 publishes the row means: the next producer's centring constants
     }
   };
   rowstat_finish(rsr, m0, head);
-  auto run = [&](auto GC) {
-    constexpr int G = decltype(GC)::value;
-    if constexpr (G == 0) load_part(g256q_ic<0>{}, g256q_ic<0>{}, 0, 1 < nk, 2 < nk);
-    G256_BARRIER();
-    auto tile = [&](auto BUFC, int t) {
-      constexpr int BUF = decltype(BUFC)::value;
-      const bool s1 = t + 1 < nk, s2 = t + 2 < nk, s3 = t + 3 < nk;
-      auto phase = [&](auto PHC) {
-        constexpr int PH = decltype(PHC)::value;
-        if constexpr (G == 0) {
-          mfma_part(PHC);
-          if constexpr (PH < 3) load_part(g256q_ic<PH + 1>{}, BUFC, t, s1, s2);
-          else if (s1) load_part(g256q_ic<0>{}, g256q_ic<(BUF ^ 1)>{}, t + 1, s2, s3);
-        } else {
-          load_part(PHC, BUFC, t, s1, s2);
-          mfma_part(PHC);
-        }
-        G256_BARRIER();
-      };
-      phase(g256q_ic<0>{});
-      phase(g256q_ic<1>{});
-      phase(g256q_ic<2>{});
-      phase(g256q_ic<3>{});
-    };
-    int t = 0;
-    for (; t + 1 < nk; t += 2) {
-      tile(g256q_ic<0>{}, t);
-      tile(g256q_ic<1>{}, t + 1);
-    }
-    if (t < nk) tile(g256q_ic<0>{}, t);
-  };
   // LDS in the attention phase: K [256][64] and V^T [64][256] in the SECOND ring half, Q [256][64] above the ring -- the first ring half stays free, so the next
   // item's first four operand pieces can be requested from the moment the K loop ends.  A wave's own 32 Q rows (4 KiB) are its output staging once it holds its Q
   // fragments.  Q, K: 128-byte rows, chunk c of row r at c ^ ((r >> 1) & 7); V^T: 512-byte rows, tokens of a 16-group in the vt_pos order, chunk c of row d at
@@ -329,12 +235,12 @@ __global__ __launch_bounds__(512) void qkv_attention_kernel(const half_t* __rest
 #pragma unroll
       for (int j = 0; j < 3; ++j) acc[i][j] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
     stamp(0);
-    if (first) QKVA_VMCNT(6);
-    else QKVA_VMCNT(10);
+    if (first) G256Q_VMCNT(6);
+    else G256Q_VMCNT(10);
     G256_BARRIER();
     stamp(1);
-    if (g == 0) run(g256q_ic<0>{});
-    else run(g256q_ic<1>{});
+    if (g == 0) g256q_run<0>(nk, load_part, mfma_part);
+    else g256q_run<1>(nk, load_part, mfma_part);
     stamp(2);
 
     // ---- hand-over: the ring is dead (every wave is past the last barrier, its fragment reads retired before its MFMAs).  (The lane id is laundered per phase:
@@ -560,8 +466,6 @@ __global__ __launch_bounds__(512) void qkv_attention_kernel(const half_t* __rest
     m0 = ntile_m * G256_BM;
     first = false;
   }
-#undef QKVA_VMCNT
-#undef QKVA_LGKM
 }
 
 // A: [M, lda] fp16 (the centred, (1 + scale)-weighted rows A' of the folded path), W: [3 D, ldw] fp16 (rows q | k | v, head-major), O: [M, D].

@@ -667,6 +667,45 @@ def test_fused_qkv_attention_matches_two_kernels(dev, name, batch, labels):
     assert rel_l2(a[:k].cpu(), ref) < 2e-3
 
 
+@pytest.mark.parametrize("hidden,heads,batch", [(256, 4, 192), (512, 8, 96)])
+def test_fused_qkv_attention_shortest_k_loops(dev, hidden, heads, batch):
+    """The fused kernel at the shortest K loops it can run: a depth-2 DiT with patch 2 on 32 x 32 latents at hidden 256 (4 K-tiles) and 512 (8 K-tiles), where the
+    prologue, the last-but-one / last K-tile waits of the shared K loop (csrc/gemm256q_ring.h) and the next item's requests sit closest together.  Batch = the
+    smallest for which the plan takes the fused kernel ((M / 256) x (D / 256) >= 192): 768 items on 256 CUs, every persistent workgroup walks three items.  Same
+    assertions as test_fused_qkv_attention_matches_two_kernels: bit-identical to the two-kernel path per image, bit-repeatable, finite, the oracle on two images."""
+    from lfm_amd import hip
+    from lfm_amd.models.DiT import DiT
+
+    kw = dict(num_classes=1, label_dropout=0.0)
+    cfg = dit_ref.DiTCfg(2, hidden, 2, heads, **kw)
+    sd = dit_ref.make_dit_state(cfg, seed=11)
+    m = DiT(depth=2, hidden_size=hidden, patch_size=2, num_heads=heads, img_resolution=32, in_channels=4, **kw)
+    m.load_state_dict(sd, strict=True)
+    m = m.to(dev).eval()
+    g = torch.Generator().manual_seed(5)
+    x = torch.randn(batch, 4, 32, 32, generator=g)
+    t = torch.tensor(0.4)
+    xd, td = x.to(dev), t.to(dev)
+    plan = hip.dit_plan(m.shape_struct(), batch, t_len=1, labels=False)
+    assert plan == hip.PLAN_FOLDED_LN | hip.PLAN_FUSED_QKV_ATTENTION, "the fused kernel would not run for this case: the comparison below would be vacuous"
+    try:
+        hip.set_option(hip.OPT_FUSED_QKV_ATTENTION, 0)
+        two = m(td, xd, None).clone()
+        hip.set_option(hip.OPT_FUSED_QKV_ATTENTION, 1)
+        a = m(td, xd, None).clone()
+        b = m(td, xd, None).clone()
+        torch.cuda.synchronize()
+    finally:
+        hip.set_option(hip.OPT_FUSED_QKV_ATTENTION, 1)
+    assert bool(torch.isfinite(a).all())
+    assert torch.equal(a, b)
+    bad = (a != two).flatten(1).any(dim=1)
+    assert not bool(bad.any()), f"{int(bad.sum())} of {batch} images differ (first {bad.nonzero()[:4].flatten().tolist()}), rel-L2 {rel_l2(a, two):.3e}"
+    k = 2
+    ref = dit_ref.dit_forward(sd, cfg, t, x[:k], None)
+    assert rel_l2(a[:k].cpu(), ref) < 2e-3
+
+
 @pytest.mark.parametrize("fold", [1, 0])
 def test_trained_like_dynamic_range(dev, fold):
     """Every other parity test runs on xavier / N(0, 0.02) weights.  A trained DiT has a few 'massive' residual channels, large adaLN scales and a wide
