@@ -201,6 +201,12 @@ int lfm_profile_blocks_read(float* host_ms_out, int max_n);
  * its VALU kernel serves (ch % 16 == 0, ch <= 256, any token count) on the streamed kernel (csrc/unet_attention_stream_kernel.h).  0 = those shapes are
  * refused (LFM_ERR_SHAPE); 2 = EVERY shape with ch % 16 == 0, ch <= 256 takes the streamed kernel (parity tests and A/B only). */
 #define LFM_OPT_UNET_ATTENTION_STREAM 7
+/* key 8 (LFM_OPT_ATTENTION_TILED), value 0 / 1 / 2, default 1 (any other value: LFM_ERR_ARG): lfm_dit_attention_hd runs the token counts no other kernel serves --
+ * T the square of a grid side that is a multiple of 4, 144 <= T <= 3600: 144, 400, 576, 784, 1296, ... (--image_size 192 / 320 / 384 / 448 / 576 with a DiT-x/2) --
+ * on the tiled kernel (csrc/attention_tiled_kernel.h: T a runtime argument, 128 queries per workgroup, keys in stages of 64 through an LDS ring).  0 = those
+ * token counts are refused (LFM_ERR_SHAPE, by lfm_dit_forward too); 2 = EVERY shape the kernel takes (head_dim 64 / 72, T % 16 == 0, 16 <= T < 4096) runs on
+ * it, the ones other kernels own included (parity tests and A/B only). */
+#define LFM_OPT_ATTENTION_TILED 8
 int lfm_set_option(int key, int value);
 /* The settings lfm_dit_forward would run `call` with if it were enqueued by the calling thread now (per-call fields over the library defaults):
  * *gemm_select_out = kernel | flags << 4, *fold_ln_out = 0 / 1.  No launch; usable without a GPU. */
@@ -232,7 +238,8 @@ int lfm_profile_fc1_read(float* host_ms_out, int max_n);
 int lfm_ln_modulate(const float* X, void* A, int M, int D, int tokens, const float* shift, const float* scale, long mod_stride,
                     lfm_stream_t stream);
 
-/* softmax(q k^T / sqrt(hd)) v for hd = 64, T in {16,64,128,256,1024} (timm Attention as called at models/DiT.py:120; 1024 = four key chunks of 256).
+/* softmax(q k^T / sqrt(hd)) v for hd = 64, T in {16,64,128,256,1024} (timm Attention as called at models/DiT.py:120; 1024 = four key chunks of 256) or the
+ * square of a grid side that is a multiple of 4 with 144 <= T <= 3600 (the tiled kernel, LFM_OPT_ATTENTION_TILED); 4096 tokens and more are refused.
  * Q,K: fp16 [batch*T, D] token-major; Vt: fp16 [batch, heads, hd, T] in the token order lfm_gemm_qkv_f16 writes (16-groups permuted); O: fp16 [batch*T, D]. */
 int lfm_dit_attention(const void* Q, const void* K, const void* Vt, void* O, int batch, int heads, int T, lfm_stream_t stream);
 /* The same with the head size as an argument: head_dim 64 (DiT-S / B / L) or 72 (DiT-XL/{2,4,8}: 1152 / 16, models/DiT.py:354-363);
@@ -242,7 +249,8 @@ int lfm_dit_attention_hd(const void* Q, const void* K, const void* Vt, void* O, 
 /* Which kernel lfm_dit_attention_hd runs for this shape under the calling thread's flags and the library options, or LFM_ERR_SHAPE for a shape no kernel
  * serves: 1 = the 16-token kernel, 2 = one workgroup per (image, head) item, 3 = the same with four waves x 64 queries (flag LFM_DBG_ATT_WIDE), 4 = four key
  * chunks (1024 tokens), 5 = the latency-mode query split (256 tokens x head_dim 64, at most 64 items), 6 = the streamed kernel (LFM_OPT_ATTENTION_STREAM;
- * more than 64 items, each tensor below 2 GiB).  No launch; usable without a GPU. */
+ * more than 64 items, each tensor below 2 GiB), 7 = the tiled any-T kernel (LFM_OPT_ATTENTION_TILED: by default the square grids of a side that is a multiple of
+ * 4 from 144 to 3600 tokens that 2 .. 6 do not serve).  No launch; usable without a GPU. */
 int lfm_attention_plan(int batch, int heads, int head_dim, int T);
 
 /* ------------------------------------------------------------------ first-stage VAE decoder

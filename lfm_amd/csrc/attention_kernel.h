@@ -19,6 +19,7 @@
 #include <type_traits>
 #include "attention_common.h"
 #include "attention_stream_kernel.h"  // attention_launch runs its kernel too
+#include "attention_tiled_kernel.h"   // ... and the any-T kernel
 
 // MODE 3 (measurement only): s_memtime stamps of wave 0 of the first workgroup (slots 0..31) and of the last one (32..63), read back with
 // lfm_attention_trace_read.  Slots: 0 start, 1 all DMAs / Q loads issued, 2 K and Q landed (first barrier), 3 + 4 k + {0: S(next) issued,
@@ -395,6 +396,7 @@ enum {
   ATT_KERN_CHUNKS = 4,  // 1024 tokens: four key chunks of 256 through the LDS, one workgroup per 256 queries
   ATT_KERN_QSPLIT = 5,  // latency mode (hd 64, 256 tokens, at most 64 items): two workgroups of four waves per item
   ATT_KERN_STREAM = 6,  // attention_stream_kernel.h (hd 64, 256 tokens, more than 64 items): persistent workgroups, K / V^T streamed through an LDS ring
+  ATT_KERN_TILED = 7,   // attention_tiled_kernel.h: any T % 16 == 0 as a runtime argument, 128 queries per workgroup, keys in 64-key stages through an LDS ring
 };
 // the measurement-only variants MODE 1 / 2 / 3 of the hd-64, 256-token kernels (product builds have none)
 static inline int att_measure_mode() {
@@ -407,6 +409,8 @@ static inline int att_measure_mode() {
 // Kernel for `batch` images x `heads` heads of `hd` dims x T tokens under the calling thread's flags and the library options, or LFM_ERR_SHAPE.  Pure host code.
 static inline int attention_choose(int batch, int heads, int hd, int T) {
   if (hd != 64 && hd != 72) return LFM_ERR_SHAPE;
+  const int tiled = lfm_attention_tiled_mode();  // LFM_OPT_ATTENTION_TILED: 0 = its shapes refused, 1 = the shapes no other kernel serves, 2 = every shape it takes (parity, A/B)
+  if (tiled == 2 && attention_tiled_takes(hd, T)) return ATT_KERN_TILED;
   if (hd == 64 && T == 256) {  // the benchmarked shape
     // Rounds 1-3: 8 waves x 32 queries (4 waves/SIMD) measured 44.3 us vs 40.2 us for 4 waves x 64 queries (two 8-byte V^T reads per fragment then).
     // Round 4: with the V^T operand a single conflict-free ds_read_b128 (vt_pos) the balance flipped -- 8 waves x 32 queries (126 VGPRs: four waves per
@@ -421,6 +425,7 @@ static inline int attention_choose(int batch, int heads, int hd, int T) {
   if (T == 16) return ATT_KERN_T16;
   if (T == 1024) return ATT_KERN_CHUNKS;
   if (T == 64 || T == 128 || T == 256) return ATT_KERN_ITEM;
+  if (tiled && attention_tiled_default(hd, T)) return ATT_KERN_TILED;  // the other square grids of a side that is a multiple of 4, 144 .. 3600 tokens
   return LFM_ERR_SHAPE;
 }
 
@@ -455,7 +460,7 @@ static int att_with_mode(F&& f) {
   return f(std::integral_constant<int, 0>{});
 }
 
-// Q, K: [batch*T, heads*hd] token-major; Vt: [batch][heads*hd][T]; O: [batch*T, heads*hd].  hd 64 / 72; T in {16, 64, 128, 256, 1024}.
+// Q, K: [batch*T, heads*hd] token-major; Vt: [batch][heads*hd][T]; O: [batch*T, heads*hd].  hd 64 / 72; T in {16, 64, 128, 256, 1024} or what attention_tiled_default says.
 static int attention_launch(const half_t* Q, const half_t* K, const half_t* Vt, half_t* O, int batch, int heads, int hd, int T, hipStream_t st) {
   const int kern = attention_choose(batch, heads, hd, T);
   if (kern < 0) return kern;
@@ -472,6 +477,7 @@ static int attention_launch(const half_t* Q, const half_t* K, const half_t* Vt, 
     case ATT_KERN_QSPLIT: a.stag = 0; return att_run<256, 1, 64, 0, 1, 2>(a);
     case ATT_KERN_STREAM: return att_with_mode([&](auto m) { return attention_stream_launch<decltype(m)::value>(Q, K, Vt, O, batch, heads, st); });
     case ATT_KERN_WIDE: return att_with_mode([&](auto m) { return att_run<256, 2, 64, decltype(m)::value>(a); });
+    case ATT_KERN_TILED: return hd == 64 ? attention_tiled_run<64>(Q, K, Vt, O, batch, heads, T, a.sl2, st) : attention_tiled_run<72>(Q, K, Vt, O, batch, heads, T, a.sl2, st);
   }
   // ATT_KERN_ITEM.  hd 72: one query block per wave (48 accumulator + 20 Q registers per block)
   if (hd == 72) return T == 64 ? att_run<64, 1, 72>(a) : T == 128 ? att_run<128, 1, 72>(a) : att_run<256, 1, 72>(a);

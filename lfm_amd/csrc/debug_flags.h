@@ -73,4 +73,5 @@ int lfm_gemm_prefers_v4(int M, int N, int K);  // shapes where the 256x128 two-w
 int lfm_gemm_v6_default();      // 1: chip-filling row-major GEMMs with K % 64 == 0 take kernel 6 instead of 5 (LFM_OPT_GEMM_V6)
 int lfm_stagger_ticks();        // measurement builds (lfm_set_option key 3): s_memtime ticks by which workgroups 256..511 of a co-resident-pair kernel start late; else 0
 int lfm_attention_stream_enabled();  // LFM_OPT_ATTENTION_STREAM
+int lfm_attention_tiled_mode();     // LFM_OPT_ATTENTION_TILED: 0 never, 1 the DiT token counts no other attention kernel serves, 2 every shape it takes
 int lfm_unet_attention_stream_mode();  // LFM_OPT_UNET_ATTENTION_STREAM: 0 never, 1 the shapes no other UNet attention kernel serves, 2 every shape it takes

@@ -24,6 +24,7 @@ static struct {
   Opt stagger{0};     // measurement builds, lfm_set_option key 3
   Opt att_stream{1};  // LFM_OPT_ATTENTION_STREAM: 256 tokens x head_dim 64 with more than 64 (image, head) items on the persistent streamed kernel
   Opt fused_qkv{1};   // LFM_OPT_FUSED_QKV_ATTENTION: folded path at 256 tokens x head_dim 64: QKV projection + attention in one kernel (qkv_attention_kernel.h)
+  Opt att_tiled{1};   // LFM_OPT_ATTENTION_TILED: DiT attention at the token counts no other kernel serves on the tiled any-T kernel (attention_tiled_kernel.h); 2: every shape it takes
   Opt unet_att_stream{1};  // LFM_OPT_UNET_ATTENTION_STREAM: UNet attention shapes neither the resident nor the VALU kernel serves on the streamed kernel (ops.hip: unet_attention_choose)
 } g_def;
 static thread_local int tl_sel_set = 0, tl_gemm_sel = 0, tl_gemm_dbg = 0;  // per-call kernel selection active on this thread
@@ -45,6 +46,7 @@ int lfm_gemm_prefers_v4(int M, int N, int K) {  // no shape today: only the A/B 
 int lfm_gemm_v6_default() { return opt_get(g_def.v6); }
 int lfm_stagger_ticks() { return opt_get(g_def.stagger); }
 int lfm_attention_stream_enabled() { return opt_get(g_def.att_stream); }
+int lfm_attention_tiled_mode() { return opt_get(g_def.att_tiled); }
 int lfm_unet_attention_stream_mode() { return opt_get(g_def.unet_att_stream); }
 // Which kernel launch_gemm_auto runs for a shape under the calling thread's selection (host only, no GPU needed): caps bit 0 = the instantiation can take
 // kernel 6 (row-major A, no per-lane tile accumulators in the epilogue), bit 1 = the operands fit 32-bit buffer offsets.
@@ -98,6 +100,10 @@ extern "C" int lfm_set_option(int key, int value) {
     case 5: opt_set(g_def.att_stream, value != 0); break;  // LFM_OPT_ATTENTION_STREAM: 0 = one workgroup per (image, head) item (the rounds 1-5 kernel; A/B and the bit-equality test)
     case 6: opt_set(g_def.fused_qkv, value != 0); break;   // LFM_OPT_FUSED_QKV_ATTENTION: 0 = the QKV GEMM and the attention kernel as two launches (A/B and the bit-equality test)
     case 7: opt_set(g_def.unet_att_stream, value < 0 || value > 2 ? 1 : value); break;  // LFM_OPT_UNET_ATTENTION_STREAM: 0 = those shapes refused (as before the kernel), 2 = every shape it takes (parity, A/B)
+    case 8:  // LFM_OPT_ATTENTION_TILED: 0 = the token counts only the tiled kernel serves are refused (as before the kernel), 2 = every shape it takes (parity, A/B)
+      if (value < 0 || value > 2) return LFM_ERR_ARG;
+      opt_set(g_def.att_tiled, value);
+      break;
     default: return LFM_ERR_ARG;
   }
   return LFM_OK;
@@ -201,8 +207,9 @@ static int check_shape(const lfm_dit_shape* s) {
   if (s->hidden % s->heads) return LFM_ERR_SHAPE;
   if (s->res % s->patch) return LFM_ERR_SHAPE;
   const int T = (s->res / s->patch) * (s->res / s->patch);
-  // an attention kernel for (head_dim, tokens) -- S / B / L: 64; XL: 1152 / 16 = 72; LDS-resident K / V^T up to 256 tokens, 1024 = four key chunks (the answer
-  // for ONE image: whether a shape is served does not depend on the batch)
+  // an attention kernel for (head_dim, tokens) -- S / B / L: 64; XL: 1152 / 16 = 72; LDS-resident K / V^T up to 256 tokens, 1024 = four key chunks, the other
+  // square grids of a side that is a multiple of 4 up to 3600 tokens on the tiled kernel (the answer for ONE image: whether a shape is served does not
+  // depend on the batch)
   if (attention_choose(1, s->heads, s->hidden / s->heads, T) < 0) return LFM_ERR_SHAPE;
   if (s->hidden % 64 || s->hidden > 256 * LN_MAXV || s->mlp_hidden % 64) return LFM_ERR_SHAPE;
   const int kk = s->patch * s->patch * s->in_ch;

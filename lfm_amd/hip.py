@@ -1,5 +1,6 @@
 """ctypes binding of liblfm_hip.so (C ABI: include/lfm_hip.h).  Fails loudly -- no fallback."""
 import ctypes as C
+import math
 import os
 
 import torch
@@ -321,6 +322,7 @@ OPT_SKINNY_GEMM = 4  # batch-1 DiT linears on the latency-mode kernels (1, defau
 OPT_ATTENTION_STREAM = 5  # 256-token hd-64 attention on persistent workgroups with an LDS ring of K / V^T stages (csrc/attention_stream_kernel.h), default on; 0: one workgroup per item
 OPT_FUSED_QKV_ATTENTION = 6  # folded path, 256 tokens x hd 64: QKV projection + attention in one kernel (csrc/qkv_attention_kernel.h), default on; 0: two kernels
 OPT_UNET_ATTENTION_STREAM = 7  # UNet attention shapes beyond the resident and the VALU kernel on the streamed kernel (csrc/unet_attention_stream_kernel.h), default 1; 0: refused; 2: every shape it takes
+OPT_ATTENTION_TILED = 8  # DiT attention at the token counts no other kernel serves on the tiled any-T kernel (csrc/attention_tiled_kernel.h), default 1; 0: refused; 2: every shape it takes
 OPT_GEMM_V6 = 2  # chip-filling row-major GEMMs on the one-wave-per-SIMD 256x256 kernel (csrc/gemm256w_kernel.h) instead of the 8-wave one
 
 
@@ -365,9 +367,24 @@ def gemm_plan(M, N, K, batch=1, caps=GEMM_CAP_V6 | GEMM_CAP_FITS):
 
 
 def attention_plan(batch, heads, head_dim, T):
-    """The kernel id (1 .. 6, include/lfm_hip.h: lfm_attention_plan) dit_attention runs for this shape under the calling thread's flags and the library
-    options, or LFM_ERR_SHAPE (-1) for a shape no kernel serves (no launch, no GPU needed)."""
+    """The kernel id (1 .. 7, include/lfm_hip.h: lfm_attention_plan; 7 = the tiled any-T kernel) dit_attention runs for this shape under the calling thread's
+    flags and the library options (OPT_ATTENTION_STREAM, OPT_ATTENTION_TILED), or LFM_ERR_SHAPE (-1) for a shape no kernel serves (no launch, no GPU needed)."""
     return lib().lfm_attention_plan(int(batch), int(heads), int(head_dim), int(T))
+
+
+DIT_RESIDENT_TOKENS = (16, 64, 128, 256, 1024)  # token counts of the kernels with K / V^T resident in the LDS (csrc/attention_kernel.h)
+
+
+def dit_tokens_served(tokens):
+    """Whether a DiT attention kernel serves `tokens` tokens per image under the default library options (csrc/attention_kernel.h: attention_choose, for
+    head_dim 64 / 72): the resident kernels' 16 / 64 / 128 / 256 / 1024, or -- the tiled kernel -- the square of a grid side that is a multiple of 4
+    with 144 <= tokens <= 3600.  Pure Python (a model is constructed without the library); tests/test_dit_attention_tiled_ref.py holds it against
+    lfm_attention_plan."""
+    tokens = int(tokens)
+    if tokens in DIT_RESIDENT_TOKENS:
+        return True
+    side = math.isqrt(tokens) if tokens > 0 else 0
+    return side * side == tokens and side % 4 == 0 and 144 <= tokens <= 3600
 
 
 CONV_PLAN_HALO, CONV_PLAN_SPLITK, CONV_PLAN_GEMM = 1, 2, 3  # lfm_conv3x3_plan
@@ -406,7 +423,8 @@ def vt_token_perm(T, device=None):
 
 
 def dit_attention(Q, K, Vt, batch, heads, T, head_dim=64):
-    """Q, K, O: fp16 [batch*T, heads*head_dim]; Vt: fp16 [batch, heads, head_dim, T] in the library's token order (vt_token_perm).  head_dim 64 or 72."""
+    """Q, K, O: fp16 [batch*T, heads*head_dim]; Vt: fp16 [batch, heads, head_dim, T] in the library's token order (vt_token_perm).  head_dim 64 or 72;
+    T as dit_tokens_served says (attention_plan names the kernel)."""
     require_gpu(Q, "dit_attention")
     O = torch.empty_like(Q)
     check(lib().lfm_dit_attention_hd(ptr(Q), ptr(K), ptr(Vt), ptr(O), batch, heads, head_dim, T, stream_ptr()), "lfm_dit_attention_hd")
