@@ -6,20 +6,15 @@
 // K [T][HD] and V^T [HD][T] of the head are staged once into LDS by LDS-DMA.  K rows are HD * 2 bytes: 128-B rows (hd 64) are
 // XOR-swizzled at the DMA source (chunk' = chunk ^ ((row>>1)&7)); 144-B rows (hd 72) need no swizzle -- 36 dwords per row put 16
 // consecutive rows on 16 disjoint groups of four banks.  V^T rows (2T bytes) are swizzled by row (chunk' = chunk ^ (row & VKEY)).
-// S^T = K Q^T on v_mfma_f32_32x32x16_f16: a lane then holds, for ONE query (lane&31), the scores of
-// keys kb*32 + 8g + 4*(lane>>5) + r -- row max / row sum are in-lane plus one lane^32 exchange, and the
-// fp32->fp16 packed P registers are directly the B-operand of O^T = V^T P^T (the key order inside an
-// MFMA k-slot is the same permutation on both operands, so no shuffle is needed).
-// hd 72 = 4.5 k-slots of 16: the fifth slot's upper half (dims 72..79) is fed zeros on BOTH operands (LDS past a row end is
-// another row or stale bytes, possibly NaN patterns); O^T has 2.25 blocks of 32 rows: the third block computes 8 live rows.
-// V^T rows hold the tokens of every 16-group in the order 0-3, 8-11, 4-7, 12-15 (gemm_kernel.h: vt_pos), which makes a lane's P V operand one 16-byte read.
+// The arithmetic is attention_common.h's, one text for all four MFMA kernels: S^T = K Q^T on v_mfma_f32_32x32x16_f16 (att_qk_block: a lane then holds the scores
+// of ONE query, so row max / row sum are in-lane plus one lane^32 exchange, and the fp32->fp16 packed P registers are directly the B-operand of O^T = V^T P^T,
+// att_pv_block: the key order inside an MFMA k-slot is the same permutation on both operands, so no shuffle is needed), the zero-fed half k-slot of hd 72
+// (O^T has 2.25 blocks of 32 rows: the third block computes 8 live rows), V^T rows in the vt_pos token order (gemm_kernel.h), which makes a lane's P V operand
+// one 16-byte read.  This file owns the LDS image, the staging and the schedule.
 // Keys are consumed in 32-key blocks with an online softmax (running max m, running sum l), which keeps
 // the live state at S 32 + P 16 + O 64 + Q 32 registers for hd 64, JQ 2 (2 waves / SIMD).
 #pragma once
-#include <type_traits>
 #include "attention_common.h"
-#include "attention_stream_kernel.h"  // attention_launch runs its kernel too
-#include "attention_tiled_kernel.h"   // ... and the any-T kernel
 
 // MODE 3 (measurement only): s_memtime stamps of wave 0 of the first workgroup (slots 0..31) and of the last one (32..63), read back with
 // lfm_attention_trace_read.  Slots: 0 start, 1 all DMAs / Q loads issued, 2 K and Q landed (first barrier), 3 + 4 k + {0: S(next) issued,
@@ -80,28 +75,13 @@ __global__ __launch_bounds__((T / (32 * JQ * QS)) * 64, HD == 64 && QS == 1 ? (T
   const int head = blockIdx.x, img = blockIdx.y;
   const bool tr_first = blockIdx.x == 0 && blockIdx.y == 0, tr_last = blockIdx.x == gridDim.x - 1 && blockIdx.y == gridDim.y - 1;
   auto stamp = [&](int slot) {
-    if constexpr (MODE == 3) {
-      if (wave == 0 && (tr_first || tr_last)) {
-        unsigned long long t;
-        asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory");
-        if (lane == 0) att_trace[(tr_first ? 0 : 32) + slot] = t;
-      }
-    }
+    if constexpr (MODE == 3)
+      if (wave == 0 && (tr_first || tr_last)) att_stamp((tr_first ? 0 : 32) + slot, lane);
   };
   stamp(0);
   auto wg_stamp = [&](int slot) {
-    if constexpr (MODE == 3) {
-      const int lin = blockIdx.y * gridDim.x + blockIdx.x;
-      if (wave == 0 && lin < ATT_WG_TRACE) {
-        unsigned long long t;
-        asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory");
-        if (slot == 0) {
-          const unsigned hw = __builtin_amdgcn_s_getreg((31 << 11) | 4), xcc = __builtin_amdgcn_s_getreg((31 << 11) | 20);
-          if (lane == 0) att_wg_trace[lin][0] = (unsigned long long)hw | ((unsigned long long)xcc << 32);
-        }
-        if (lane == 0) att_wg_trace[lin][slot + 1] = t;
-      }
-    }
+    if constexpr (MODE == 3)
+      if (wave == 0) att_wg_stamp(blockIdx.y * gridDim.x + blockIdx.x, slot, lane);
   };
   wg_stamp(0);
   const int qblk = NCH > 1 ? (int)blockIdx.z : 0;
@@ -149,16 +129,9 @@ __global__ __launch_bounds__((T / (32 * JQ * QS)) * 64, HD == 64 && QS == 1 ? (T
   stage_k(0, tid);
   const int q0 = ((QS > 1 ? (int)blockIdx.z * NW : 0) + wave) * 32 * JQ;
   const int hsel = lane >> 5, l31 = lane & 31;
-  const half8_t zero8 = {0, 0, 0, 0, 0, 0, 0, 0};
   half8_t qf[JQ][KS];
 #pragma unroll
-  for (int jq = 0; jq < JQ; ++jq)
-#pragma unroll
-    for (int ks = 0; ks < KS; ++ks) {
-      const half_t* qp = Q + ((long)img * TT + qblk * T + q0 + jq * 32 + l31) * D + head * HD;
-      if (ks * 16 + 16 <= HD) qf[jq][ks] = *(const half8_t*)(qp + ks * 16 + hsel * 8);
-      else qf[jq][ks] = hsel ? zero8 : *(const half8_t*)(qp + ks * 16);
-    }
+  for (int jq = 0; jq < JQ; ++jq) att_load_q<HD>(qf[jq], Q + ((long)img * TT + qblk * T + q0 + jq * 32 + l31) * D + head * HD, hsel);
   stage_v(0, tid);
 
   if constexpr (MODE == 1) {  // everything has landed -> one output row per query, straight from the Q registers
@@ -193,25 +166,12 @@ __global__ __launch_bounds__((T / (32 * JQ * QS)) * 64, HD == 64 && QS == 1 ? (T
   stamp(2);
   wg_stamp(1);
 
-  f32x16 zero16;
-#pragma unroll
-  for (int e = 0; e < 16; ++e) zero16[e] = 0.f;
-  // S^T block kb: 32 keys x 32 JQ queries (the first MFMA takes a shared all-zero C: no per-block accumulator clears)
+  // S^T block kb: 32 keys x 32 JQ queries (att_qk_block, attention_common.h)
   auto qk = [&](f32x16 (&S)[JQ], int kb) {
     const int row = kb * 32 + l31;
     const int key = KSWZ ? ((row >> 1) & 7) : 0;
     const char* kp = Ks + row * KROW;
-#pragma unroll
-    for (int ks = 0; ks < KS; ++ks) {
-      half8_t kf;
-      if (ks * 16 + 16 <= HD) kf = *(const half8_t*)(kp + (((ks * 2 + hsel) ^ key) << 4));
-      else {  // half slot: the upper 8 dims do not exist
-        kf = *(const half8_t*)(kp + (ks * 2 << 4));
-        kf = hsel ? zero8 : kf;
-      }
-#pragma unroll
-      for (int jq = 0; jq < JQ; ++jq) S[jq] = __builtin_amdgcn_mfma_f32_32x32x16_f16(kf, qf[jq][ks], ks == 0 ? zero16 : S[jq], 0, 0, 0);
-    }
+    att_qk_block<HD, JQ>(S, qf, hsel, [&](int ks) { return kp + ((att_k_chunk<HD>(ks, hsel) ^ key) << 4); });
   };
   // online softmax update for the queries this lane owns, then O^T[d][q] += sum_key V^T[d][key] P[q][key].
   // VALU diet (the kernel is VALU-issue-bound: ~1.9k VALU per wave vs 128 MFMAs): 3-input max, packed fp32 FMA / ADD on
@@ -229,20 +189,10 @@ __global__ __launch_bounds__((T / (32 * JQ * QS)) * 64, HD == 64 && QS == 1 ? (T
       asm volatile("" ::: "memory");
       stamp(22);
     }
-#pragma unroll
-    for (int s = 0; s < 2; ++s) {
-#pragma unroll
-      for (int db = 0; db < NDB; ++db) {
-        // rows past HD (third block of hd 72) re-read row HD-1: finite values into accumulator rows nobody stores
-        const int d = (db * 32 + 32 <= HD) ? db * 32 + l31 : (db * 32 + l31 < HD ? db * 32 + l31 : HD - 1);
-        const int vkey = d & VKEY;
-        // keys {4 h + r} and {8 + 4 h + r} of the 16-key k-slot are ONE 16-byte chunk of the permuted V^T row (gemm_kernel.h: vt_pos): chunk 2 (2 kb + s) + h
-        const int c0 = kb * 4 + 2 * s + hsel;
-        const half8_t vf = *(const half8_t*)(Vs + d * (2 * T) + ((c0 ^ vkey) << 4));
-#pragma unroll
-        for (int jq = 0; jq < JQ; ++jq) Oa[jq][db] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vf, P[jq][s], Oa[jq][db], 0, 0, 0);
-      }
-    }
+    att_pv_block<NDB, JQ>(Oa, P, [&](int s, int db) {  // chunk 4 kb + 2 s + hsel of the lane's V^T row
+      const int d = att_v_row<HD>(db, l31);
+      return Vs + d * (2 * T) + (((kb * 4 + 2 * s + hsel) ^ (d & VKEY)) << 4);
+    });
     if (kb == 0) stamp(23);
   };
   // software pipeline over the key blocks: the S MFMAs of block kb+1 are issued BEFORE the softmax VALU of block kb, so
@@ -276,51 +226,30 @@ __global__ __launch_bounds__((T / (32 * JQ * QS)) * 64, HD == 64 && QS == 1 ? (T
       stamp(6 + 2 * kb);
     }
   }
-  // ---- normalise and store: lane owns query q, d = db*32 + 8g + 4*hsel + r
+  // ---- normalise and store (att_normalised, attention_common.h)
   if constexpr (HD == 64 && MODE == 0) {
     // Round 4: through the LDS (K / V^T are dead) so that a store instruction covers eight whole 128-byte output rows instead of 64 scattered 8-byte
     // pieces (the store drain was ~5k of a workgroup's ~33k cycles, profiles/r03_attention_wg_timeline.txt; MI355X guide T21).  Per-wave region of
-    // 32 JQ rows x 144 B (128 B of data; the 36-dword stride keeps the 16 lanes of a ds_write_b64 group on distinct banks).
+    // 32 JQ padded rows (att_ostage_*, attention_common.h).
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();  // every wave has finished reading K / V^T
     asm volatile("" ::: "memory");
-    char* ob = smem + wave * (32 * JQ * 144);
+    unsigned tid_l = threadIdx.x;  // laundered: the staging addresses are functions of the thread id that the compiler would otherwise compute up front and keep
+    asm volatile("" : "+v"(tid_l));  // -- spilled, in the chunked kernel -- across the key loop
+    const int ln = tid_l & 63;
+    char* ob = smem + (tid_l >> 6) * (32 * JQ * ATT_OSTR<HD>);
 #pragma unroll
-    for (int jq = 0; jq < JQ; ++jq) {
-      const float inv = 1.0f / (lrun[jq] + xhalf(lrun[jq]));
-#pragma unroll
-      for (int db = 0; db < NDB; ++db)
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-          half4_t h = {(half_t)(Oa[jq][db][4 * g] * inv), (half_t)(Oa[jq][db][4 * g + 1] * inv), (half_t)(Oa[jq][db][4 * g + 2] * inv),
-                       (half_t)(Oa[jq][db][4 * g + 3] * inv)};
-          *(half4_t*)(ob + (jq * 32 + l31) * 144 + (db * 32 + 8 * g + 4 * hsel) * 2) = h;
-        }
-    }
+    for (int jq = 0; jq < JQ; ++jq)
+      att_normalised<HD>(Oa[jq], att_inv_l(lrun[jq]), [&](int db, int g, half4_t h) { att_ostage_put<HD>(ob, jq * 32 + (ln & 31), ln >> 5, db, g, h); });
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // wave-private region: no barrier
-    half_t* obase = O + ((long)img * TT + qblk * T + q0) * D + head * HD;
-#pragma unroll
-    for (int i = 0; i < 4 * JQ; ++i) {
-      const int row = i * 8 + (lane >> 3), ch = lane & 7;
-      const half8_t v = *(const half8_t*)(ob + row * 144 + ch * 16);
-      *(half8_t*)(obase + (long)row * D + ch * 8) = v;
-    }
+    att_ostage_store<HD, 32 * JQ>(ob, O + ((long)img * TT + qblk * T + q0) * D + head * HD, D, ln, 32 * JQ);
     stamp(19);
     return;
   }
 #pragma unroll
-  for (int jq = 0; jq < JQ; ++jq) {
-    const float inv = 1.0f / (lrun[jq] + xhalf(lrun[jq]));
+  for (int jq = 0; jq < JQ; ++jq) {  // straight from the registers, 8-byte pieces
     half_t* orow = O + ((long)img * TT + qblk * T + q0 + jq * 32 + l31) * D + head * HD;
-#pragma unroll
-    for (int db = 0; db < NDB; ++db)
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        if (db * 32 + 8 * g >= HD) continue;  // HD % 8 == 0: an 8-row group is live or dead as a whole
-        half4_t h = {(half_t)(Oa[jq][db][4 * g] * inv), (half_t)(Oa[jq][db][4 * g + 1] * inv), (half_t)(Oa[jq][db][4 * g + 2] * inv),
-                     (half_t)(Oa[jq][db][4 * g + 3] * inv)};
-        *(half4_t*)(orow + db * 32 + 8 * g + 4 * hsel) = h;
-      }
+    att_normalised<HD>(Oa[jq], att_inv_l(lrun[jq]), [&](int db, int g, half4_t h) { *(half4_t*)(orow + db * 32 + 8 * g + 4 * hsel) = h; });
   }
   stamp(19);
   if constexpr (MODE == 3) {
@@ -385,102 +314,4 @@ __global__ __launch_bounds__(64) void dit_attention_t16_kernel(const half_t* __r
     }
     *(half8_t*)(op + c * 8) = o8;
   }
-}
-
-// ---- dispatch.  attention_choose is the ONE place that knows which kernel serves a shape (lfm_attention_plan returns its answer without a launch:
-// tests/test_host_logic.py pins the table); attention_launch runs that answer.
-enum {
-  ATT_KERN_T16 = 1,     // dit_attention_t16_kernel
-  ATT_KERN_ITEM = 2,    // one workgroup per (image, head): 64 / 128 / 256 tokens
-  ATT_KERN_WIDE = 3,    // the same with four waves x 64 queries (flag ATT_WIDE; hd 64, 256 tokens)
-  ATT_KERN_CHUNKS = 4,  // 1024 tokens: four key chunks of 256 through the LDS, one workgroup per 256 queries
-  ATT_KERN_QSPLIT = 5,  // latency mode (hd 64, 256 tokens, at most 64 items): two workgroups of four waves per item
-  ATT_KERN_STREAM = 6,  // attention_stream_kernel.h (hd 64, 256 tokens, more than 64 items): persistent workgroups, K / V^T streamed through an LDS ring
-  ATT_KERN_TILED = 7,   // attention_tiled_kernel.h: any T % 16 == 0 as a runtime argument, 128 queries per workgroup, keys in 64-key stages through an LDS ring
-};
-// the measurement-only variants MODE 1 / 2 / 3 of the hd-64, 256-token kernels (product builds have none)
-static inline int att_measure_mode() {
-#ifdef LFM_MEASURE
-  return (lfm_gemm_debug_flags() >> LFM_DBG_ATT_MODE_SHIFT) & LFM_DBG_ATT_MODE_MASK;
-#else
-  return 0;
-#endif
-}
-// Kernel for `batch` images x `heads` heads of `hd` dims x T tokens under the calling thread's flags and the library options, or LFM_ERR_SHAPE.  Pure host code.
-static inline int attention_choose(int batch, int heads, int hd, int T) {
-  if (hd != 64 && hd != 72) return LFM_ERR_SHAPE;
-  const int tiled = lfm_attention_tiled_mode();  // LFM_OPT_ATTENTION_TILED: 0 = its shapes refused, 1 = the shapes no other kernel serves, 2 = every shape it takes (parity, A/B)
-  if (tiled == 2 && attention_tiled_takes(hd, T)) return ATT_KERN_TILED;
-  if (hd == 64 && T == 256) {  // the benchmarked shape
-    // Rounds 1-3: 8 waves x 32 queries (4 waves/SIMD) measured 44.3 us vs 40.2 us for 4 waves x 64 queries (two 8-byte V^T reads per fragment then).
-    // Round 4: with the V^T operand a single conflict-free ds_read_b128 (vt_pos) the balance flipped -- 8 waves x 32 queries (126 VGPRs: four waves per
-    // SIMD) 35.7 us, 4 waves x 64 queries (228 VGPRs: two) 38.9 us -- so the narrow shape is the default; flag ATT_WIDE selects the wide one (A/B)
-    if (lfm_gemm_debug_flags() & LFM_DBG_ATT_WIDE) return ATT_KERN_WIDE;
-    const int items = batch * heads;
-    if (items <= 64 && !att_measure_mode()) return ATT_KERN_QSPLIT;  // (it has no measurement variants: a mode runs the per-item kernel's)
-    // the streamed kernel addresses each of Q, K, V^T, O with 32-bit buffer offsets whose bit 31 is its out-of-range mark: tensors below 2 GiB only
-    if (items > 64 && lfm_attention_stream_enabled() && (long)items * 256 * 64 * 2 < (1L << 31)) return ATT_KERN_STREAM;
-    return ATT_KERN_ITEM;
-  }
-  if (T == 16) return ATT_KERN_T16;
-  if (T == 1024) return ATT_KERN_CHUNKS;
-  if (T == 64 || T == 128 || T == 256) return ATT_KERN_ITEM;
-  if (tiled && attention_tiled_default(hd, T)) return ATT_KERN_TILED;  // the other square grids of a side that is a multiple of 4, 144 .. 3600 tokens
-  return LFM_ERR_SHAPE;
-}
-
-struct AttArgs {  // what every launch below passes on
-  const half_t *Q, *K, *Vt;
-  half_t* O;
-  int batch, heads;
-  float sl2;  // hd^-0.5 * log2(e)
-  int stag;   // measurement builds: start offset of the second resident workgroups
-  hipStream_t st;
-};
-// One instantiation of dit_attention_kernel: grid, block and LDS size are what its template arguments say.
-template <int T, int JQ, int HD, int MODE = 0, int NCH = 1, int QS = 1>
-static int att_run(const AttArgs& a) {
-  constexpr int LDS = T * HD * 4;  // K + V^T, 2 bytes each (hd 72: 72 KiB, above the 64-KiB default)
-  if (!lfm_kernel_lds<&dit_attention_kernel<T, JQ, HD, MODE, NCH, QS>>(LDS)) return LFM_ERR_LAUNCH;
-  hipLaunchKernelGGL((dit_attention_kernel<T, JQ, HD, MODE, NCH, QS>), dim3(a.heads, a.batch, NCH * QS), dim3(T / (32 * JQ * QS) * 64), LDS, a.st, a.Q, a.K, a.Vt,
-                     a.O, a.heads * HD, a.heads, a.sl2, a.stag);
-  LFM_CHECK_LAUNCH();
-  return LFM_OK;
-}
-// f(std::integral_constant<int, MODE>) for the calling thread's measurement mode
-template <class F>
-static int att_with_mode(F&& f) {
-#ifdef LFM_MEASURE
-  switch (att_measure_mode()) {
-    case 1: return f(std::integral_constant<int, 1>{});
-    case 2: return f(std::integral_constant<int, 2>{});
-    case 3: return f(std::integral_constant<int, 3>{});
-  }
-#endif
-  return f(std::integral_constant<int, 0>{});
-}
-
-// Q, K: [batch*T, heads*hd] token-major; Vt: [batch][heads*hd][T]; O: [batch*T, heads*hd].  hd 64 / 72; T in {16, 64, 128, 256, 1024} or what attention_tiled_default says.
-static int attention_launch(const half_t* Q, const half_t* K, const half_t* Vt, half_t* O, int batch, int heads, int hd, int T, hipStream_t st) {
-  const int kern = attention_choose(batch, heads, hd, T);
-  if (kern < 0) return kern;
-  AttArgs a{Q, K, Vt, O, batch, heads, (hd == 64 ? 0.125f : 0.11785113019775793f) * 1.4426950408889634f, lfm_stagger_ticks(), st};
-  switch (kern) {
-    case ATT_KERN_T16: {
-      const int items = batch * heads, D = heads * hd;
-      if (hd == 64) hipLaunchKernelGGL(dit_attention_t16_kernel<64>, dim3((items + 3) / 4), dim3(64), 0, st, Q, K, Vt, O, D, heads, items, a.sl2);
-      else hipLaunchKernelGGL(dit_attention_t16_kernel<72>, dim3((items + 3) / 4), dim3(64), 0, st, Q, K, Vt, O, D, heads, items, a.sl2);
-      LFM_CHECK_LAUNCH();
-      return LFM_OK;
-    }
-    case ATT_KERN_CHUNKS: return hd == 64 ? att_run<256, 1, 64, 0, 4>(a) : att_run<256, 1, 72, 0, 4>(a);
-    case ATT_KERN_QSPLIT: a.stag = 0; return att_run<256, 1, 64, 0, 1, 2>(a);
-    case ATT_KERN_STREAM: return att_with_mode([&](auto m) { return attention_stream_launch<decltype(m)::value>(Q, K, Vt, O, batch, heads, st); });
-    case ATT_KERN_WIDE: return att_with_mode([&](auto m) { return att_run<256, 2, 64, decltype(m)::value>(a); });
-    case ATT_KERN_TILED: return hd == 64 ? attention_tiled_run<64>(Q, K, Vt, O, batch, heads, T, a.sl2, st) : attention_tiled_run<72>(Q, K, Vt, O, batch, heads, T, a.sl2, st);
-  }
-  // ATT_KERN_ITEM.  hd 72: one query block per wave (48 accumulator + 20 Q registers per block)
-  if (hd == 72) return T == 64 ? att_run<64, 1, 72>(a) : T == 128 ? att_run<128, 1, 72>(a) : att_run<256, 1, 72>(a);
-  if (T == 256) return att_with_mode([&](auto m) { return att_run<256, 1, 64, decltype(m)::value>(a); });
-  return T == 64 ? att_run<64, 2, 64>(a) : att_run<128, 2, 64>(a);
 }

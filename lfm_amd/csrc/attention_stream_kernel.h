@@ -10,10 +10,9 @@
 // the first barrier after its last reader: K runs three stages ahead of the MFMAs that consume it, V^T two -- across item boundaries, so only the first stage of a
 // workgroup's first item is ever waited for with nothing else to do.
 //
-// Same arithmetic as dit_attention_kernel<256, 1, 64>: eight waves x 32 queries, S^T = K Q^T on v_mfma_f32_32x32x16_f16 (a lane owns one query: row max / row sum
-// are in-lane plus one lane^32 exchange), online softmax over 32-key blocks (att_softmax_block, attention_common.h, shared by both kernels), P rounded to fp16 straight into the
-// B operand of O^T = V^T P^T, V^T rows in the vt_pos token order -- the results are BIT-IDENTICAL to that kernel's (tests/test_gpu_dit.py::
-// test_attention_stream_matches_per_item).
+// Same arithmetic as dit_attention_kernel<256, 1, 64>, eight waves x 32 queries: the S^T block, the online softmax over 32-key blocks, the P V block, the
+// normalisation and the swizzled output staging are attention_common.h's (att_qk_block, att_softmax_block, att_pv_block, att_normalised, att_oswz_*), the one
+// text every MFMA attention kernel inlines -- the results are BIT-IDENTICAL to that kernel's (tests/test_gpu_dit.py::test_attention_stream_matches_per_item).
 //   * every LDS address of the key loop is one of four per-lane registers + an immediate (slot, key block and k-slot are compile-time: the item body is fully unrolled);
 //     K and V^T stages share the swizzle (16-byte chunk c of row r stored at c ^ ((r >> 1) & 7): conflict-free for the 16-lane groups of ds_read_b128), so the SAME
 //     four registers address both;
@@ -49,26 +48,12 @@ __global__ __launch_bounds__(512, 4) void dit_attention_stream_kernel(const half
   [[maybe_unused]] const bool tr_first = blockIdx.x == 0, tr_last = blockIdx.x == gridDim.x - 1;
   [[maybe_unused]] int tr_item = 0;
   auto stamp = [&](int slot) {
-    if constexpr (MODE == 3) {
-      if (wave == 0 && (tr_first || tr_last) && slot < 32) {
-        unsigned long long t;
-        asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory");
-        if (lane == 0) att_trace[(tr_first ? 0 : 32) + slot] = t;
-      }
-    }
+    if constexpr (MODE == 3)
+      if (wave == 0 && (tr_first || tr_last) && slot < 32) att_stamp((tr_first ? 0 : 32) + slot, lane);
   };
   auto wg_stamp = [&](int slot) {
-    if constexpr (MODE == 3) {
-      if (wave == 0 && blockIdx.x < ATT_WG_TRACE) {
-        unsigned long long t;
-        asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory");
-        if (slot == 0) {
-          const unsigned hw = __builtin_amdgcn_s_getreg((31 << 11) | 4), xcc = __builtin_amdgcn_s_getreg((31 << 11) | 20);
-          if (lane == 0) att_wg_trace[blockIdx.x][0] = (unsigned long long)hw | ((unsigned long long)xcc << 32);
-        }
-        if (lane == 0) att_wg_trace[blockIdx.x][slot + 1] = t;
-      }
-    }
+    if constexpr (MODE == 3)
+      if (wave == 0) att_wg_stamp(blockIdx.x, slot, lane);
   };
   stamp(0);
   wg_stamp(0);
@@ -91,13 +76,10 @@ __global__ __launch_bounds__(512, 4) void dit_attention_stream_kernel(const half
 #pragma unroll
   for (int j = 0; j < 4; ++j) fa[j] = (unsigned)(l31 * 128 + ((((j * 2 + hsel) ^ ((l31 >> 1) & 7))) << 4));
   const unsigned qoff = (unsigned)((wave * 32 + l31) * D + hsel * 8) * 2u;
-  // output staging, per wave: pass h holds rows 8 h .. 8 h + 7 of the wave's 32 queries as 128-byte rows, 8-byte position p of row r at p ^ (r << 1)
+  // output staging, per wave: pass h holds rows 8 h .. 8 h + 7 of the wave's 32 queries as swizzled 128-byte rows (att_oswz_*, attention_common.h)
   char* const ob = smem + OSTG + wave * 1024;
-  const unsigned ow = (unsigned)((l31 & 7) * 128);  // + ((c ^ key2) << 3)
-  const unsigned okey2 = (unsigned)((l31 & 7) << 1);
-  const int orow = lane >> 3, och = lane & 7;
-  const unsigned ord0 = (unsigned)(orow * 128 + ((och ^ orow) << 4));
-  const unsigned ooff = (unsigned)((wave * 32 + orow) * D + och * 8) * 2u;
+  const unsigned ord0 = att_oswz_get(lane);
+  const unsigned ooff = (unsigned)((wave * 32 + (lane >> 3)) * D + (lane & 7) * 8) * 2u;
 
   auto item_k = [&](int im, int hd) { return (unsigned)((im * T) * D + hd * HD) * 2u; };   // byte offset of the item's K / Q / O block (row 0, head column 0)
   auto item_v = [&](int im, int hd) { return (unsigned)((im * heads + hd) * HD * T) * 2u; };
@@ -126,34 +108,20 @@ __global__ __launch_bounds__(512, 4) void dit_attention_stream_kernel(const half
   dma_k(kb_cur, true, 2);
   stamp(1);
 
-  f32x16 zero16;
-#pragma unroll
-  for (int e = 0; e < 16; ++e) zero16[e] = 0.f;
   f32x16 Oa[2];
   float mrun, lrun;
 
   // S^T block: 32 keys (block kbl of the stage in `slot`) x the wave's 32 queries
   auto qk = [&](f32x16& S, int slot, int kbl) {
     if constexpr (MODE == 1) return;
-#pragma unroll
-    for (int ks = 0; ks < 4; ++ks) {
-      const half8_t kf = *(const half8_t*)(smem + slot * SLOT + kbl * 4096 + fa[ks]);
-      S = __builtin_amdgcn_mfma_f32_32x32x16_f16(kf, qf[ks], ks == 0 ? zero16 : S, 0, 0, 0);
-    }
+    att_qk_block<HD, 1>(&S, &qf, hsel, [&](int ks) { return smem + slot * SLOT + kbl * 4096 + fa[ks]; });
   };
-  // online softmax of one 32-key block for the query this lane owns, then O^T += V^T P^T
+  // online softmax of one 32-key block for the query this lane owns, then O^T += V^T P^T (chunk 4 kbl + 2 s + hsel of the stage's V^T row)
   auto softmax_pv = [&](f32x16& S, int slot, int kbl, bool first_block) {
     if constexpr (MODE == 1) return;
     half8_t P[2];
     att_softmax_block<2>(S, first_block, mrun, lrun, Oa, scale_log2e, P);
-#pragma unroll
-    for (int s = 0; s < 2; ++s)
-#pragma unroll
-      for (int db = 0; db < 2; ++db) {
-        // keys {4 h + r} and {8 + 4 h + r} of k-slot s are ONE 16-byte chunk of the permuted V^T row (gemm_kernel.h: vt_pos): chunk 4 kbl + 2 s + h of the stage
-        const half8_t vf = *(const half8_t*)(smem + slot * SLOT + VOFF + db * 4096 + fa[kbl * 2 + s]);
-        Oa[db] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vf, P[s], Oa[db], 0, 0, 0);
-      }
+    att_pv_block<2, 1>(&Oa, &P, [&](int s, int db) { return smem + slot * SLOT + VOFF + db * 4096 + fa[kbl * 2 + s]; });
   };
 
   bool first = true;
@@ -228,19 +196,11 @@ __global__ __launch_bounds__(512, 4) void dit_attention_stream_kernel(const half
     // ---- normalise and store: lane owns query (lane & 31), d = db * 32 + 8 g + 4 hsel + r.  Four passes of 8 rows through the wave's staging rows.
     if (tr_item < 2) stamp(14 + 14 * tr_item);
     {
-      const float inv = 1.0f / (lrun + xhalf(lrun));
+      const float inv = att_inv_l(lrun);
       const unsigned obase = kb_cur;
 #pragma unroll
       for (int h = 0; h < 4; ++h) {
-        if ((l31 >> 3) == h) {
-#pragma unroll
-          for (int db = 0; db < 2; ++db)
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-              half4_t hv = {(half_t)(Oa[db][4 * g] * inv), (half_t)(Oa[db][4 * g + 1] * inv), (half_t)(Oa[db][4 * g + 2] * inv), (half_t)(Oa[db][4 * g + 3] * inv)};
-              *(half4_t*)(ob + ow + ((((unsigned)(db * 8 + 2 * g + hsel)) ^ okey2) << 3)) = hv;
-            }
-        }
+        if ((l31 >> 3) == h) att_normalised<HD>(Oa, inv, [&](int db, int g, half4_t hv) { *(half4_t*)(ob + att_oswz_put(l31 & 7, hsel, db, g)) = hv; });
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // wave-private rows: no barrier (the asm is also the COMPILER barrier between the half4 writes and the
                                                             // f32x4 read of the same bytes: without it type-based alias analysis lets the read move up -- measured: wrong rows)
         const f32x4 v = *(const f32x4*)(ob + ord0);

@@ -1,7 +1,7 @@
 // Tiled attention core of a DiT block for ANY token count T with T % 16 == 0 (timm Attention as called at models/DiT.py:120 of the reference):
 // O = softmax(Q K^T * hd^-0.5) V per (image, head) item, head_dim 64 or 72, T a RUNTIME argument.
 //
-// Why another kernel: every kernel behind attention_choose (attention_kernel.h) has its token count as a template argument and the whole K / V^T of an item
+// Why another kernel: every kernel behind attention_choose (attention_dispatch.h) has its token count as a template argument and the whole K / V^T of an item
 // (or a 256-key chunk of it) resident in the LDS -- 16 / 64 / 128 / 256 / 1024 tokens, the grids of 256^2 and 512^2 images.  This one serves the other grids
 // (--image_size 384 = 576 tokens, 192 = 144, 320 = 400, 768 = 2304): only a 64-key STAGE is resident, T is an argument.  Same operands as the other kernels, so
 // the QKV epilogue is unchanged: Q, K, O fp16 [batch * T, D] with head-major columns, V^T fp16 [batch, heads, hd, T] in the vt_pos token order (gemm_kernel.h).
@@ -20,10 +20,10 @@
 //     stage s + 1 has landed", one barrier (which also says that every wave is past its reads of stage s - 1, the slot stage s + 2 overwrites), the DMAs of
 //     stage s + 2, then the two 32-key blocks of stage s.  No vmcnt(0) inside the loop; stages past the item's end are issued out of range (no traffic, but
 //     they COUNT), so the wait is the same to the end.
-//   * operand mapping of the per-item kernel: S^T = K Q^T and O^T = V^T P^T on v_mfma_f32_32x32x16_f16, a lane owns ONE query (lane & 31) and holds its scores
-//     at keys 32 block + 8 g + 4 (lane >> 5) + r in register 4 g + r; att_softmax_block (attention_common.h) per 32-key block; P goes from the score registers
-//     straight into the B operand; the fifth k-slot of hd 72 is fed zeros on both operands; the S MFMAs of both blocks of a stage are issued before the
-//     softmax arithmetic of the first.  Same arithmetic in the same key order as the kernels that own 64 / 128 / 256 / 1024 tokens.
+//   * the arithmetic is attention_common.h's, one text for all kernels (att_load_q, att_qk_block, att_softmax_block, att_pv_block, att_normalised, att_ostage_*:
+//     a lane owns ONE query, lane & 31, and holds its scores at keys 32 block + 8 g + 4 (lane >> 5) + r in register 4 g + r); the S MFMAs of both blocks of a
+//     stage are issued before the softmax arithmetic of the first.  Same key order as the kernels that own 64 / 128 / 256 / 1024 tokens => bit-identical to them
+//     (tests/test_gpu_dit_attention_tiled.py::test_tiled_kernel_on_the_shapes_other_kernels_own).
 //   * every item is addressed through buffer resources of its own -- base = the item's K / V^T block, num_records = its extent, 32-bit offsets inside it (at most
 //     T * D * 2 bytes) -- so no tensor-size limit appears; Q and O rows go through 64-bit pointers.
 // The two tails.  T % 64 is 0 / 16 / 32 / 48, and for a grid side of 4 x odd T % 32 is 16: half a softmax block.
@@ -53,10 +53,9 @@ __global__ __launch_bounds__(256, 2) void dit_attention_tiled_kernel(const half_
   constexpr int KSLOTS = KST * KCH, VSLOTS = HD * 8, SLOTS = KSLOTS + VSLOTS;  // 16-byte DMA slots of a stage: K rows, then V^T rows
   constexpr int NPASS = (SLOTS + NTHR - 1) / NTHR;                            // DMAs per lane and stage: 4 / 5
   constexpr int STAGE = NPASS * NTHR * 16, VOFF = KSLOTS * 16;
-  constexpr int OSTR = HD * 2 + 16;  // output staging row stride (36 / 40 dwords: the 16 lanes of a ds_write_b64 group on distinct banks)
   static_assert(NPASS == 4 || NPASS == 5, "the counted wait below");
   static_assert(KSLOTS % 64 == 0 && SLOTS % 64 == 0, "K / V^T / dead slots change at wave boundaries");
-  static_assert(4 * 32 * OSTR <= 3 * STAGE, "output staging inside the ring");
+  static_assert(4 * 32 * ATT_OSTR<HD> <= 3 * STAGE, "output staging (padded rows, attention_common.h) inside the ring");
   constexpr unsigned POISON = 0x80000000u;  // beyond every num_records below: the DMA fetches nothing and writes zeros
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x, lane = tid & 63;
@@ -108,43 +107,25 @@ __global__ __launch_bounds__(256, 2) void dit_attention_tiled_kernel(const half_
   // fragments (in front of the loop) then leaves the two stages behind them in flight.
   const int q0 = qb * QB + wave * 32;
   const bool wave_live = q0 < T;  // wave-uniform
-  const half8_t zero8 = {0, 0, 0, 0, 0, 0, 0, 0};
   half8_t qf[KS];
-  {
-    const int qrow = q0 + l31 < T ? q0 + l31 : T - 1;
-    const half_t* qp = Q + ((long)img * T + qrow) * D + head * HD;
-#pragma unroll
-    for (int ks = 0; ks < KS; ++ks) {
-      if (ks * 16 + 16 <= HD) qf[ks] = *(const half8_t*)(qp + ks * 16 + hsel * 8);
-      else qf[ks] = hsel ? zero8 : *(const half8_t*)(qp + ks * 16);
-    }
-  }
+  att_load_q<HD>(qf, Q + ((long)img * T + (q0 + l31 < T ? q0 + l31 : T - 1)) * D + head * HD, hsel);
   issue(0, 0);
   issue(1, 1);
 #pragma unroll
   for (int ks = 0; ks < KS; ++ks) asm volatile("" : "+v"(qf[ks]));  // the compiler's wait for the fragments goes HERE, counted (in front of a loop it drains everything)
 
-  f32x16 Oa[NDB], zero16;
+  f32x16 Oa[NDB];
 #pragma unroll
-  for (int e = 0; e < 16; ++e) zero16[e] = 0.f;
+  for (int db = 0; db < NDB; ++db)
 #pragma unroll
-  for (int db = 0; db < NDB; ++db) Oa[db] = zero16;
+    for (int e = 0; e < 16; ++e) Oa[db][e] = 0.f;
   float mrun = -3.0e38f, lrun = 0.f;
 
   // S^T block kbl of the stage at Ks: 32 keys x the wave's 32 queries
   const int kkey = KSWZ ? ((l31 >> 1) & 7) : 0;
   auto qk = [&](f32x16& S, const char* Ks, int kbl) {
     const char* kp = Ks + (kbl * 32 + l31) * KROW;
-#pragma unroll
-    for (int ks = 0; ks < KS; ++ks) {
-      half8_t kf;
-      if (ks * 16 + 16 <= HD) kf = *(const half8_t*)(kp + (((ks * 2 + hsel) ^ kkey) << 4));
-      else {  // half slot: dims 72 .. 79 do not exist (the bytes there are the next row's)
-        kf = *(const half8_t*)(kp + (ks * 2 << 4));
-        kf = hsel ? zero8 : kf;
-      }
-      S = __builtin_amdgcn_mfma_f32_32x32x16_f16(kf, qf[ks], ks == 0 ? zero16 : S, 0, 0, 0);
-    }
+    att_qk_block<HD, 1>(&S, &qf, hsel, [&](int ks) { return kp + ((att_k_chunk<HD>(ks, hsel) ^ kkey) << 4); });
   };
   // online softmax of the block for the query this lane owns, then O^T += V^T P^T.  `half_blk`: only the block's first 16 keys exist.
   auto softmax_pv = [&](f32x16& S, const char* Ks, int kbl, bool first, bool half_blk) {
@@ -153,16 +134,10 @@ __global__ __launch_bounds__(256, 2) void dit_attention_tiled_kernel(const half_
       if (half_blk) S[e] = -__builtin_inff();
     half8_t P[2];
     att_softmax_block<NDB>(S, first, mrun, lrun, Oa, scale_log2e, P);
-#pragma unroll
-    for (int s = 0; s < 2; ++s)
-#pragma unroll
-      for (int db = 0; db < NDB; ++db) {
-        // rows past HD (third block of hd 72) re-read row HD - 1: finite values into accumulator rows nobody stores
-        const int d = (db * 32 + 32 <= HD) ? db * 32 + l31 : (db * 32 + l31 < HD ? db * 32 + l31 : HD - 1);
-        // keys {4 h + r} and {8 + 4 h + r} of a 16-key k-slot are ONE 16-byte chunk of the permuted V^T row (vt_pos): chunk 4 kbl + 2 s + h of the stage
-        const half8_t vf = *(const half8_t*)(Ks + VOFF + d * 128 + (((kbl * 4 + 2 * s + hsel) ^ ((d >> 1) & 7)) << 4));
-        Oa[db] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vf, P[s], Oa[db], 0, 0, 0);
-      }
+    att_pv_block<NDB, 1>(&Oa, &P, [&](int s, int db) {  // chunk 4 kbl + 2 s + hsel of the lane's V^T row of the stage
+      const int d = att_v_row<HD>(db, l31);
+      return Ks + VOFF + d * 128 + (((kbl * 4 + 2 * s + hsel) ^ ((d >> 1) & 7)) << 4);
+    });
   };
 
   // top of stage st: stage st (first time also Q) has landed -- only the DMAs of stage st + 1 may still fly --, every wave's share of it is in the LDS and every
@@ -212,50 +187,8 @@ __global__ __launch_bounds__(256, 2) void dit_attention_tiled_kernel(const half_
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   ATS_BARRIER();
   if (!wave_live) return;
-  char* ob = smem + wave * (32 * OSTR);
-  {
-    const float inv = 1.0f / (lrun + xhalf(lrun));
-#pragma unroll
-    for (int db = 0; db < NDB; ++db)
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        if (db * 32 + 8 * g >= HD) continue;  // HD % 8 == 0: an 8-row group is live or dead as a whole
-        half4_t h = {(half_t)(Oa[db][4 * g] * inv), (half_t)(Oa[db][4 * g + 1] * inv), (half_t)(Oa[db][4 * g + 2] * inv), (half_t)(Oa[db][4 * g + 3] * inv)};
-        *(half4_t*)(ob + l31 * OSTR + (db * 32 + 8 * g + 4 * hsel) * 2) = h;
-      }
-  }
+  char* ob = smem + wave * (32 * ATT_OSTR<HD>);
+  att_normalised<HD>(Oa, att_inv_l(lrun), [&](int db, int g, half4_t h) { att_ostage_put<HD>(ob, l31, hsel, db, g, h); });
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // wave-private rows: no barrier
-  half_t* obase = O + ((long)img * T + q0) * D + head * HD;
-  constexpr int OCH = 32 * KCH;  // 16-byte chunks of the wave's 32 rows
-#pragma unroll
-  for (int i = 0; i < (OCH + 63) / 64; ++i) {
-    const int c = i * 64 + lane, row = c / KCH, ch = c - row * KCH;
-    if ((OCH % 64 == 0 || c < OCH) && q0 + row < T) {
-      const half8_t v = *(const half8_t*)(ob + row * OSTR + ch * 16);
-      *(half8_t*)(obase + (long)row * D + ch * 8) = v;
-    }
-  }
-}
-
-// Shapes the kernel takes (LFM_OPT_ATTENTION_TILED = 2 sends all of them here) and the ones it serves by default: square grids of a side that is a multiple of 4
-// which no other kernel serves -- attention_choose asks the other kernels first.  T >= 4096 stays refused (tests/test_host_logic.py pins it), not a kernel limit.
-static inline bool attention_tiled_takes(int hd, int T) { return (hd == 64 || hd == 72) && T >= 16 && T < 4096 && T % 16 == 0; }
-static inline bool attention_tiled_default(int hd, int T) {
-  if (!attention_tiled_takes(hd, T) || T < 144 || T > 3600) return false;
-  int g = 12;
-  while (g * g < T) g += 4;
-  return g * g == T;
-}
-
-template <int HD>
-static int attention_tiled_run(const half_t* Q, const half_t* K, const half_t* Vt, half_t* O, int batch, int heads, int T, float sl2, hipStream_t st) {
-  constexpr int SLOTS = 64 * (HD / 8) + HD * 8, LDS = 3 * ((SLOTS + 255) / 256) * 256 * 16;
-  if (!attention_tiled_takes(HD, T)) return LFM_ERR_SHAPE;
-  const int qblocks = (T + 127) / 128;
-  const long grid = (long)batch * heads * qblocks;
-  if (grid <= 0 || grid >= (1L << 31) || (long)T * heads * HD * 2 >= (1L << 31)) return LFM_ERR_SHAPE;  // (32-bit offsets inside ONE item's K rows)
-  if (!lfm_kernel_lds<&dit_attention_tiled_kernel<HD>>(LDS)) return LFM_ERR_LAUNCH;
-  hipLaunchKernelGGL(dit_attention_tiled_kernel<HD>, dim3((unsigned)grid), dim3(256), LDS, st, Q, K, Vt, O, T, heads * HD, heads, qblocks, sl2);
-  LFM_CHECK_LAUNCH();
-  return LFM_OK;
+  att_ostage_store<HD, 32>(ob, O + ((long)img * T + q0) * D + head * HD, D, lane, T - q0);
 }

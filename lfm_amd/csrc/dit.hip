@@ -116,7 +116,7 @@ extern "C" int lfm_gemm_select(int which) {  // low 4 bits: kernel choice (0 aut
 }
 
 #include "dit_kernels.h"
-#include "attention_kernel.h"  // dit_attention_kernel<T, JQ, HD> + attention_launch
+#include "attention_dispatch.h"  // the DiT attention kernels + attention_choose / attention_launch
 #include "solver_kernels.h"
 #include "dit_measure.h"
 

@@ -10,7 +10,7 @@
 // image's panel), W and O: 266 MB -> ~75 MB per block.
 //
 // Same arithmetic, same order: the K loop accumulates the K-tiles in the same sequence on the same MFMA (v_mfma_f32_16x16x32_f16), the affine is row_affine4 /
-// fma_v as in EpiQKVMod, the softmax block is att_softmax_block, S^T / O^T MFMAs and the normalisation as in the per-item kernel => O is BIT-IDENTICAL to
+// fma_v as in EpiQKVMod, the S^T, softmax and P V blocks, the normalisation and the output staging are the one text of attention_common.h => O is BIT-IDENTICAL to
 // launch_gemm256h_tn<EpiQKVMod> + attention_launch (tests/test_gpu_dit.py::test_fused_qkv_attention_matches_two_kernels).
 //
 // K loop = the shared one of gemm256q_ring.h (phase table, hazard rule, ping-pong skeleton, counted waits; the same text the 256x256 GEMM runs) with a 192-column
@@ -219,11 +219,7 @@ __global__ __launch_bounds__(512) void qkv_attention_kernel(const half_t* __rest
   [[maybe_unused]] int tr_k = 0;
   auto stamp = [&](int slot) {
 #ifdef LFM_MEASURE
-    if ((dbg & LFM_DBG_QKV_TRACE) && blockIdx.x == 0 && (wave & 3) == 0 && tr_k < 4) {
-      unsigned long long t;
-      asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory");
-      if (lane == 0) att_trace[(wave >> 2) * 32 + 7 * tr_k + slot] = t;
-    }
+    if ((dbg & LFM_DBG_QKV_TRACE) && blockIdx.x == 0 && (wave & 3) == 0 && tr_k < 4) att_stamp((wave >> 2) * 32 + 7 * tr_k + slot, lane);
 #else
     (void)slot;
 #endif
@@ -379,29 +375,17 @@ __global__ __launch_bounds__(512) void qkv_attention_kernel(const half_t* __rest
 #pragma unroll
     for (int e = 0; e < 16; ++e) Oa[0][e] = 0.f, Oa[1][e] = 0.f;
     float mrun = -3.0e38f, lrun = 0.f;
-    f32x16 zero16;
-#pragma unroll
-    for (int e = 0; e < 16; ++e) zero16[e] = 0.f;
     auto qk = [&](f32x16& S, int kb) {
       const char* kp = Ks + (kb * 32 + l31) * 128;
-#pragma unroll
-      for (int ks = 0; ks < 4; ++ks) {
-        const half8_t kf = *(const half8_t*)(kp + (((ks * 2 + hsel) ^ akey) << 4));
-        S = __builtin_amdgcn_mfma_f32_32x32x16_f16(kf, qf[ks], ks == 0 ? zero16 : S, 0, 0, 0);
-      }
+      att_qk_block<64, 1>(&S, &qf, hsel, [&](int ks) { return kp + (((ks * 2 + hsel) ^ akey) << 4); });
     };
     auto softmax_pv = [&](f32x16& S, int kb) {
       half8_t P[2];
       att_softmax_block<2>(S, kb == 0, mrun, lrun, Oa, scale_log2e, P);
-#pragma unroll
-      for (int s = 0; s < 2; ++s)
-#pragma unroll
-        for (int db = 0; db < 2; ++db) {
-          const int dd = db * 32 + l31;
-          const int c0 = kb * 4 + 2 * s + hsel;
-          const half8_t vf = *(const half8_t*)(Vs + dd * 512 + ((c0 ^ (dd & 15)) << 4));
-          Oa[db] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vf, P[s], Oa[db], 0, 0, 0);
-        }
+      att_pv_block<2, 1>(&Oa, &P, [&](int s, int db) {
+        const int dd = db * 32 + l31;
+        return Vs + dd * 512 + (((kb * 4 + 2 * s + hsel) ^ (dd & 15)) << 4);
+      });
     };
     f32x16 Sa, Sb;
 #ifdef LFM_MEASURE
@@ -426,23 +410,14 @@ __global__ __launch_bounds__(512) void qkv_attention_kernel(const half_t* __rest
     }
 #endif
     stamp(5);
-    // ---- normalise and store: lane owns query l31, d = db * 32 + 8 g + 4 hsel + r.  One pass through the wave's 4 KiB of staging (32 rows x 128 B; 8-byte position
-    // p of row r at p ^ ((r & 7) << 1)), read back as 16-byte chunks: a store instruction covers eight whole 128-byte output rows.  The staging lies above the
-    // ring, over the (a, b) rows of THIS item, dead since the hand-over.
+    // ---- normalise and store: one pass through the wave's 4 KiB of staging (32 swizzled 128-byte rows: att_oswz_*, attention_common.h), read back as 16-byte
+    // chunks: a store instruction covers eight whole 128-byte output rows.  The staging lies above the ring, over the (a, b) rows of THIS item, dead since the
+    // hand-over.
     {
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      const float inv = 1.0f / (lrun + xhalf(lrun));
-      const unsigned ow = (unsigned)(l31 * 128), okey2 = (unsigned)((l31 & 7) << 1);
-      const int orow = lna >> 3, och = lna & 7;
-      const unsigned ord0 = (unsigned)(orow * 128 + ((och ^ orow) << 4));
-      half_t* const obase = ep.O + ((long)m0 + wave * 32 + orow) * D + head * 64 + och * 8;
-#pragma unroll
-      for (int db = 0; db < 2; ++db)
-#pragma unroll
-        for (int gg = 0; gg < 4; ++gg) {
-          half4_t hv = {(half_t)(Oa[db][4 * gg] * inv), (half_t)(Oa[db][4 * gg + 1] * inv), (half_t)(Oa[db][4 * gg + 2] * inv), (half_t)(Oa[db][4 * gg + 3] * inv)};
-          *(half4_t*)(ob + ow + ((((unsigned)(db * 8 + 2 * gg + hsel)) ^ okey2) << 3)) = hv;
-        }
+      const unsigned ord0 = att_oswz_get(lna);
+      half_t* const obase = ep.O + ((long)m0 + wave * 32 + (lna >> 3)) * D + head * 64 + (lna & 7) * 8;
+      att_normalised<64>(Oa, att_inv_l(lrun), [&](int db, int gg, half4_t hv) { *(half4_t*)(ob + att_oswz_put(l31, hsel, db, gg)) = hv; });
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // wave-private rows: no barrier (also the compiler barrier between the half4 writes and the f32x4 reads)
       f32x4 vrow[4];
 #pragma unroll

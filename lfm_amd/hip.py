@@ -376,7 +376,7 @@ DIT_RESIDENT_TOKENS = (16, 64, 128, 256, 1024)  # token counts of the kernels wi
 
 
 def dit_tokens_served(tokens):
-    """Whether a DiT attention kernel serves `tokens` tokens per image under the default library options (csrc/attention_kernel.h: attention_choose, for
+    """Whether a DiT attention kernel serves `tokens` tokens per image under the default library options (csrc/attention_dispatch.h: attention_choose, for
     head_dim 64 / 72): the resident kernels' 16 / 64 / 128 / 256 / 1024, or -- the tiled kernel -- the square of a grid side that is a multiple of 4
     with 144 <= tokens <= 3600.  Pure Python (a model is constructed without the library); tests/test_dit_attention_tiled_ref.py holds it against
     lfm_attention_plan."""
