@@ -50,7 +50,7 @@ __device__ __forceinline__ void att_qk_block(f32x16* S, const half8_t (*qf)[(HD 
   }
 }
 // O^T[d][q] += sum_key V^T[d][key] P[q][key] for the block whose packed P (k-slots 0 and 1) att_softmax_block returned: the A operand of k-slot s is V^T row
-// att_v_row(db, l31) at the block's keys {4 hsel + r} and {8 + 4 hsel + r} of the slot's 16 -- ONE 16-byte chunk of the row in the vt_pos token order (gemm_kernel.h),
+// att_v_row(db, l31) at the block's keys {4 hsel + r} and {8 + 4 hsel + r} of the slot's 16 -- ONE 16-byte chunk of the row in the vt_pos token order (gemm_epilogues.h),
 // chunk 2 s + hsel of the block.  vfrag(s, db) = that chunk in the kernel's LDS image.  Oa: [JQ][NDB], P: [JQ][2].
 template <int NDB, int JQ, class VF>
 __device__ __forceinline__ void att_pv_block(f32x16 (*Oa)[NDB], const half8_t (*P)[2], VF&& vfrag) {

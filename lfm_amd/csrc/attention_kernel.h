@@ -9,7 +9,7 @@
 // The arithmetic is attention_common.h's, one text for all four MFMA kernels: S^T = K Q^T on v_mfma_f32_32x32x16_f16 (att_qk_block: a lane then holds the scores
 // of ONE query, so row max / row sum are in-lane plus one lane^32 exchange, and the fp32->fp16 packed P registers are directly the B-operand of O^T = V^T P^T,
 // att_pv_block: the key order inside an MFMA k-slot is the same permutation on both operands, so no shuffle is needed), the zero-fed half k-slot of hd 72
-// (O^T has 2.25 blocks of 32 rows: the third block computes 8 live rows), V^T rows in the vt_pos token order (gemm_kernel.h), which makes a lane's P V operand
+// (O^T has 2.25 blocks of 32 rows: the third block computes 8 live rows), V^T rows in the vt_pos token order (gemm_epilogues.h), which makes a lane's P V operand
 // one 16-byte read.  This file owns the LDS image, the staging and the schedule.
 // Keys are consumed in 32-key blocks with an online softmax (running max m, running sum l), which keeps
 // the live state at S 32 + P 16 + O 64 + Q 32 registers for hd 64, JQ 2 (2 waves / SIMD).

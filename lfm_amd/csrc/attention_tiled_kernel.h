@@ -4,7 +4,7 @@
 // Why another kernel: every kernel behind attention_choose (attention_dispatch.h) has its token count as a template argument and the whole K / V^T of an item
 // (or a 256-key chunk of it) resident in the LDS -- 16 / 64 / 128 / 256 / 1024 tokens, the grids of 256^2 and 512^2 images.  This one serves the other grids
 // (--image_size 384 = 576 tokens, 192 = 144, 320 = 400, 768 = 2304): only a 64-key STAGE is resident, T is an argument.  Same operands as the other kernels, so
-// the QKV epilogue is unchanged: Q, K, O fp16 [batch * T, D] with head-major columns, V^T fp16 [batch, heads, hd, T] in the vt_pos token order (gemm_kernel.h).
+// the QKV epilogue is unchanged: Q, K, O fp16 [batch * T, D] with head-major columns, V^T fp16 [batch, heads, hd, T] in the vt_pos token order (gemm_epilogues.h).
 //
 // Shape.  A workgroup owns 128 QUERIES of one item (four waves x 32; blockIdx.x = item * qblocks + query block, so the workgroups that read the same K / V^T
 // are neighbours) and walks ALL keys of the item in stages of 64 through a three-slot LDS ring.

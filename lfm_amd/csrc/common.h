@@ -100,7 +100,7 @@ __device__ __forceinline__ f32x2_t gelu_tanh_pk(f32x2_t x) {
   return x * r;
 }
 
-// a * b + c as ONE plain v_fma_f32 per element.  The row-affine epilogues of the folded LayerNorm path (gemm_kernel.h: a[m] * acc + (b[m] * u[n] + v[n])
+// a * b + c as ONE plain v_fma_f32 per element.  The row-affine epilogues of the folded LayerNorm path (gemm_epilogues.h: a[m] * acc + (b[m] * u[n] + v[n])
 // with (a, b) in a register pair) are written element by element with it INSTEAD of the vector expression `ab.x * acc + (ab.y * u + v)`, for which the
 // compiler selects v_pk_fma_f32 with op_sel:[0,1,0] -- the LOW half of the packed operation takes src1 from the HIGH register of the pair.  On MI355X
 // that form sporadically evaluates with the operand read as 0.0 in lanes 48-63 when a foreign wave shares the SIMD (two HIP streams in flight): the

@@ -19,8 +19,8 @@
 //               follow that ratio (~1.5, ~1.2, ~0.9 PFLOP/s): staging each input byte once is what buys the rate.
 // Pixel rows and weight rows are 64 B (4 chunks of 16 B); chunk c of row p sits at c ^ ((p >> 1) & 2) -- conflict-free for ds_read_b128 of
 // 16 consecutive rows starting at ANY row (searched exhaustively over the instruction's lane groups: the tap shift moves the start row).
-// The accumulator map and the row-major LDS-transposed hand-over to the epilogue are those of gemm256h_kernel.h (shared Epi interface:
-// load / store8, and finish_slab for the GroupNorm partial sums).
+// The accumulator map is gemm256h_kernel.h's; the scratch fill and the 8-column read-back of the epilogue are those of epilogue_handover.h
+// (HoMap16, ho_read8), under this kernel's own pixel addresses (Epi interface: load / store8, and finish_slab for the GroupNorm partial sums).
 // Measured (tools/conv_probe.py, profiles/r03_halo_conv_probe.txt): 1.0-1.4 PFLOP/s on every 3x3 convolution of the VAE decoder and the ADM UNet
 // against 0.65-1.2 for the implicit GEMM.  Measured and not kept: s_setprio around the MFMA block (+-1 %).
 #pragma once
@@ -35,15 +35,6 @@
 template <int V>
 struct ch_ic {
   static constexpr int value = V;
-};
-
-template <class Epi, class = void>
-struct epi_has_finish_slab {
-  static constexpr bool value = false;
-};
-template <class Epi>
-struct epi_has_finish_slab<Epi, decltype((void)&Epi::finish_slab)> {
-  static constexpr bool value = true;
 };
 
 // UPS = 1: the convolution runs on the nearest-2x upsampled image (H, W are the upsampled = output size) without materialising it: only the
@@ -197,30 +188,29 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo_kernel(const half_t* __re
 
   // ---- epilogue: 32 pixels (two row segments) x 64 channels at a time through a per-wave scratch [32][64 + pad] fp32; then lane (rrow = lane >> 3,
   // rcol = lane & 7) owns 8 consecutive channels of pixel rows rrow, rrow + 8, ..: 16-byte stores, full 128-byte runs per pixel
-  char* scr = smem + wave * (32 * 272);
-  const int rrow = lane >> 3, rcol = lane & 7, n = n0 + wn * 64 + rcol * 8;
+  // (fill, read-back and the order contracts the statistics epilogue relies on: epilogue_handover.h; the pixel addresses are this kernel's)
+  char* scr = ho_slot(smem, wave);
+  int el = lane;
+  asm volatile("" : "+v"(el));  // the epilogue's lane-dependent addresses are computed here, not ahead of the main loop (register budget)
+  const int rrow = el >> 3, rcol = el & 7, n = n0 + wn * 64 + rcol * 8;
 #pragma unroll
   for (int I = 0; I < 4; ++I) {
-#pragma unroll
-    for (int h2 = 0; h2 < 2; ++h2)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) *(f32x4_t*)(scr + (h2 * 16 + r) * 272 + (j * 16 + q * 4) * 4) = acc[2 * I + h2][j];
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    HoMap16::fill_rows(acc, I, scr, el);
+    HO_LGKM0();
     f32x4 lo[4], hi[4];
     int m[4];
     typename Epi::Aux al[4], ah[4];
 #pragma unroll
     for (int ps = 0; ps < 4; ++ps) {
       const int rb = ps * 8 + rrow;  // row of the 32-pixel block: segment rb >> 4, pixel rb & 15
-      lo[ps] = *(const f32x4*)(scr + rb * 272 + rcol * 32);
-      hi[ps] = *(const f32x4*)(scr + rb * 272 + rcol * 32 + 16);
+      ho_read8(scr, el, ps, lo[ps], hi[ps]);
       m[ps] = (img * H + y0 + wm * 8 + 2 * I + (rb >> 4)) * W + x0 + (rb & 15);
       al[ps] = epi.load(m[ps], n);
       ah[ps] = epi.load(m[ps], n + 4);
     }
 #pragma unroll
     for (int ps = 0; ps < 4; ++ps) epi.store8(m[ps], n, lo[ps], hi[ps], al[ps], ah[ps]);
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    HO_LGKM0();
   }
   if constexpr (epi_has_finish_slab<Epi>::value) epi.finish_slab(img, rem * 2 + wm, n0 + wn * 64, lane);
 }

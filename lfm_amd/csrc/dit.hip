@@ -134,7 +134,7 @@ struct DitWs {
   half_t* c_half; // [B, D]
   float* mod;     // [B, J]
   float* ones;    // [D] of 1.0f: gate row of the patch-embedding GEMM (large patches)
-  // folded LayerNorm-modulate (gemm_kernel.h): row partials, two centring-constant arrays (ping-pong), the u / v GEMM's operand and results
+  // folded LayerNorm-modulate (gemm_epilogues.h): row partials, two centring-constant arrays (ping-pong), the u / v GEMM's operand and results
   float* ln_part;  // [M][ceil(D / 256)][2]
   float* cen[2];   // [M] each
   half_t* amod;    // [depth][2 branches][2][rows][D] fp16: (1 + scale | shift) rows
@@ -320,7 +320,7 @@ extern "C" int lfm_gemm_qkv_f16(const void* A, long lda, const void* W, long ldw
 
 // ------------------------------------------------------------------ conditioning (everything the forward derives from t and y alone)
 // c = t_emb(t) (+ y_emb), the adaLN modulation rows of every block and of the final layer (DiT.py:252-262, 128, 170) and -- for the folded
-// LayerNorm path -- the u / v rows of the qkv and fc1 projections (gemm_kernel.h).  One function, so that the per-grid tables below are written by
+// LayerNorm path -- the u / v rows of the qkv and fc1 projections (gemm_epilogues.h).  One function, so that the per-grid tables below are written by
 // exactly the launches a forward would make.
 static int dit_conditioning(const lfm_dit_shape* s, const lfm_dit_weights* w, const DitWs& ws, const DitDims& d, const float* t, int t_len, const int64_t* y,
                             int rows, bool want_uv, hipStream_t st) {
@@ -398,7 +398,7 @@ extern "C" int lfm_dit_cond_table_build(const lfm_dit_shape* s, const lfm_dit_we
 // Every launch-shape decision of an evaluation, taken once: each setting is read ONCE here, on the calling thread and inside the call's scope (another host thread
 // may store a default between two reads).  The launchers shared with the standalone entry points (ln_modulate_launch, attention_launch, gemm_choose) read theirs
 // themselves.  The block loop is one of three:
-//   folded    the adaLN LayerNorm-modulate folded into the GEMM epilogues (gemm_kernel.h), optionally with QKV projection + attention as one kernel;
+//   folded    the adaLN LayerNorm-modulate folded into the GEMM epilogues (gemm_epilogues.h), optionally with QKV projection + attention as one kernel;
 //   latency   one image of <= 256 tokens: the four linears on the latency-mode kernels (gemm_skinny_kernel.h / gemm_sq64_kernel.h);
 //   separate  everything else: split-K GEMMs where they apply, else the automatic choice plus a LayerNorm-modulate launch.
 enum DitLoop { DIT_LOOP_FOLDED, DIT_LOOP_LATENCY, DIT_LOOP_SEPARATE };
@@ -524,7 +524,7 @@ int DitCtx::embed() const {
   return LFM_OK;
 }
 
-// FOLDED LayerNorm-modulate (default; gemm_kernel.h): only where its preconditions hold (dit_plan).  Everything else (small batches, DiT-S / XL widths, patch 4 / 8
+// FOLDED LayerNorm-modulate (default; gemm_epilogues.h): only where its preconditions hold (dit_plan).  Everything else (small batches, DiT-S / XL widths, patch 4 / 8
 // token counts with per-image conditioning, forced kernels) takes the separate ln_modulate launches of the other two loops.
 int DitCtx::blocks_folded() const {
   const long uvs_q = rows == 1 ? 0 : 3 * D, uvs_f = rows == 1 ? 0 : H;
@@ -547,7 +547,7 @@ int DitCtx::blocks_folded() const {
       const QkvAttnArgs e_qa{uq, uq + (long)rows * 3 * D, uvs_q, rowstat_src(), Ob, D, s->heads, 0.125f * 1.4426950408889634f, nullptr, 0};
       if ((rc = launch_qkv_attention(ws.A, D, b.qkv_w, D, M, D, s->heads, D, e_qa, st))) return rc;
     } else {
-      const EpiQKVMod e_qkv{Qb, Kb, Vb, uq, uq + (long)rows * 3 * D, uvs_q, D, hd, T, EpiQKV::log2_or_neg(T), rowstat_src(), nullptr, 0};
+      const EpiQKVMod e_qkv{{}, Qb, Kb, Vb, uq, uq + (long)rows * 3 * D, uvs_q, D, hd, T, EpiQKV::log2_or_neg(T), rowstat_src(), nullptr, 0};
       if ((rc = launch_fold(ASrcRowMajor{ws.A, D, M, 0}, b.qkv_w, D, M, 3 * D, D, e_qkv))) return rc;
       checksum(ws.QKVH, (size_t)3 * M * D * 2, i, 0);
       if ((rc = attention_launch(Qb, Kb, Vb, Ob, B, s->heads, hd, T, st))) return rc;

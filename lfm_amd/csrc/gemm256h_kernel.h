@@ -12,244 +12,38 @@
 //                      4*ks + (l >> 4) of a 128-byte LDS row (ks = 0, 1 per 64-deep K-tile); the same 12 / 4 / 8 / 0 reads per phase as v3;
 //   accumulators       a wave's 128 x 64 block = 8 (m) x 4 (n) tiles of f32x4; issued with W as the A operand, so lane l owns
 //                      C[m = 16 i + (l & 15)][n = 16 j + 4 (l >> 4) + r], r = 0..3: four consecutive n per lane as before;
-//   epilogue           the same LDS-transposed row-major hand-over (shared Epi interface), with the scratch filled from the new map.
+//   epilogue           the LDS-transposed hand-over of epilogue_handover.h with the scratch filled from this map (HoMap16); this file keeps the
+//                      8-wave schedule of the folded LayerNorm's producer epilogue and its consumer prologue.
 #pragma once
 #include "gemm256n_kernel.h"
 #include "gemm256q_ring.h"
 
-typedef float f32x4_t __attribute__((ext_vector_type(4)));
-
-// ---- epilogue for the 16x16 accumulator map.  acc[i][j]: tile i (16 rows) x j (16 columns) of the wave's 128 x 64 block.
-// fill32(I, scr): rows 32 I .. 32 I + 31 of the block -> scratch [32][64 + pad] fp32, row stride 272 B (as g256_epilogue_rows)
-// Measurement only (lfm_gemm_select flag TRACE_GEMM with kernel 5): waves 0 and 4 of the tile at row 0, column TRACE_COL stamp s_memtime at the end of the K loop and after the
-// scratch fill / read-back / store issue of each of the four 32-row blocks of the row-major epilogue (g256q_trace, lfm_gemm_trace_read).
-template <bool TRACE>
-__device__ __forceinline__ void g256h_stamp(bool tr, int g, int wn, int lane, int slot) {
-  if constexpr (TRACE) {
-    if (tr && wn == 0 && lane == 0) {
-      unsigned long long t;
-      asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory");
-      g256q_trace[g][slot] = t;
-    }
-  }
-}
-
-// epilogues with per-row operands in LDS provide row_aux(m) -> f32x2 and store8r(m, n, lo, hi, aux_lo, aux_hi, row_aux)
-template <class Epi, class = void>
-struct epi_has_row_aux {
-  static constexpr bool value = false;
-};
-template <class Epi>
-struct epi_has_row_aux<Epi, decltype((void)&Epi::row_aux)> {
-  static constexpr bool value = true;
-};
-
-template <int BN, bool TRACE = false, class Epi>
-__device__ __forceinline__ void g256h_epilogue_rows(f32x4_t (&acc)[8][4], char* smem, const Epi& epi, int m0, int n0, int M, int N, int g, int wn,
-                                                    int lane, int wave, bool narrow, bool tr = false) {
-  char* scr = smem + wave * (32 * 272);
-  const bool interior = (m0 + G256_BM <= M) && (n0 + BN <= N);
-  constexpr bool COL = epi_column_aux<Epi>::value;  // bias-only auxiliary operand: loaded once per tile, ahead of the first store
-  const int l15 = lane & 15, l4 = lane >> 4;
-  auto fill32 = [&](int I) {
-#pragma unroll
-    for (int h2 = 0; h2 < 2; ++h2)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) *(f32x4_t*)(scr + (h2 * 16 + l15) * 272 + (j * 16 + l4 * 4) * 4) = acc[2 * I + h2][j];
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  };
-  if constexpr (epi_has_store8<Epi>::value) {
-    if (!narrow && epi.wide_ok()) {
-      const int rrow = lane >> 3, rcol = lane & 7;
-      typename Epi::Aux cl, ch;
-      if constexpr (COL) {
-        if (interior) {
-          cl = epi.load(m0, n0 + wn * 64 + rcol * 8);
-          ch = epi.load(m0, n0 + wn * 64 + rcol * 8 + 4);
-        }
-      }
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        fill32(i);
-        g256h_stamp<TRACE>(tr, g, wn, lane, 1 + 4 * i);
-        f32x4 lo[4], hi[4];
-        const int mb = m0 + g * 128 + i * 32 + rrow, n = n0 + wn * 64 + rcol * 8;
-#pragma unroll
-        for (int ps = 0; ps < 4; ++ps) {
-          lo[ps] = *(const f32x4*)(scr + (ps * 8 + rrow) * 272 + rcol * 32);
-          hi[ps] = *(const f32x4*)(scr + (ps * 8 + rrow) * 272 + rcol * 32 + 16);
-        }
-        if constexpr (epi_has_row_aux<Epi>::value) {  // per-row operands of the epilogue (LDS), fetched with the read-back: one wait covers both
-          if (COL && interior) {
-            f32x2 ra[4];
-#pragma unroll
-            for (int ps = 0; ps < 4; ++ps) ra[ps] = epi.row_aux(mb + ps * 8);
-#ifdef LFM_EXP_WAIT_ALL  // (experiment build) every LDS read of the pass has landed, plus 16 idle cycles, before the first VALU instruction that consumes one
-            asm volatile("s_waitcnt lgkmcnt(0)\n\ts_nop 7\n\ts_nop 7" ::: "memory");
-            __builtin_amdgcn_sched_barrier(0);
-#endif
-#pragma unroll
-            for (int ps = 0; ps < 4; ++ps) epi.store8r(mb + ps * 8, n, lo[ps], hi[ps], cl, ch, ra[ps]);
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            continue;
-          }
-        }
-        if constexpr (TRACE) {
-          asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-          g256h_stamp<TRACE>(tr, g, wn, lane, 2 + 4 * i);
-        }
-        if (COL && interior) {
-          if constexpr (COL) {
-            g256h_stamp<TRACE>(tr, g, wn, lane, 3 + 4 * i);
-#pragma unroll
-            for (int ps = 0; ps < 4; ++ps) epi.store8(mb + ps * 8, n, lo[ps], hi[ps], cl, ch);
-            g256h_stamp<TRACE>(tr, g, wn, lane, 4 + 4 * i);
-          }
-        } else if (interior) {
-          typename Epi::Aux al[4], ah[4];
-#pragma unroll
-          for (int ps = 0; ps < 4; ++ps) {
-            al[ps] = epi.load(mb + ps * 8, n);
-            ah[ps] = epi.load(mb + ps * 8, n + 4);
-          }
-          if constexpr (TRACE) {
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // (trace build only) the auxiliary loads have returned
-            g256h_stamp<TRACE>(tr, g, wn, lane, 3 + 4 * i);
-          }
-#pragma unroll
-          for (int ps = 0; ps < 4; ++ps) epi.store8(mb + ps * 8, n, lo[ps], hi[ps], al[ps], ah[ps]);
-          g256h_stamp<TRACE>(tr, g, wn, lane, 4 + 4 * i);
-        } else {
-#pragma unroll
-          for (int ps = 0; ps < 4; ++ps) {
-            const int m = mb + ps * 8;
-            if (m >= M) continue;
-            if (n + 7 < N) epi.store8(m, n, lo[ps], hi[ps], epi.load(m, n), epi.load(m, n + 4));
-            else if (n + 3 < N) epi.store(m, n, lo[ps], epi.load(m, n));
-          }
-        }
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      }
-      return;
-    }
-  }
-  const int rrow = lane >> 4, rcol = lane & 15;
-  typename Epi::Aux cx;
-  if constexpr (COL) {
-    if (interior) cx = epi.load(m0, n0 + wn * 64 + rcol * 4);
-  }
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    fill32(i);
-    g256h_stamp<TRACE>(tr, g, wn, lane, 1 + 4 * i);
-    f32x4 v[8];
-#pragma unroll
-    for (int ps = 0; ps < 8; ++ps) v[ps] = *(const f32x4*)(scr + (ps * 4 + rrow) * 272 + rcol * 16);
-    if constexpr (TRACE) {
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      g256h_stamp<TRACE>(tr, g, wn, lane, 2 + 4 * i);
-    }
-    const int mb = m0 + g * 128 + i * 32 + rrow, n = n0 + wn * 64 + rcol * 4;
-    if (COL && interior) {
-      if constexpr (COL) {
-#pragma unroll
-        for (int ps = 0; ps < 8; ++ps) epi.store(mb + ps * 4, n, v[ps], cx);
-        g256h_stamp<TRACE>(tr, g, wn, lane, 4 + 4 * i);
-      }
-    } else if (interior) {
-      typename Epi::Aux aux[8];
-#pragma unroll
-      for (int ps = 0; ps < 8; ++ps) aux[ps] = epi.load(mb + ps * 4, n);
-      if constexpr (TRACE) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        g256h_stamp<TRACE>(tr, g, wn, lane, 3 + 4 * i);
-      }
-#pragma unroll
-      for (int ps = 0; ps < 8; ++ps) epi.store(mb + ps * 4, n, v[ps], aux[ps]);
-      g256h_stamp<TRACE>(tr, g, wn, lane, 4 + 4 * i);
-    } else if (n + 3 < N) {
-#pragma unroll
-      for (int ps = 0; ps < 8; ++ps)
-        if (mb + ps * 4 < M) epi.store(mb + ps * 4, n, v[ps], epi.load(mb + ps * 4, n));
-    }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  }
-}
-
-// sum over the 16 lanes of a DPP row (every lane of the row receives it): quad swaps, then two row rotations
-__device__ __forceinline__ float g256h_row16_sum(float v) {
-  v = dpp_add<0xB1>(v);
-  v = dpp_add<0x4E>(v);
-  v = dpp_add<0x124>(v);
-  v = dpp_add<0x128>(v);
-  return v;
-}
-
-// Producer epilogue of the folded LayerNorm-modulate (EpiGateResidMod, gemm_kernel.h): the gated-residual read-modify-write of X, plus the consumer
-// GEMM's A operand A' = fp16((X' - c)(1 + scale)) and this tile's per-row partials (sum X', sum (X' - c)^2).  Interior tiles of ONE image only (the
-// host guarantees it).  Row-major hand-over as g256h_epilogue_rows (4-column form): per pass a lane owns rows mb + 4 ps (ps = 0..7), columns n .. n + 3;
-// the 16 lanes that share a row are one DPP row, so a row's sums over the wave's 64 columns cost four DPP adds each.
+// Producer epilogue of the folded LayerNorm-modulate, 8-wave form (the arithmetic and the LDS areas: epilogue_handover.h): wave (g, wn) owns rows
+// g * 128 .., column quarter wn of the tile; all eight X rows of a 32-row pass are requested before the pass's first store.
 template <class Epi>
 __device__ __forceinline__ void g256h_epilogue_mod(f32x4_t (&acc)[8][4], char* smem, const Epi& epi, int m0, int n0, int tile_n, int N, int g, int wn,
                                                    int lane, int wave) {
-  char* scr = smem + wave * (32 * 272);
-  float* red = (float*)(smem + 8 * 32 * 272);           // [g][wn][128 rows][2]: 8 KiB behind the eight scratch areas
-  float* cen_s = (float*)(smem + 8 * 32 * 272 + 8192);  // [256 rows] centring constants of the tile's rows
-  const int l15 = lane & 15, l4 = lane >> 4;
+  char* scr = ho_slot(smem, wave);
+  float* cen_s = (float*)(smem + HO_CEN_OFF);
   const int rrow = lane >> 4, rcol = lane & 15;
   const int n = n0 + wn * 64 + rcol * 4;
-  const int img = m0 / epi.tokens;
   if (threadIdx.x < 256) cen_s[threadIdx.x] = epi.cen[m0 + threadIdx.x];
-  const f32x4 bias = *(const f32x4*)(epi.bias + n);
-  const f32x4 gate = *(const f32x4*)(epi.gate + (long)img * epi.gate_stride + n);
-  const f32x4 sc1 = *(const f32x4*)(epi.scale + (long)img * epi.mod_stride + n) + 1.0f;
+  const HoModCols k = HoModCols::load(epi, m0 / epi.tokens, n);
   __syncthreads();
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
-#pragma unroll
-    for (int h2 = 0; h2 < 2; ++h2)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) *(f32x4_t*)(scr + (h2 * 16 + l15) * 272 + (j * 16 + l4 * 4) * 4) = acc[2 * i + h2][j];
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    HoMap16::fill_rows(acc, i, scr, lane);
+    HO_LGKM0();
     const int rl = g * 128 + i * 32 + rrow;  // + 4 ps: row inside the tile
     f32x4 xo[8];
 #pragma unroll
     for (int ps = 0; ps < 8; ++ps) xo[ps] = *(const f32x4*)(epi.X + (long)(m0 + rl + ps * 4) * epi.ldx + n);
 #pragma unroll
-    for (int ps = 0; ps < 8; ++ps) {
-      const f32x4 v = *(const f32x4*)(scr + (ps * 4 + rrow) * 272 + rcol * 16);
-      const float c = cen_s[rl + ps * 4];
-      const f32x4 xn = xo[ps] + gate * (v + bias);
-      *(f32x4*)(epi.X + (long)(m0 + rl + ps * 4) * epi.ldx + n) = xn;
-      const f32x4 d = xn - c;
-      const f32x4 ap = d * sc1;
-      const half4_t h = {(half_t)ap.x, (half_t)ap.y, (half_t)ap.z, (half_t)ap.w};
-      *(half4_t*)(epi.A + (long)(m0 + rl + ps * 4) * N + n) = h;
-      const float sx = g256h_row16_sum((xn.x + xn.y) + (xn.z + xn.w));
-      const float sq = g256h_row16_sum((d.x * d.x + d.y * d.y) + (d.z * d.z + d.w * d.w));
-      if (rcol == 0) {
-        float* dst = red + (((g * 4 + wn) * 128) + i * 32 + ps * 4 + rrow) * 2;
-        dst[0] = sx;
-        dst[1] = sq;
-      }
-    }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    for (int ps = 0; ps < 8; ++ps) ho_mod_row(epi, scr, lane, ps, xo[ps], cen_s, k, m0, rl, n, N, ho_red_pass(smem, g, wn, i));
+    HO_LGKM0();
   }
   __syncthreads();
-  // tile-level row sums (fixed order over the four waves) -> this tile's slot of the row's partials
-  if (wn == 0) {
-#pragma unroll
-    for (int rr = 0; rr < 2; ++rr) {
-      const int r = lane + 64 * rr;
-      float sx = 0.f, sq = 0.f;
-#pragma unroll
-      for (int w4 = 0; w4 < 4; ++w4) {
-        sx += red[((g * 4 + w4) * 128 + r) * 2];
-        sq += red[((g * 4 + w4) * 128 + r) * 2 + 1];
-      }
-      *(f32x2*)(epi.part + ((long)(m0 + g * 128 + r) * epi.tiles_n + tile_n) * 2) = (f32x2){sx, sq};
-    }
-  }
+  if (wn == 0) ho_mod_tile_sums(epi, smem, g, lane, m0, tile_n);
 }
 
 // Consumer prologue of the folded LayerNorm-modulate: (a, b) = (rstd, -rstd (mu - c)) of the tile's 256 rows -> LDS rs[256][2] (above the operand
@@ -280,123 +74,6 @@ __device__ __forceinline__ void g256h_rowstat_finish(Epi& epi, const G256hRowSta
   epi.m0 = m0;
 }
 
-// One 128 x 64 accumulator block (rows g * 128 .., columns wn * 64 .. of the tile at m0, n0) through the epilogue `epi`; the wave's private scratch is
-// slot `wave`.  Shared by the 8-wave kernel below (one block per wave) and the 4-wave kernel of gemm256w_kernel.h (two blocks per wave).
-template <int BN, bool TRACE = false, class Epi>
-__device__ __forceinline__ void g256h_epilogue_body(f32x4_t (&acc)[8][4], char* smem, Epi& epi, int m0, int n0, int M, int N, int g, int wn, int lane,
-                                                    int wave, int dbg, bool swapped, bool tr) {
-  const int l15 = lane & 15, l4 = lane >> 4;
-  if constexpr (epi_has_transposed<Epi>::value) {
-    // The K loop ran this tile with the MFMA operands swapped: acc[i][j][r] = C[m = 16 i + 4 l4 + r][n = 16 j + l15], FOUR CONSECUTIVE m per
-    // lane.  Scratch rows = 32 columns n (tiles 2 J, 2 J + 1), scratch columns = 64 rows m (tiles 4 ih .. 4 ih + 3); read back row-major:
-    // a lane gets 8 (or 4) consecutive m of one n -> epi.store_t8 / store_t.
-    if (swapped) {
-      char* scr = smem + wave * (32 * 272);
-      const bool wide = !(dbg & LFM_DBG_GEMM_STORE8) && epi.wide_t_ok();
-      // the per-column bias of every pass, loaded ahead of the first store (a load issued after stores waits for them: vmcnt is in order)
-      typedef decltype(epi.load_t(0)) AuxT;  // float (a bias) or (u, v) of the folded path
-      AuxT bt[2][4];
-      if (wide) {
-#pragma unroll
-        for (int J = 0; J < 2; ++J)
-#pragma unroll
-          for (int ps = 0; ps < 4; ++ps) {
-            const int n = n0 + wn * 64 + J * 32 + (lane >> 3) + ps * 8;
-            bt[J][ps] = n < N ? epi.load_t(n) : AuxT{};
-          }
-      }
-#pragma unroll
-      for (int J = 0; J < 2; ++J) {
-#pragma unroll
-        for (int ih = 0; ih < 2; ++ih) {
-#pragma unroll
-          for (int j2 = 0; j2 < 2; ++j2)
-#pragma unroll
-            for (int i4 = 0; i4 < 4; ++i4)
-              *(f32x4_t*)(scr + (j2 * 16 + l15) * 272 + (i4 * 16 + l4 * 4) * 4) = acc[4 * ih + i4][2 * J + j2];
-          asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-          g256h_stamp<TRACE>(tr, g, wn, lane, 1 + 4 * (2 * J + ih));
-          // wide stores: a lane owns tokens ml .. ml + 3 and ml + 8 .. ml + 11 of a 16-token group (one 16-byte chunk of the permuted V^T row: vt_pos)
-          const int ml = 16 * ((lane & 7) >> 1) + 4 * (lane & 1);
-          if (wide && m0 + G256_BM <= M && n0 + BN <= N) {  // interior tile: no per-store bounds checks
-            const int rrow = lane >> 3;
-            const int nb = n0 + wn * 64 + J * 32 + rrow, m = m0 + g * 128 + ih * 64 + ml;
-            f32x4 lo[4], hi[4];
-#pragma unroll
-            for (int ps = 0; ps < 4; ++ps) {
-              lo[ps] = *(const f32x4*)(scr + (ps * 8 + rrow) * 272 + ml * 4);
-              hi[ps] = *(const f32x4*)(scr + (ps * 8 + rrow) * 272 + ml * 4 + 32);
-            }
-            if constexpr (TRACE) {
-              asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-              g256h_stamp<TRACE>(tr, g, wn, lane, 2 + 4 * (2 * J + ih));
-            }
-            if (!(TRACE && (dbg & LFM_DBG_TRACE_NO_STORES))) {  // (trace build: the pass without its stores)
-#pragma unroll
-              for (int ps = 0; ps < 4; ++ps) epi.store_t8(nb + ps * 8, m, lo[ps], hi[ps], bt[J][ps]);
-            }
-          } else if (wide) {
-            const int rrow = lane >> 3;
-            const int nb = n0 + wn * 64 + J * 32 + rrow, m = m0 + g * 128 + ih * 64 + ml;
-#pragma unroll
-            for (int ps = 0; ps < 4; ++ps) {
-              const f32x4 lo = *(const f32x4*)(scr + (ps * 8 + rrow) * 272 + ml * 4);
-              const f32x4 hi = *(const f32x4*)(scr + (ps * 8 + rrow) * 272 + ml * 4 + 32);
-              const int n = nb + ps * 8;
-              if (n >= N) continue;
-              const AuxT b = bt[J][ps];
-              if (m + 11 < M) epi.store_t8(n, m, lo, hi, b);
-              else {
-                if (m + 3 < M) epi.store_t(n, m, lo, b);
-                // (the hi half -- tokens m + 8 .. m + 11 -- lies beyond M here; wide_t_ok() implies M % 16 == 0, so this branch only trims whole tails)
-              }
-            }
-          } else {
-            const int rrow = lane >> 4, rcol = lane & 15;
-            const int nb = n0 + wn * 64 + J * 32 + rrow, m = m0 + g * 128 + ih * 64 + rcol * 4;
-#pragma unroll
-            for (int ps = 0; ps < 8; ++ps) {
-              const f32x4 v = *(const f32x4*)(scr + (ps * 4 + rrow) * 272 + rcol * 16);
-              const int n = nb + ps * 4;
-              if (n < N && m + 3 < M) epi.store_t(n, m, v, epi.load_t(n));
-            }
-          }
-          asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-          g256h_stamp<TRACE>(tr, g, wn, lane, 4 + 4 * (2 * J + ih));
-        }
-      }
-      g256h_stamp<TRACE>(tr, g, wn, lane, 17);
-      return;
-    }
-  }
-  if (epi_direct(epi, n0, 0)) {  // epilogues that want the fragment layout: (m, n..n+3) per lane straight from the accumulators
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-      const int m = m0 + g * 128 + i * 16 + l15;
-      if (m >= M) continue;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const int n = n0 + wn * 64 + j * 16 + l4 * 4;
-        if (n + 3 < N) {
-          f32x4 v = {acc[i][j][0], acc[i][j][1], acc[i][j][2], acc[i][j][3]};
-          epi.store(m, n, v, epi.load(m, n));
-        }
-      }
-    }
-    return;
-  }
-  if constexpr (epi_has_plain<Epi>::value) {
-    if (epi.plain_tile(n0, BN)) {
-      auto pe = epi.plain(n0);
-      g256h_epilogue_rows<BN, TRACE>(acc, smem, pe, m0, n0, M, N, g, wn, lane, wave, (dbg & LFM_DBG_GEMM_STORE8) != 0, tr);
-      return;
-    }
-  }
-  g256h_epilogue_rows<BN, TRACE>(acc, smem, epi, m0, n0, M, N, g, wn, lane, wave, (dbg & LFM_DBG_GEMM_STORE8) != 0, tr);
-  if constexpr (epi_has_finish_tile<Epi>::value) epi.finish_tile(m0, n0, g, wn, lane);
-  g256h_stamp<TRACE>(tr, g, wn, lane, 17);
-}
-
 template <int BN, bool TRACE = false, class Epi>
 __device__ __forceinline__ void g256h_epilogue(f32x4_t (&acc)[8][4], char* smem, Epi& epi, int m0, int n0, int M, int N, int g, int wn, int lane,
                                                int wave, int bz, long bsC, int dbg, bool swapped) {
@@ -408,7 +85,7 @@ __device__ __forceinline__ void g256h_epilogue(f32x4_t (&acc)[8][4], char* smem,
     g256h_epilogue_mod(acc, smem, epi, m0, n0, n0 / BN, N, g, wn, lane, wave);
     return;
   }
-  g256h_epilogue_body<BN, TRACE>(acc, smem, epi, m0, n0, M, N, g, wn, lane, wave, dbg, swapped, tr);
+  ho_block<HoMap16, BN, TRACE>(acc, smem, epi, m0, n0, M, N, g, wn, lane, wave, dbg, swapped, tr);
 }
 
 // Round 3, where the main loop goes (tools/mainloop_ablation.py on an LFM_MEASURE build, profiles/r03_mainloop_ablation.txt; epilogue off, fc2 shape

@@ -1,6 +1,7 @@
 // 256x128 "two-workgroups-per-CU" MFMA GEMM for gfx950 (v4):  C[m][n] = sum_k A[m][k] * W[n][k]  (+ fused epilogue).
 // Same operand / A-source / epilogue interfaces and the same wave -> accumulator mapping as the 256x256 kernels (a wave owns a
-// 128x64 block = 4 x 2 fragments of v_mfma_f32_32x32x16_f16), so the epilogue code is shared.
+// 128x64 block = 4 x 2 fragments of v_mfma_f32_32x32x16_f16); the epilogue is the hand-over of epilogue_handover.h with the 32x32x16 accumulator
+// map (HoMap32): this kernel keeps only the call.
 //
 // Why another generation: the 256x256 kernels run ONE 8-wave workgroup per CU with all 512 registers of every
 // SIMD.  Their epilogues (write 128 KiB fp16, or read-modify-write 256 KiB fp32 per tile) are bound by the memory path and no MFMA
@@ -181,7 +182,9 @@ __global__ __launch_bounds__(256, 2) void gemm256n_tn_kernel(ASrc asrc, const ha
     run(g256n_ic<0>{});
   }
   G256_BARRIER();  // every wave's last fragment reads are retired: the ring is free for the epilogue scratch (4 x 8.5 KiB)
-  g256_epilogue<G256N_BN>(acc, smem, epi, m0, n0, M, N, wm, wn, lane, wave, bz, bsC, dbg, swapped);
+  epi_batch(epi, bz, bsC, 0);
+  if (dbg & LFM_DBG_GEMM_NO_EPILOGUE) return;  // ablation: no epilogue
+  ho_block<HoMap32, G256N_BN>(acc, smem, epi, m0, n0, M, N, wm, wn, lane, wave, dbg, swapped);
 }
 
 template <class ASrc, class Epi>

@@ -17,7 +17,8 @@
 //                  after the barrier in the middle of tile t every wave has retired those reads (lgkmcnt(0) precedes it), so tile t + 2 may be
 //                  staged into b during step 1 of tile t; it is waited for (vmcnt(0), a full K-tile later) before the barrier in the middle of
 //                  tile t + 1, behind which its first reads are issued.
-// Epilogue: the wave's block is two 128 x 64 halves with v5's accumulator map, handed one after the other to the shared epilogue code.
+// Epilogue: the wave's block is two 128 x 64 halves with v5's accumulator map (HoMap16), handed one after the other to the hand-over of
+// epilogue_handover.h; this file keeps the 4-wave schedule of the folded LayerNorm's producer epilogue.
 #pragma once
 #include <utility>
 #include "gemm256h_kernel.h"
@@ -42,16 +43,14 @@ __device__ __forceinline__ void g256w_mfma(f32x4_t& c, const half8_t& a, const h
   asm volatile("v_mfma_f32_16x16x32_f16 %0, %1, %2, %0" : "+a"(c) : "v"(w), "v"(a));
 }
 
-// Producer epilogue of the folded LayerNorm-modulate for the 4-wave kernel (see g256h_epilogue_mod): wave (wm, wn) owns rows wm * 128 .., column
-// quarters 2 wn and 2 wn + 1 of the tile.  The X rows of the NEXT 32-row pass are requested before the stores of the current one are issued (vmcnt
-// returns in order: a load behind a pass's 16 stores waits for their round trip -- profiles/r02_epilogue_trace.txt, the "aux" column).
+// Producer epilogue of the folded LayerNorm-modulate, 4-wave form (the arithmetic and the LDS areas: epilogue_handover.h): wave (wm, wn) owns rows
+// wm * 128 .., column quarters 2 wn and 2 wn + 1 of the tile.  The X rows of the NEXT 32-row pass are requested before the stores of the current one
+// are issued (vmcnt returns in order: a load behind a pass's 16 stores waits for their round trip -- profiles/r02_epilogue_trace.txt, the "aux" column).
 template <class Epi>
 __device__ __forceinline__ void g256w_epilogue_mod(f32x4_t (&acc)[2][8][4], char* smem, const Epi& epi, int m0, int n0, int tile_n, int N, int wm, int wn,
                                                    int lane, int wave) {
-  char* scr = smem + wave * (32 * 272);
-  float* red = (float*)(smem + 8 * 32 * 272);           // [g][quarter][128 rows][2]
-  float* cen_s = (float*)(smem + 8 * 32 * 272 + 8192);  // [256 rows]
-  const int l15 = lane & 15, l4 = lane >> 4;
+  char* scr = ho_slot(smem, wave);
+  float* cen_s = (float*)(smem + HO_CEN_OFF);
   const int rrow = lane >> 4, rcol = lane & 15;
   const int img = m0 / epi.tokens;
   cen_s[threadIdx.x] = epi.cen[m0 + threadIdx.x];  // 256 threads, 256 rows
@@ -66,54 +65,21 @@ __device__ __forceinline__ void g256w_epilogue_mod(f32x4_t (&acc)[2][8][4], char
 #pragma unroll
   for (int h = 0; h < 2; ++h) {
     const int n = n0 + (2 * wn + h) * 64 + rcol * 4;
-    const f32x4 bias = *(const f32x4*)(epi.bias + n);
-    const f32x4 gate = *(const f32x4*)(epi.gate + (long)img * epi.gate_stride + n);
-    const f32x4 sc1 = *(const f32x4*)(epi.scale + (long)img * epi.mod_stride + n) + 1.0f;
+    const HoModCols k = HoModCols::load(epi, img, n);
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       const int cur = (h * 4 + i) & 1;
-#pragma unroll
-      for (int h2 = 0; h2 < 2; ++h2)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) *(f32x4_t*)(scr + (h2 * 16 + l15) * 272 + (j * 16 + l4 * 4) * 4) = acc[h][2 * i + h2][j];
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+      HoMap16::fill_rows(acc[h], i, scr, lane);
+      HO_LGKM0();
       if (h * 4 + i + 1 < 8) load_x(cur ^ 1, (h * 4 + i + 1) >> 2, (h * 4 + i + 1) & 3);
       const int rl = wm * 128 + i * 32 + rrow;
 #pragma unroll
-      for (int ps = 0; ps < 8; ++ps) {
-        const f32x4 v = *(const f32x4*)(scr + (ps * 4 + rrow) * 272 + rcol * 16);
-        const float c = cen_s[rl + ps * 4];
-        const f32x4 xn = xo[cur][ps] + gate * (v + bias);
-        *(f32x4*)(epi.X + (long)(m0 + rl + ps * 4) * epi.ldx + n) = xn;
-        const f32x4 d = xn - c;
-        const f32x4 ap = d * sc1;
-        const half4_t hh = {(half_t)ap.x, (half_t)ap.y, (half_t)ap.z, (half_t)ap.w};
-        *(half4_t*)(epi.A + (long)(m0 + rl + ps * 4) * N + n) = hh;
-        const float sx = g256h_row16_sum((xn.x + xn.y) + (xn.z + xn.w));
-        const float sq = g256h_row16_sum((d.x * d.x + d.y * d.y) + (d.z * d.z + d.w * d.w));
-        if (rcol == 0) {
-          float* dst = red + (((wm * 4 + 2 * wn + h) * 128) + i * 32 + ps * 4 + rrow) * 2;
-          dst[0] = sx;
-          dst[1] = sq;
-        }
-      }
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+      for (int ps = 0; ps < 8; ++ps) ho_mod_row(epi, scr, lane, ps, xo[cur][ps], cen_s, k, m0, rl, n, N, ho_red_pass(smem, wm, 2 * wn + h, i));
+      HO_LGKM0();
     }
   }
   __syncthreads();
-  if (wn == 0) {  // tile-level row sums (fixed order over the four column quarters) -> this tile's slot of the row's partials
-#pragma unroll
-    for (int rr = 0; rr < 2; ++rr) {
-      const int r = lane + 64 * rr;
-      float sx = 0.f, sq = 0.f;
-#pragma unroll
-      for (int w4 = 0; w4 < 4; ++w4) {
-        sx += red[((wm * 4 + w4) * 128 + r) * 2];
-        sq += red[((wm * 4 + w4) * 128 + r) * 2 + 1];
-      }
-      *(f32x2*)(epi.part + ((long)(m0 + wm * 128 + r) * epi.tiles_n + tile_n) * 2) = (f32x2){sx, sq};
-    }
-  }
+  if (wn == 0) ho_mod_tile_sums(epi, smem, wm, lane, m0, tile_n);
 }
 
 // ABL (LFM_MEASURE builds; results are garbage, timings are the point): 1 = no LDS-DMA after the prologue, 2 = no fragment reads, 3 = neither,
@@ -320,13 +286,13 @@ __global__ __launch_bounds__(256) void gemm256w_tn_kernel(ASrc asrc, const half_
           for (int i = 0; i < 8; ++i)
 #pragma unroll
             for (int j = 0; j < 4; ++j) view[i][j] = acc[i >> 2][4 * hn + j][i & 3];
-          g256h_epilogue_body<G256_BN>(view, smem, epi, m0, n0, M, N, wm, 2 * wn + hn, lane, wave, dbg, true, false);
+          ho_block<HoMap16, G256_BN>(view, smem, epi, m0, n0, M, N, wm, 2 * wn + hn, lane, wave, dbg, true);
         }
         return;
       }
     }
-    g256h_epilogue_body<G256_BN>(acc[0], smem, epi, m0, n0, M, N, wm, 2 * wn, lane, wave, dbg, false, false);
-    g256h_epilogue_body<G256_BN>(acc[1], smem, epi, m0, n0, M, N, wm, 2 * wn + 1, lane, wave, dbg, false, false);
+    ho_block<HoMap16, G256_BN>(acc[0], smem, epi, m0, n0, M, N, wm, 2 * wn, lane, wave, dbg, false);
+    ho_block<HoMap16, G256_BN>(acc[1], smem, epi, m0, n0, M, N, wm, 2 * wn + 1, lane, wave, dbg, false);
   }
 }
 

@@ -149,12 +149,18 @@ def test_gemm256_kernels(dev, M, N, K, epi, kernel):
         for _ in range(4):
             out = X.clone().to(dev) if epi == 3 else None
             outs.append(hip.gemm_f16(Ad, Wd, bd, epilogue=epi, out=out, gate=gate, gate_stride=N, tokens=tokens))
+        other = None
+        if not kernel >> 4:  # the 8-byte-store form of the same kernel: the same hand-over text read back four columns at a time
+            hip.gemm_select(kernel | (hip.DBG_GEMM_STORE8 << 4))
+            other = hip.gemm_f16(Ad, Wd, bd, epilogue=epi, out=X.clone().to(dev) if epi == 3 else None, gate=gate, gate_stride=N, tokens=tokens)
         torch.cuda.synchronize()
     finally:
         hip.gemm_select(0)
     assert rel_l2(outs[0], ref) < (2e-3 if epi in (0, 1) else 2e-4)
     for o in outs[1:]:
         assert torch.equal(o, outs[0])  # deterministic across launches (no data race on the LDS stages)
+    if other is not None:
+        assert torch.equal(other, outs[0])  # 16-byte and 8-byte stores carry the same bits (profiles/epilogue_handover_refactor.txt: so did the parent)
 
 
 @pytest.mark.parametrize("kernel", [4, 5, 6])
@@ -181,7 +187,7 @@ def _qkv_case(batch, tokens, D):
     return A, W, bias, A.float() @ W.float().t() + bias
 
 
-@pytest.mark.parametrize("kernel", [1, 4, 5, 5 | (hip.DBG_GEMM_STORE8 << 4), 6, 6 | (hip.DBG_GEMM_STORE8 << 4)])
+@pytest.mark.parametrize("kernel", [1, 4, 4 | (hip.DBG_GEMM_STORE8 << 4), 5, 5 | (hip.DBG_GEMM_STORE8 << 4), 6, 6 | (hip.DBG_GEMM_STORE8 << 4)])
 @pytest.mark.parametrize("batch,tokens,D,hd", [(3, 256, 384, 64), (8, 64, 512, 64), (2, 256, 1024, 64), (2, 256, 1152, 72), (3, 64, 576, 72)])
 def test_gemm_qkv_split(dev, batch, tokens, D, hd, kernel):
     """Fused QKV projection: Q, K row-major, V transposed per head (timm Attention's qkv + reshape + permute, DiT.py:120), with

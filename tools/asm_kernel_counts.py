@@ -19,9 +19,12 @@ def kernels(path):
         name, body = m.group(1), m.group(2)
         if name not in meta:
             continue
-        lines = [re.sub(r"\s*;.*", "", ln) for ln in body.splitlines()]
+        lines = [ln if "#ASM" in ln else re.sub(r"\s*;.*", "", ln) for ln in body.splitlines()]
         c = collections.Counter()
+        in_asm = False
         for ln in lines:
+            in_asm = (in_asm or "#ASMSTART" in ln) and "#ASMEND" not in ln
+            c["ds_read_b128_asm"] += in_asm and "ds_read_b128" in ln  # written out in inline asm: the K loops' fragment reads (the epilogues' scratch reads are the compiler's)
             c["mfma"] += "v_mfma" in ln
             c["ldsdma"] += bool(re.search(r"\bbuffer_load_dword\w* .* lds$|global_load_lds_", ln))
             c["ds_read_b128"] += "ds_read_b128" in ln
