@@ -397,11 +397,11 @@ int lfm_concat_channels_f16(const void* a, const void* b, void* out, long pixels
  * x, y fp16 NHWC [N*HW, C], e fp32 rows e_stride apart */
 int lfm_add_image_vec_f16(const void* x, const float* e, long e_stride, void* y, int N, int HW, int C, lfm_stream_t stream);
 /* QKVAttentionLegacy (unet.py:310-334) and the attention of EDM's UNetBlock: qkv fp16 [N*T, 3C], columns [head][q|k|v][ch]; out fp16 [N*T, C], columns
- * [head][ch]; softmax(q k^T / sqrt(ch)) v with fp32 scores and softmax.  Three kernels (lfm_unet_attention_plan tells which):
- *   2 = the resident MFMA kernel: T = 64 / 256 with ch = 64 / 128, all of K and V^T of a head in the LDS;
+ * [head][ch]; softmax(q k^T / sqrt(ch)) v with fp32 scores and softmax.  Three kernels (csrc/unet_attention_dispatch.h; lfm_unet_attention_plan tells which):
+ *   2 = the resident MFMA kernel (csrc/unet_attention_kernel.h, as the VALU kernel): T = 64 / 256 with ch = 64 / 128, all of K and V^T of a head in the LDS;
  *   1 = the VALU kernel: any ch, K, V and a 64-query score block in the LDS -- min(T, 64) (T + 1) 4 + 4 T (ch + 2) bytes <= 160 KiB
  *       (T <= 314 at ch = 64, T <= 127 at ch = 256);
- *   3 = the streamed MFMA kernel (LFM_OPT_UNET_ATTENTION_STREAM): every other shape with ch % 16 == 0 and ch <= 256, ANY T -- keys in blocks of 64
+ *   3 = the streamed MFMA kernel (csrc/unet_attention_stream_kernel.h, LFM_OPT_UNET_ATTENTION_STREAM): every other shape with ch % 16 == 0 and ch <= 256, ANY T -- keys in blocks of 64
  *       through a double-buffered LDS stage, online softmax.
  * The MFMA kernels need 16-byte aligned pointers; otherwise the VALU kernel runs where it fits.  LFM_ERR_SHAPE when no kernel serves the shape
  * (ch % 16 != 0 or ch > 256 beyond the VALU kernel's LDS bound).  No workspace, no synchronisation, graph-capturable. */

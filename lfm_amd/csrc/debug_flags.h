@@ -60,7 +60,7 @@ constexpr int LFM_DBG_CONV_HALO_SMALL = 16777216;    // the halo-tiled kernel fo
 // ---- VAE: the decoder (vae.hip)
 constexpr int LFM_DBG_VAE_SEPARATE_STATS = 4194304;  // GroupNorm statistics in a pass of their own, not in the convolution's epilogue; shares QKV_PER_ITEM, GEMM_ABL, TRACE_COL
 
-// ---- UNET: the UNets' own kernels (ops.hip)
+// ---- UNET: the UNets' own kernels (ops.hip, unet_attention_dispatch.h)
 constexpr int LFM_DBG_UNET_CONV_IN_SCALAR = 1;   // input convolution: the scalar kernel instead of the MFMA one
 constexpr int LFM_DBG_UNET_ATT_VALU = 16;        // attention: the VALU kernel instead of the MFMA one
 constexpr int LFM_DBG_UNET_GN_ROWS = 16384;      // GroupNorm: the three-kernel path instead of the one-kernel path for small maps

@@ -25,7 +25,7 @@ static struct {
   Opt att_stream{1};  // LFM_OPT_ATTENTION_STREAM: 256 tokens x head_dim 64 with more than 64 (image, head) items on the persistent streamed kernel
   Opt fused_qkv{1};   // LFM_OPT_FUSED_QKV_ATTENTION: folded path at 256 tokens x head_dim 64: QKV projection + attention in one kernel (qkv_attention_kernel.h)
   Opt att_tiled{1};   // LFM_OPT_ATTENTION_TILED: DiT attention at the token counts no other kernel serves on the tiled any-T kernel (attention_tiled_kernel.h); 2: every shape it takes
-  Opt unet_att_stream{1};  // LFM_OPT_UNET_ATTENTION_STREAM: UNet attention shapes neither the resident nor the VALU kernel serves on the streamed kernel (ops.hip: unet_attention_choose)
+  Opt unet_att_stream{1};  // LFM_OPT_UNET_ATTENTION_STREAM: UNet attention shapes neither the resident nor the VALU kernel serves on the streamed kernel (unet_attention_dispatch.h: unet_attention_choose)
 } g_def;
 static thread_local int tl_sel_set = 0, tl_gemm_sel = 0, tl_gemm_dbg = 0;  // per-call kernel selection active on this thread
 static thread_local int tl_fold = 0;                                       // 0: default, LFM_CALL_OFF, LFM_CALL_ON

@@ -714,207 +714,8 @@ extern "C" int lfm_concat_channels_f16(const void* a, const void* b, void* out, 
   return LFM_OK;
 }
 
-// ------------------------------------------------------------------ small-T attention (QKVAttentionLegacy, unet.py:310-334)
-// qkv: fp16 [N*T, 3*C], column layout [head][q | k | v][ch] (what reshape(bs*heads, 3*ch, T).split(ch) means for a
-// token-major tensor); out: fp16 [N*T, C] with columns [head][ch].  softmax((q*s)(k*s)^T) v with s = ch^-1/4, fp32 softmax.
-// Three kernels, chosen by unet_attention_choose below: this VALU kernel (any ch; all of K and V of a head as fp16 rows plus a 64-query fp32 score block in
-// the LDS, which bounds T: 314 tokens at ch = 64, 127 at ch = 256), the resident MFMA kernel (T = 64 / 256 x ch = 64 / 128) and the streamed MFMA kernel
-// (unet_attention_stream_kernel.h: ch % 16 == 0, ch <= 256, any T).  One workgroup per (head, image, 64 queries), one query per thread-group.
-__global__ __launch_bounds__(256) void attention_small_kernel(const half_t* __restrict__ qkv, half_t* __restrict__ out, int T, int heads, int ch,
-                                                              int QB) {
-  extern __shared__ __attribute__((aligned(16))) char smraw[];  // S fp32 [QB][T+1], then K, V fp16 [T][ch+2]
-  const int head = blockIdx.x, n = blockIdx.y, q0 = blockIdx.z * QB, tid = threadIdx.x;
-  const int nq = min(QB, T - q0);
-  const int C = heads * ch, ldq = 3 * C, ks = ch + 2;
-  float* S = (float*)smraw;
-  half_t* Ks = (half_t*)(S + QB * (T + 1));
-  half_t* Vs = Ks + T * ks;
-  const half_t* base = qkv + (long)n * T * ldq + head * 3 * ch;
-  for (int e = tid; e < T * ch; e += 256) {
-    const int t = e / ch, c = e - t * ch;
-    Ks[t * ks + c] = base[(long)t * ldq + ch + c];
-    Vs[t * ks + c] = base[(long)t * ldq + 2 * ch + c];
-  }
-  __syncthreads();
-  const float scale = rsqrtf((float)ch);  // (ch^-1/4)^2
-  for (int e = tid; e < nq * T; e += 256) {
-    const int t = e / T, s = e - t * T;
-    const half_t* q = base + (long)(q0 + t) * ldq;
-    float a = 0.f;
-    for (int c = 0; c < ch; ++c) a += (float)q[c] * (float)Ks[s * ks + c];
-    S[t * (T + 1) + s] = a * scale;
-  }
-  __syncthreads();
-  for (int t = tid; t < nq; t += 256) {
-    float* r = S + t * (T + 1);
-    float mx = r[0];
-    for (int s = 1; s < T; ++s) mx = fmaxf(mx, r[s]);
-    float sum = 0.f;
-    for (int s = 0; s < T; ++s) {
-      r[s] = __expf(r[s] - mx);
-      sum += r[s];
-    }
-    const float inv = 1.0f / sum;
-    for (int s = 0; s < T; ++s) r[s] *= inv;
-  }
-  __syncthreads();
-  half_t* ob = out + ((long)n * T + q0) * C + head * ch;
-  for (int e = tid; e < nq * ch; e += 256) {
-    const int t = e / ch, c = e - t * ch;
-    const float* r = S + t * (T + 1);
-    float a = 0.f;
-    for (int s = 0; s < T; ++s) a += r[s] * (float)Vs[s * ks + c];
-    ob[(long)t * C + c] = (half_t)a;
-  }
-}
-
-// MFMA path for the shapes the big UNets use (T = 64 / 256 tokens = 8x8 / 16x16 maps, ch = 64 / 128 per head).  The VALU kernel above was written for
-// "T <= 64, FLOPs negligible"; the celeb512 UNet attends at 16x16 (T = 256, ch = 128: 4.3 GFLOP per call at batch 32) and spent 5 % of an evaluation there
-// (85-104 us per call = 45 TFLOP/s).  One workgroup = 64 queries of one (image, head), a wave = 16 queries:
-//   K [T][ch] and V^T [ch][T] of the head in LDS (padded rows; V is transposed while it is staged, two keys per dword);
-//   S^T = K Q^T on v_mfma_f32_16x16x32_f16 with K as the A operand: lane (q = lane >> 4, j = lane & 15) ends up with the scores of ONE query j
-//   at keys 16 tile + 4 q + r -- the whole softmax row of a query lives in four lanes (two xor-shuffles per reduction), and
-//   O^T = V^T P^T takes P straight from those registers as the B operand: the 8 k-slots of lane q in key step kt are keys 32 kt + 4 q + r and
-//   32 kt + 16 + 4 q + r, which is what the two 8-byte V^T reads of the A operand fetch.  No transposition of P, no cross-lane traffic for O;
-//   fp32 scores / softmax, P and V in fp16 (as the DiT attention kernel), 1 / sum applied to the fp32 accumulators.
-template <int CH, int T>
-__global__ __launch_bounds__(256) void attention_unet_mfma_kernel(const half_t* __restrict__ qkv, half_t* __restrict__ out, int heads, float scale) {
-  constexpr int KS = CH * 2 + 16, VS = T * 2 + 16;  // LDS row strides in bytes (16 B of padding: consecutive rows start 4 banks apart)
-  extern __shared__ __attribute__((aligned(16))) char smraw[];
-  char* Ks = smraw;            // [T][KS]
-  char* Vt = smraw + T * KS;   // [CH][VS]
-  const int head = blockIdx.x, n = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int C = heads * CH, ldq = 3 * C;
-  const half_t* base = qkv + (long)n * T * ldq + head * 3 * CH;
-  // ---- stage K (16-byte chunks) and V^T (two keys x 8 channels per item -> eight dword writes)
-  for (int e = tid; e < T * (CH / 8); e += 256) {
-    const int t = e / (CH / 8), c8 = e - t * (CH / 8);
-    *(half8_t*)(Ks + t * KS + c8 * 16) = *(const half8_t*)(base + (long)t * ldq + CH + c8 * 8);
-  }
-  for (int e = tid; e < (T / 2) * (CH / 8); e += 256) {
-    const int tp = e % (T / 2), c8 = e / (T / 2);  // consecutive lanes: consecutive key pairs of one channel octet (conflict-free dword writes)
-    const half8_t v0 = *(const half8_t*)(base + (long)(2 * tp) * ldq + 2 * CH + c8 * 8);
-    const half8_t v1 = *(const half8_t*)(base + (long)(2 * tp + 1) * ldq + 2 * CH + c8 * 8);
-#pragma unroll
-    for (int i = 0; i < 8; ++i) *(half2_t*)(Vt + (c8 * 8 + i) * VS + tp * 4) = (half2_t){v0[i], v1[i]};
-  }
-  // ---- this wave's 16 queries as the B operand of S^T: lane (q, j) holds Q[q0 + j][32 ks + 8 q .. + 7]
-  const int j = lane & 15, q = lane >> 4;
-  const int q0 = blockIdx.z * 64 + wave * 16;
-  half8_t qf[CH / 32];
-#pragma unroll
-  for (int ks = 0; ks < CH / 32; ++ks) qf[ks] = *(const half8_t*)(base + (long)(q0 + j) * ldq + ks * 32 + q * 8);
-  __syncthreads();
-  // ---- S^T tiles: st[tile][r] = score of query j at key 16 tile + 4 q + r
-  f32x4 st[T / 16];
-#pragma unroll
-  for (int tile = 0; tile < T / 16; ++tile) {
-    f32x4 a = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int ks = 0; ks < CH / 32; ++ks) {
-      const half8_t kf = *(const half8_t*)(Ks + (tile * 16 + j) * KS + (ks * 4 + q) * 16);
-      a = __builtin_amdgcn_mfma_f32_16x16x32_f16(kf, qf[ks], a, 0, 0, 0);
-    }
-    st[tile] = a;
-  }
-  float mx = -3.0e38f;
-#pragma unroll
-  for (int tile = 0; tile < T / 16; ++tile) mx = fmaxf(fmaxf(fmaxf(st[tile].x, st[tile].y), fmaxf(st[tile].z, st[tile].w)), mx);
-  mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
-  mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-  const float sl = scale * 1.4426950408889634f, mo = mx * sl;
-  float sum = 0.f;
-  half4_t pf[T / 16];
-#pragma unroll
-  for (int tile = 0; tile < T / 16; ++tile) {
-    const float e0 = __builtin_amdgcn_exp2f(st[tile].x * sl - mo), e1 = __builtin_amdgcn_exp2f(st[tile].y * sl - mo);
-    const float e2 = __builtin_amdgcn_exp2f(st[tile].z * sl - mo), e3 = __builtin_amdgcn_exp2f(st[tile].w * sl - mo);
-    sum += (e0 + e1) + (e2 + e3);
-    pf[tile] = (half4_t){(half_t)e0, (half_t)e1, (half_t)e2, (half_t)e3};
-  }
-  sum += __shfl_xor(sum, 16, 64);
-  sum += __shfl_xor(sum, 32, 64);
-  const float inv = 1.0f / sum;
-  // ---- O^T = V^T P^T: channel tile ct, key step kt (32 keys = score tiles 2 kt, 2 kt + 1)
-  half_t* ob = out + ((long)n * T + q0 + j) * C + head * CH;
-#pragma unroll
-  for (int ct = 0; ct < CH / 16; ++ct) {
-    f32x4 o = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int kt = 0; kt < T / 32; ++kt) {
-      const char* vr = Vt + (ct * 16 + j) * VS + (kt * 32 + q * 4) * 2;
-      const half4_t va = *(const half4_t*)vr, vb = *(const half4_t*)(vr + 32);
-      const half8_t vf = {va[0], va[1], va[2], va[3], vb[0], vb[1], vb[2], vb[3]};
-      const half4_t pa = pf[2 * kt], pb = pf[2 * kt + 1];
-      const half8_t pp = {pa[0], pa[1], pa[2], pa[3], pb[0], pb[1], pb[2], pb[3]};
-      o = __builtin_amdgcn_mfma_f32_16x16x32_f16(vf, pp, o, 0, 0, 0);
-    }
-    // lane holds O[query j][channels 16 ct + 4 q .. + 3]
-    *(half4_t*)(ob + ct * 16 + q * 4) = (half4_t){(half_t)(o.x * inv), (half_t)(o.y * inv), (half_t)(o.z * inv), (half_t)(o.w * inv)};
-  }
-}
-
-template <int CH, int T>
-static int launch_attention_unet_mfma(const half_t* qkv, half_t* out, int N, int heads, hipStream_t st) {
-  constexpr int LDS = T * (CH * 2 + 16) + CH * (T * 2 + 16);
-  if (!lfm_kernel_lds<&attention_unet_mfma_kernel<CH, T>>(LDS)) return LFM_ERR_LAUNCH;
-  hipLaunchKernelGGL((attention_unet_mfma_kernel<CH, T>), dim3(heads, N, T / 64), dim3(256), LDS, st, qkv, out, heads, 1.0f / sqrtf((float)CH));
-  LFM_CHECK_LAUNCH();
-  return LFM_OK;
-}
-
-#include "unet_attention_stream_kernel.h"
-
-// ---- dispatch.  unet_attention_choose is the ONE place that knows which kernel serves a shape with 16-byte-aligned operands (lfm_unet_attention_plan returns its
-// answer without a launch: the CPU truth table of tests/test_unet_attention_ref.py).  Nothing a kernel served before the streamed one existed moves to it:
-// flag UNET_ATT_VALU decides first, then the four resident shapes, then whatever the VALU kernel's LDS admits, and only the rest is streamed.
-enum { UNET_ATT_VALU = 1, UNET_ATT_RESIDENT = 2, UNET_ATT_STREAM = 3 };
-static inline size_t unet_attention_valu_lds(int T, int ch) {  // S fp32 [min(T, 64)][T + 1], then K, V fp16 [T][ch + 2]
-  return (size_t)(T < 64 ? T : 64) * ((size_t)T + 1) * 4 + (size_t)4 * T * ((size_t)ch + 2);
-}
-static inline int unet_attention_choose(int T, int heads, int ch) {
-  if (T <= 0 || heads <= 0 || ch <= 0) return LFM_ERR_SHAPE;
-  const bool valu_fits = unet_attention_valu_lds(T, ch) <= 160 * 1024;
-  const bool stream_fits = ch % 16 == 0 && ch <= 256;
-  const int stream = lfm_unet_attention_stream_mode();
-  if (lfm_gemm_debug_flags() & LFM_DBG_UNET_ATT_VALU) return valu_fits ? UNET_ATT_VALU : LFM_ERR_SHAPE;  // flag: the VALU kernel or nothing (A/B)
-  if (stream == 2 && stream_fits) return UNET_ATT_STREAM;  // parity tests and A/B: every shape the streamed kernel takes
-  if ((T == 64 || T == 256) && (ch == 64 || ch == 128)) return UNET_ATT_RESIDENT;
-  if (valu_fits) return UNET_ATT_VALU;
-  if (stream && stream_fits) return UNET_ATT_STREAM;
-  return LFM_ERR_SHAPE;
-}
-extern "C" int lfm_unet_attention_plan(int N, int T, int heads, int ch) {
-  if (N <= 0) return LFM_ERR_SHAPE;
-  return unet_attention_choose(T, heads, ch);
-}
-
-extern "C" int lfm_attention_small_f16(const void* qkv, void* out, int N, int T, int heads, int ch, lfm_stream_t stream) {
-  if (!qkv || !out) return LFM_ERR_ARG;
-  if (N <= 0 || T <= 0 || heads <= 0 || ch <= 0) return LFM_ERR_SHAPE;
-  const half_t* qi = (const half_t*)qkv;
-  half_t* oi = (half_t*)out;
-  hipStream_t st = (hipStream_t)stream;
-  int kern = unet_attention_choose(T, heads, ch);
-  if ((((uintptr_t)qkv | (uintptr_t)out) & 15) && kern != UNET_ATT_VALU)  // the MFMA kernels read and write 16-byte chunks: the VALU kernel where it fits
-    kern = unet_attention_valu_lds(T, ch) <= 160 * 1024 ? UNET_ATT_VALU : LFM_ERR_SHAPE;
-  switch (kern) {
-    case UNET_ATT_RESIDENT:
-      if (T == 256 && ch == 128) return launch_attention_unet_mfma<128, 256>(qi, oi, N, heads, st);
-      if (T == 256 && ch == 64) return launch_attention_unet_mfma<64, 256>(qi, oi, N, heads, st);
-      if (T == 64 && ch == 128) return launch_attention_unet_mfma<128, 64>(qi, oi, N, heads, st);
-      return launch_attention_unet_mfma<64, 64>(qi, oi, N, heads, st);
-    case UNET_ATT_STREAM: return attention_unet_stream_launch(qi, oi, N, T, heads, ch, st);
-    case UNET_ATT_VALU: {
-      const int QB = T < 64 ? T : 64;  // queries per workgroup
-      if (!lfm_kernel_lds<&attention_small_kernel>(160 * 1024)) return LFM_ERR_LAUNCH;
-      hipLaunchKernelGGL(attention_small_kernel, dim3(heads, N, cdiv(T, QB)), dim3(256), unet_attention_valu_lds(T, ch), st, qi, oi, T, heads, ch, QB);
-      LFM_CHECK_LAUNCH();
-      return LFM_OK;
-    }
-    default: return LFM_ERR_SHAPE;
-  }
-}
+// ------------------------------------------------------------------ attention (QKVAttentionLegacy, unet.py:310-334): lfm_attention_small_f16, lfm_unet_attention_plan
+#include "unet_attention_dispatch.h"
 
 // ------------------------------------------------------------------ timestep embedding MLP (nn.py:103-121 + unet.py:633-641)
 // emb[r] = W2 silu(W0 [cos(t f) | sin(t f)] + b0) + b2 (+ label_emb[y[r]]);  also emits fp16 silu(emb) for the ResBlock emb_layers

@@ -1,34 +1,25 @@
-// Streamed attention of the UNets (QKVAttentionLegacy, unet.py:310-334; models/EDM.py UNetBlock) for ANY token count: the qkv layout and the arithmetic of
-// attention_unet_mfma_kernel (ops.hip), the key streaming and online softmax of the DiT side (attention_stream_kernel.h, attention_common.h).
-//   qkv fp16 [N*T, 3C], columns [head][q | k | v][ch]; out fp16 [N*T, C], columns [head][ch]; softmax(q k^T / sqrt(ch)) v.
-// The resident kernel holds all of K and V^T of a head in the LDS and every score of a query in registers: T is a template argument and ends at 256.  Here a
+// Streamed attention of the UNets (QKVAttentionLegacy, unet.py:310-334; models/EDM.py UNetBlock) for ANY token count.  qkv layout: unet_attention_kernel.h; LDS image,
+// operand mapping and arithmetic: unet_attention_common.h, one text with the resident kernel, whose token count is a template argument and ends at 256.  Here a
 // workgroup (NW waves x 16 queries of one (image, head)) walks the keys in blocks of 64 and only a block is resident:
-//   * two LDS stages of {K [64][CHP] | V^T [CHP][64]} (row strides padded by 16 bytes, as in the resident kernel).  The global loads of block i + 1 are issued into
+//   * two LDS stages (UattStage<CHP>): 36 KiB at CHP = 64 (four workgroups per CU), 138 KiB at CHP = 256 (one).  The global loads of block i + 1 are issued into
 //     registers BEFORE the MFMAs of block i and written to the other stage after them; one barrier per block (the stage written in iteration i was last read in
-//     iteration i - 1, which ended with a barrier).
-//   * V^T is built WHILE STAGING, exactly as the resident kernel does (two keys x 8 channels per item -> eight conflict-free dword writes), not with the LDS
-//     transpose reads of gfx950: the A operand of O^T = V^T P^T then is two plain 8-byte reads, the code both kernels share.
-//   * operand mapping of the resident kernel: S^T = K Q^T on v_mfma_f32_16x16x32_f16 with K as the A operand -- lane (q = lane >> 4, j = lane & 15) holds the scores
-//     of ONE query j at keys 16 tile + 4 q + r, a query's softmax row lives in four lanes -- and O^T = V^T P^T takes P straight from those registers as the B operand.
-//     No transposition of P, no cross-lane traffic for O.
-//   * online softmax per query in fp32: running maximum m and running sum l; when the maximum of ANY query of the wave rises, l and the O accumulators are scaled by
-//     2^((m_old - m_new) scale) (wave-uniform branch: blocks that leave every maximum alone skip the multiplications).  The four lanes of a query agree on m, so each
-//     keeps a PARTIAL sum and the two xor-shuffles of the sum happen once, after the last block.  P and V in fp16, fp32 accumulators, 1 / l applied once at the end.
+//     iteration i - 1, which ended with a barrier).  V^T is built while staging, not with the LDS transpose reads of gfx950.
+//   * online softmax per query in fp32: when the maximum of ANY query of the wave rises, l and the O accumulators are scaled by 2^((m_old - m_new) scale) (wave-uniform
+//     branch).  The four lanes of a query agree on m, so each keeps a PARTIAL sum and the two xor-shuffles of the sum happen once, after the last block.
 //   * any T >= 1: keys >= T of the ragged last block are never loaded (zeros in the LDS image) and their scores are set to -inf before the maximum; queries >= T are
 //     neither loaded nor stored.  ch % 16 == 0, 16 <= ch <= 256: CHP = ch rounded up to a multiple of 32 (the k extent of the MFMA), channels [ch, CHP) are zeros in
-//     the LDS image and in the Q fragments and their output tile is not stored -- nf = 192 models (48 / 144 per head) are served.
-//   * every global offset is 64-bit; no workspace, no allocation, no synchronisation: graph-capturable.
-// LDS: 2 x (64 (2 CHP + 16) + 144 CHP) bytes = 36 KiB at CHP = 64 (four workgroups per CU), 138 KiB at CHP = 256 (one).
-// Variants tried and what was kept: profiles/unet_attention_stream.txt.
+//     the LDS image and in the Q fragments and their output tile is not stored -- nf = 192 models (heads of 48 and of 3 x 48 channels) are served.
+//   * every global offset is 64-bit; no workspace, no allocation, no synchronisation: graph-capturable.  Variants tried: profiles/unet_attention_stream.txt.
 #pragma once
-#include "common.h"
+#include "unet_attention_common.h"
+template <int CHP>
+using UattStage = UattLayout<CHP, 64>;  // one LDS stage: a block of 64 keys (kernel and launcher)
 
 template <int CHP, int NW>
 __global__ __launch_bounds__(NW * 64) void attention_unet_stream_kernel(const half_t* __restrict__ qkv, half_t* __restrict__ out, int T, int heads, int ch,
                                                                         int qblocks, float scale) {
-  constexpr int KB = 64, NT = NW * 64, C8 = CHP / 8;
-  constexpr int KS = CHP * 2 + 16, VS = KB * 2 + 16;  // LDS row strides in bytes (16 B of padding: consecutive rows start 4 banks apart)
-  constexpr int STAGE = KB * KS + CHP * VS;
+  using L = UattStage<CHP>;
+  constexpr int KB = L::KEYS, NT = NW * 64, C8 = CHP / 8;
   constexpr int KITEMS = KB * C8, VITEMS = (KB / 2) * C8;  // 16-byte chunks of a K block; (key pair, channel octet) items of a V block
   constexpr int KIT = (KITEMS + NT - 1) / NT, VIT = (VITEMS + NT - 1) / NT;
   extern __shared__ __attribute__((aligned(16))) char smraw[];
@@ -40,7 +31,6 @@ __global__ __launch_bounds__(NW * 64) void attention_unet_stream_kernel(const ha
   const long ldq = 3L * C;
   const half_t* base = qkv + (long)n * T * ldq + (long)head * 3 * ch;
   const half8_t zero8 = {0, 0, 0, 0, 0, 0, 0, 0};
-
   // ---- a key block: global -> registers (issued a block ahead) -> LDS stage.  Keys >= T and channels >= ch are zeros and never read.
   half8_t kr[KIT], va[VIT], vb[VIT];
   auto load_block = [&](int k0) {
@@ -52,7 +42,7 @@ __global__ __launch_bounds__(NW * 64) void attention_unet_stream_kernel(const ha
     }
 #pragma unroll
     for (int it = 0; it < VIT; ++it) {
-      const int e = tid + it * NT, tp = e % (KB / 2), c8 = e / (KB / 2);  // consecutive lanes: consecutive key pairs of one channel octet (conflict-free dword writes)
+      const int e = tid + it * NT, tp = e % (KB / 2), c8 = e / (KB / 2);
       const bool live = (VITEMS % NT == 0 || e < VITEMS) && c8 * 8 < ch;
       const int t0 = k0 + 2 * tp;
       va[it] = live && t0 < T ? *(const half8_t*)(base + (long)t0 * ldq + 2 * ch + c8 * 8) : zero8;
@@ -60,73 +50,61 @@ __global__ __launch_bounds__(NW * 64) void attention_unet_stream_kernel(const ha
     }
   };
   auto store_block = [&](char* Ks) {
-    char* Vt = Ks + KB * KS;
+    char* Vt = Ks + L::VT;
 #pragma unroll
     for (int it = 0; it < KIT; ++it) {
       const int e = tid + it * NT, t = e / C8, c8 = e - t * C8;
-      if (KITEMS % NT == 0 || e < KITEMS) *(half8_t*)(Ks + t * KS + c8 * 16) = kr[it];
+      if (KITEMS % NT == 0 || e < KITEMS) *(half8_t*)(Ks + t * L::KS + c8 * 16) = kr[it];
     }
 #pragma unroll
     for (int it = 0; it < VIT; ++it) {
       const int e = tid + it * NT, tp = e % (KB / 2), c8 = e / (KB / 2);
       if (VITEMS % NT == 0 || e < VITEMS) {
 #pragma unroll
-        for (int i = 0; i < 8; ++i) *(half2_t*)(Vt + (c8 * 8 + i) * VS + tp * 4) = (half2_t){va[it][i], vb[it][i]};
+        for (int i = 0; i < 8; ++i) uatt_store_vt<L>(Vt, tp, c8 * 8 + i, va[it][i], vb[it][i]);
       }
     }
   };
-
   load_block(0);
-  // ---- this wave's 16 queries as the B operand of S^T: lane (q, j) holds Q[q0 + j][32 ks + 8 q .. + 7]
   const int j = lane & 15, q = lane >> 4;
   const int q0 = qb * (NW * 16) + wave * 16;
   const bool q_live = q0 + j < T;
   half8_t qf[CHP / 32];
 #pragma unroll
-  for (int ks = 0; ks < CHP / 32; ++ks)
-    qf[ks] = q_live && ks * 32 + q * 8 < ch ? *(const half8_t*)(base + (long)(q0 + j) * ldq + ks * 32 + q * 8) : zero8;
+  for (int ks = 0; ks < CHP / 32; ++ks) qf[ks] = uatt_q_frag(base + (long)(q0 + j) * ldq, ks, q, q_live, ch);
   store_block(smraw);
   __syncthreads();
-
   const float sl = scale * 1.4426950408889634f;
   float mrun = -3.0e38f, lsum = 0.f;  // running maximum of query j (the same in its four lanes), this lane's part of the running sum
   f32x4 o[CHP / 16];
 #pragma unroll
   for (int ct = 0; ct < CHP / 16; ++ct) o[ct] = (f32x4){0.f, 0.f, 0.f, 0.f};
-
   const int nblk = (T + KB - 1) / KB;
 #pragma unroll 1
   for (int b = 0; b < nblk; ++b) {
-    const char* Ks = smraw + (b & 1) * STAGE;
-    const char* Vt = Ks + KB * KS;
+    const char *Ks = smraw + (b & 1) * L::BYTES, *Vt = Ks + L::VT;
     const int k0 = b * KB;
     const bool more = b + 1 < nblk;
     if (more) load_block(k0 + KB);
-    // ---- S^T tiles: st[tile][r] = score of query j at key k0 + 16 tile + 4 q + r
-    f32x4 st[KB / 16];
+    f32x4 st[L::NTILE];  // st[tile][r] = score of query j at key k0 + 16 tile + 4 q + r
 #pragma unroll
-    for (int tile = 0; tile < KB / 16; ++tile) {
+    for (int tile = 0; tile < L::NTILE; ++tile) {
       f32x4 a = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-      for (int ks = 0; ks < CHP / 32; ++ks) {
-        const half8_t kf = *(const half8_t*)(Ks + (tile * 16 + j) * KS + (ks * 4 + q) * 16);
-        a = __builtin_amdgcn_mfma_f32_16x16x32_f16(kf, qf[ks], a, 0, 0, 0);
-      }
+      for (int ks = 0; ks < CHP / 32; ++ks) a = uatt_qk_step<L>(a, Ks, tile, ks, qf[ks], j, q);
       st[tile] = a;
     }
     if (k0 + KB > T) {  // the ragged last block: its zero padding must not take part in the maximum or the sum
 #pragma unroll
-      for (int tile = 0; tile < KB / 16; ++tile)
+      for (int tile = 0; tile < L::NTILE; ++tile)
 #pragma unroll
         for (int r = 0; r < 4; ++r)
           if (k0 + tile * 16 + q * 4 + r >= T) st[tile][r] = -__builtin_inff();
     }
-    float mx = fmaxf(fmaxf(st[0].x, st[0].y), fmaxf(st[0].z, st[0].w));
+    float mx = uatt_max4(st[0]);
 #pragma unroll
-    for (int tile = 1; tile < KB / 16; ++tile) mx = fmaxf(fmaxf(fmaxf(st[tile].x, st[tile].y), fmaxf(st[tile].z, st[tile].w)), mx);
-    mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
-    mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-    const float mnew = fmaxf(mrun, mx);
+    for (int tile = 1; tile < L::NTILE; ++tile) mx = fmaxf(uatt_max4(st[tile]), mx);
+    const float mnew = fmaxf(mrun, uatt_quad_max(mx));
     if (!__all(mnew == mrun)) {  // wave-uniform: some query's maximum rose (always in the first block)
       const float alpha = __builtin_amdgcn_exp2f((mrun - mnew) * sl);
       lsum *= alpha;
@@ -139,48 +117,33 @@ __global__ __launch_bounds__(NW * 64) void attention_unet_stream_kernel(const ha
       }
       mrun = mnew;
     }
+    half4_t pf[L::NTILE];
     const float mo = mrun * sl;
-    half4_t pf[KB / 16];
 #pragma unroll
-    for (int tile = 0; tile < KB / 16; ++tile) {
-      const float e0 = __builtin_amdgcn_exp2f(st[tile].x * sl - mo), e1 = __builtin_amdgcn_exp2f(st[tile].y * sl - mo);
-      const float e2 = __builtin_amdgcn_exp2f(st[tile].z * sl - mo), e3 = __builtin_amdgcn_exp2f(st[tile].w * sl - mo);
-      lsum += (e0 + e1) + (e2 + e3);
-      pf[tile] = (half4_t){(half_t)e0, (half_t)e1, (half_t)e2, (half_t)e3};
-    }
-    // ---- O^T += V^T P^T: channel tile ct, key step kt (32 keys = score tiles 2 kt, 2 kt + 1)
+    for (int tile = 0; tile < L::NTILE; ++tile) pf[tile] = uatt_exp2_tile(lsum, st[tile], sl, mo);
+    // all CHP / 16 channel tiles, branch-free: the tile of channels [ch, CHP) multiplies zeros and is never stored
 #pragma unroll
-    for (int ct = 0; ct < CHP / 16; ++ct) {  // all CHP / 16 tiles, branch-free: the tile of channels [ch, CHP) multiplies zeros and is never stored
+    for (int ct = 0; ct < CHP / 16; ++ct)
 #pragma unroll
-      for (int kt = 0; kt < KB / 32; ++kt) {
-        const char* vr = Vt + (ct * 16 + j) * VS + (kt * 32 + q * 4) * 2;
-        const half4_t v0 = *(const half4_t*)vr, v1 = *(const half4_t*)(vr + 32);
-        const half8_t vf = {v0[0], v0[1], v0[2], v0[3], v1[0], v1[1], v1[2], v1[3]};
-        const half4_t pa = pf[2 * kt], pb = pf[2 * kt + 1];
-        const half8_t pp = {pa[0], pa[1], pa[2], pa[3], pb[0], pb[1], pb[2], pb[3]};
-        o[ct] = __builtin_amdgcn_mfma_f32_16x16x32_f16(vf, pp, o[ct], 0, 0, 0);
-      }
-    }
-    if (more) store_block(smraw + ((b + 1) & 1) * STAGE);
+      for (int kt = 0; kt < L::NKT; ++kt) o[ct] = uatt_pv_step<L>(o[ct], Vt, ct, kt, pf, j, q);
+    if (more) store_block(smraw + ((b + 1) & 1) * L::BYTES);
     __syncthreads();
   }
   lsum += __shfl_xor(lsum, 16, 64);
   lsum += __shfl_xor(lsum, 32, 64);
   const float inv = 1.0f / lsum;
-  // lane holds O[query j][channels 16 ct + 4 q .. + 3]
   if (q_live) {
     half_t* ob = out + ((long)n * T + q0 + j) * C + (long)head * ch;
 #pragma unroll
     for (int ct = 0; ct < CHP / 16; ++ct)
-      if (ct * 16 < ch)
-        *(half4_t*)(ob + ct * 16 + q * 4) = (half4_t){(half_t)(o[ct].x * inv), (half_t)(o[ct].y * inv), (half_t)(o[ct].z * inv), (half_t)(o[ct].w * inv)};
+      if (ct * 16 < ch) uatt_store_o(ob, ct, q, o[ct], inv);
   }
 }
 
 // NW waves = NW x 16 queries per workgroup.  Grid: one workgroup per (image, head, query block), all in x (N is not bound by the 65535 of y / z).
 template <int CHP, int NW>
 static int launch_attention_unet_stream(const half_t* qkv, half_t* out, int N, int T, int heads, int ch, hipStream_t st) {
-  constexpr int LDS = 2 * (64 * (CHP * 2 + 16) + CHP * (64 * 2 + 16));
+  constexpr int LDS = 2 * UattStage<CHP>::BYTES;
   static_assert(LDS <= 160 * 1024, "two stages must fit the LDS");
   const int qblocks = (T + NW * 16 - 1) / (NW * 16);
   const long grid = (long)N * heads * qblocks;

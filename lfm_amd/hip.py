@@ -321,7 +321,7 @@ OPT_FOLD_LN = 1  # adaLN LayerNorm-modulate folded into the GEMM epilogues, defa
 OPT_SKINNY_GEMM = 4  # batch-1 DiT linears on the latency-mode kernels (1, default: csrc/gemm_sq64_kernel.h where rows % 64 == 0, else csrc/gemm_skinny_kernel.h; 2: always the latter; 0: split-K path)
 OPT_ATTENTION_STREAM = 5  # 256-token hd-64 attention on persistent workgroups with an LDS ring of K / V^T stages (csrc/attention_stream_kernel.h), default on; 0: one workgroup per item
 OPT_FUSED_QKV_ATTENTION = 6  # folded path, 256 tokens x hd 64: QKV projection + attention in one kernel (csrc/qkv_attention_kernel.h), default on; 0: two kernels
-OPT_UNET_ATTENTION_STREAM = 7  # UNet attention shapes beyond the resident and the VALU kernel on the streamed kernel (csrc/unet_attention_stream_kernel.h), default 1; 0: refused; 2: every shape it takes
+OPT_UNET_ATTENTION_STREAM = 7  # UNet attention shapes beyond the resident and the VALU kernel on the streamed kernel (csrc/unet_attention_stream_kernel.h; chooser: csrc/unet_attention_dispatch.h), default 1; 0: refused; 2: every shape it takes
 OPT_ATTENTION_TILED = 8  # DiT attention at the token counts no other kernel serves on the tiled any-T kernel (csrc/attention_tiled_kernel.h), default 1; 0: refused; 2: every shape it takes
 OPT_GEMM_V6 = 2  # chip-filling row-major GEMMs on the one-wave-per-SIMD 256x256 kernel (csrc/gemm256w_kernel.h) instead of the 8-wave one
 
@@ -397,7 +397,7 @@ def conv3x3_plan(N, H, W, Cin, Cout, mode=0, workspace_bytes=0):
 
 
 def unet_attention_plan(N, T, heads, ch):
-    """The kernel (1 VALU, 2 resident MFMA, 3 streamed MFMA; include/lfm_hip.h: lfm_unet_attention_plan) lfm_attention_small_f16 runs for this shape with
+    """The kernel (1 VALU, 2 resident MFMA, 3 streamed MFMA; include/lfm_hip.h: lfm_unet_attention_plan, csrc/unet_attention_dispatch.h) lfm_attention_small_f16 runs for this shape with
     16-byte-aligned operands under the calling thread's flags and the library options, or LFM_ERR_SHAPE (-1) (no launch, no GPU needed)."""
     return lib().lfm_unet_attention_plan(int(N), int(T), int(heads), int(ch))
 

@@ -295,7 +295,7 @@ def test_unet_options_match_reference_golden(golden_dir, which):
 
 @pytest.mark.parametrize("N,heads,ch,T", [(2, 4, 128, 256), (3, 2, 64, 256), (2, 4, 64, 64), (1, 8, 128, 64), (2, 2, 96, 64)])
 def test_unet_attention_mfma_vs_torch_and_the_valu_kernel(N, heads, ch, T):
-    """QKVAttentionLegacy (unet.py:310-334) on the MFMA kernel (T = 64 / 256, ch = 64 / 128) against fp32 torch on the same fp16 operands and
+    """QKVAttentionLegacy (unet.py:310-334) on the resident MFMA kernel (csrc/unet_attention_kernel.h; T = 64 / 256, ch = 64 / 128) against fp32 torch on the same fp16 operands and
     against the VALU kernel (flag UNET_ATT_VALU); any other shape (ch = 96 here) must still take the VALU kernel and agree with torch.  Scores have a
     realistic spread (|s| up to ~8 after scaling), so a wrong max / sum would show."""
     from lfm_amd import hip
@@ -321,7 +321,7 @@ def test_unet_attention_mfma_vs_torch_and_the_valu_kernel(N, heads, ch, T):
     got = run(0)
     assert torch.isfinite(got).all()
     assert rel_l2(got, ref) < 2e-3
-    if 64 * (T + 1) * 4 + 2 * T * (ch + 2) * 2 <= 160 * 1024:  # the VALU kernel keeps K, V and a score block in the LDS: T = 256 x ch = 128 does not fit
+    if 64 * (T + 1) * 4 + 2 * T * (ch + 2) * 2 <= 160 * 1024:  # the VALU kernel keeps K, V and a score block in the LDS: T = 256 x ch = 128 does not fit (the rule itself: csrc/unet_attention_dispatch.h, unet_attention_valu_lds; written out here by hand on purpose)
         valu = run(hip.DBG_UNET_ATT_VALU)
         assert rel_l2(valu, ref) < 2e-3
         assert rel_l2(got, valu) < 2e-3

@@ -1,7 +1,8 @@
-"""The streamed UNet attention kernel (csrc/unet_attention_stream_kernel.h) behind lfm_attention_small_f16: shapes no other kernel serves, against
+"""The streamed UNet attention kernel (csrc/unet_attention_stream_kernel.h; its steps are one text with the resident kernel's, csrc/unet_attention_common.h; the
+chooser and the launch: csrc/unet_attention_dispatch.h) behind lfm_attention_small_f16: shapes no other kernel serves, against
 float64 per (image, head) item on six constructed input families (tests/unet_attention_cases.py; the yardstick itself is checked without a GPU in
 tests/test_unet_attention_ref.py); the small shapes where indexing goes wrong first, forced onto it and compared with the kernel that serves them by
-default; nothing that was served before moved; and the models that need it, against the CPU oracles and the unmodified reference."""
+default; nothing that was served before moved; operands that are not 16-byte aligned fall back to the VALU kernel or are refused; and the models that need it, against the CPU oracles and the unmodified reference."""
 import os
 
 import pytest
@@ -20,15 +21,19 @@ def rel_l2(a, b):
     return float((a - b).norm() / b.norm())
 
 
-def _run(qkv, N, heads, ch, T, flags=0):
-    """lfm_attention_small_f16 on guarded buffers -> (out [N * T, heads * ch] fp16 on the device, the out guard on the CPU)."""
+def _run(qkv, N, heads, ch, T, flags=0, shift=0, out_shift=0):
+    """lfm_attention_small_f16 on guarded buffers -> (out [N * T, heads * ch] fp16 on the device, the out guard on the CPU).  shift / out_shift: qkv / out
+    starts that many fp16 values into its (16-byte aligned) buffer."""
     from lfm_amd import hip
 
     dev = torch.device("cuda:0")
     rows, C = N * T, heads * ch
-    tok = torch.full((rows + GUARD, 3 * C), float("nan"), dtype=torch.float16, device=dev)
+    buf = torch.full(((rows + GUARD) * 3 * C + shift,), float("nan"), dtype=torch.float16, device=dev)
+    tok = buf[shift:].view(rows + GUARD, 3 * C)
+    assert tok.data_ptr() % 16 == 2 * shift % 16
     tok[:rows] = uc.tokens(qkv).to(dev)
-    out = torch.full((rows + GUARD, C), SENTINEL, dtype=torch.float16, device=dev)
+    out = torch.full(((rows + GUARD) * C + out_shift,), SENTINEL, dtype=torch.float16, device=dev)[out_shift:].view(rows + GUARD, C)
+    assert out.data_ptr() % 16 == 2 * out_shift % 16
     hip.gemm_select(flags << 4)
     try:
         hip.check(hip.lib().lfm_attention_small_f16(hip.ptr(tok), hip.ptr(out), N, T, heads, ch, hip.stream_ptr()), "lfm_attention_small_f16")
@@ -65,9 +70,10 @@ def test_streamed_kernel_serves_what_was_refused(N, heads, ch, T):
         _check_case(family, N, heads, ch, T)
 
 
-# the small shapes: one token, one short of / one past a key block, two blocks and a key, the four resident shapes' kin, a VALU shape (ch = 96)
+# the small shapes: one token, one short of / one past a key block, two blocks and a key, the four resident shapes (128 x 256 is the largest resident
+# instantiation), a VALU shape (ch = 96)
 @pytest.mark.parametrize("N,heads,ch,T", [(2, 2, 64, 1), (2, 3, 64, 63), (2, 2, 64, 65), (1, 1, 32, 129), (2, 2, 64, 64), (2, 4, 64, 256), (2, 2, 128, 64),
-                                          (2, 2, 96, 64)])
+                                          (2, 2, 96, 64), (1, 2, 128, 256)])
 def test_streamed_kernel_forced_agrees_with_the_kernel_of_the_shape(N, heads, ch, T):
     from lfm_amd import hip
 
@@ -100,6 +106,29 @@ def test_nothing_served_before_moved(N, heads, ch, T):
     finally:
         hip.set_option(hip.OPT_UNET_ATTENTION_STREAM, 1)
     assert torch.equal(with_stream, without)
+
+
+def test_misaligned_operands_take_the_valu_kernel_or_are_refused():
+    """qkv, or out, 8 bytes past a 16-byte boundary (a view into a larger buffer): the MFMA kernels read and write 16-byte chunks, so the call runs the VALU
+    kernel, which reads and writes single fp16 values, where its LDS fits -- (2, 2, 64, 64), a resident shape: bit for bit the aligned run under flag UNET_ATT_VALU -- and is
+    refused where it does not: (2, 2, 64, 333), a streamed shape, needs 64 x 334 x 4 + 4 x 333 x 66 = 173 416 bytes > 160 KiB."""
+    from lfm_amd import hip
+
+    N, heads, ch, T = 2, 2, 64, 64
+    assert hip.unet_attention_plan(N, T, heads, ch) == 2
+    for family in uc.FAMILIES:
+        qkv = uc.case(family, N, heads, ch, T)[0]
+        aligned, _ = _run(qkv, N, heads, ch, T, flags=hip.DBG_UNET_ATT_VALU)
+        for shifts in (dict(shift=4), dict(out_shift=4)):
+            shifted, guard = _run(qkv, N, heads, ch, T, **shifts)
+            assert bool(torch.isfinite(shifted).all()), (family, shifts)
+            assert torch.equal(shifted, aligned), (family, shifts)
+            assert bool((guard == SENTINEL).all()), (family, shifts)
+    T = 333
+    assert hip.unet_attention_plan(N, T, heads, ch) == 3
+    for shifts in (dict(shift=4), dict(out_shift=4)):
+        with pytest.raises(hip.LfmHipError):
+            _run(uc.case("gauss", N, heads, ch, T)[0], N, heads, ch, T, **shifts)
 
 
 # ----------------------------------------------------------------------------- models

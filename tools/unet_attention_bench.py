@@ -1,4 +1,4 @@
-"""UNet attention alone: the streamed kernel (csrc/unet_attention_stream_kernel.h) against the resident MFMA kernel (csrc/ops.hip), same process, no profiler.
+"""UNet attention alone: the streamed kernel (csrc/unet_attention_stream_kernel.h) against the resident MFMA kernel (csrc/unet_attention_kernel.h), same process, no profiler.
 
     python tools/unet_attention_bench.py [windows]
 
