@@ -139,7 +139,10 @@ int lfm_dit_cond_table_build(const lfm_dit_shape* shape, const lfm_dit_weights* 
  * C[M,N] (+)= A[M,K] * W[N,K]^T on MFMA, fp16 operands, fp32 accumulate.  epilogue:
  *   0: C fp16 = acc + bias          1: C fp16 = gelu_tanh(acc + bias)       2: C fp32 = acc + bias
  *   3: C fp32 += gate[m / tokens][n] * (acc + bias)   (gate row stride gate_stride, 0 = shared row)
- * Replaces the nn.Linear calls inside timm Attention/Mlp (models/DiT.py:120,124) and adaLN (:128). */
+ * Replaces the nn.Linear calls inside timm Attention/Mlp (models/DiT.py:120,124) and adaLN (:128).
+ * Alignment (this entry point, lfm_gemm_qkv_f16 and lfm_linear*_f16 alike; LFM_ERR_ALIGN before any shape check or launch): A and W 16-byte aligned,
+ * lda and ldw multiples of 8 (operands move in 16-byte chunks), ldc a multiple of 4 (every epilogue stores 4-element vectors at m * ldc + n; the
+ * strides may exceed the row length).  K a multiple of the kernel's K-tile (64; 32 on the 256x128 kernel), N a multiple of 4: LFM_ERR_SHAPE. */
 int lfm_gemm_f16(const void* A, long lda, const void* W, long ldw, void* C, long ldc, int M, int N, int K, const float* bias,
                  int epilogue, const float* gate, long gate_stride, int tokens, lfm_stream_t stream);
 

@@ -282,7 +282,8 @@ extern "C" int lfm_ln_modulate(const float* X, void* A, int M, int D, int tokens
 extern "C" int lfm_gemm_f16(const void* A, long lda, const void* W, long ldw, void* C, long ldc, int M, int N, int K, const float* bias,
                             int epilogue, const float* gate, long gate_stride, int tokens, lfm_stream_t stream) {
   if (!A || !W || !C) return LFM_ERR_ARG;
-  if ((lda % 8) || ((uintptr_t)A & 15)) return LFM_ERR_ALIGN;
+  // every kernel moves 16-byte operand chunks, and every epilogue stores 4-element vectors at m * ldc + n: refused here, ahead of every shape check and launch
+  if ((lda % 8) || (ldw % 8) || (ldc % 4) || (((uintptr_t)A | (uintptr_t)W) & 15)) return LFM_ERR_ALIGN;
   hipStream_t st = (hipStream_t)stream;
   ASrcRowMajor a{(const half_t*)A, lda, M, 0};
   if (gemm_sel() == 7 || gemm_sel() == 8) {  // the latency-mode kernels on their own (parity tests): 7 = 64x64 tiles, 8 = all rows x 16 columns; <= 256 rows
@@ -312,7 +313,7 @@ extern "C" int lfm_gemm_f16(const void* A, long lda, const void* W, long ldw, vo
 extern "C" int lfm_gemm_qkv_f16(const void* A, long lda, const void* W, long ldw, void* Q, void* Kout, void* Vt, int M, int D, int K,
                                 const float* bias, int head_dim, int tokens, lfm_stream_t stream) {
   if (!A || !W || !Q || !Kout || !Vt || !bias) return LFM_ERR_ARG;
-  if ((lda % 8) || ((uintptr_t)A & 15)) return LFM_ERR_ALIGN;
+  if ((lda % 8) || (ldw % 8) || (((uintptr_t)A | (uintptr_t)W) & 15)) return LFM_ERR_ALIGN;
   if (head_dim <= 0 || tokens <= 0 || (D % head_dim) || (head_dim % 8) || (tokens % 16) || (M % tokens)) return LFM_ERR_SHAPE;  // 16: the V^T token groups (vt_pos)
   return gemm_f16_launch(ASrcRowMajor{(const half_t*)A, lda, M, 0}, (const half_t*)W, ldw, M, 3 * D, K,
                          EpiQKV::make((half_t*)Q, (half_t*)Kout, (half_t*)Vt, bias, D, head_dim, tokens), (hipStream_t)stream);

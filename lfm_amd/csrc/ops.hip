@@ -118,7 +118,8 @@ extern "C" int lfm_conv3x3_out_f32(const void* in, const void* w4, const float* 
 static int linear_f16_impl(const void* A, long lda, const void* W, long ldw, void* C, long ldc, int M, int N, int K, const float* bias, const void* resid,
                            float scale, lfm_stream_t stream) {
   if (!A || !W || !C) return LFM_ERR_ARG;
-  if ((lda % 8) || ((uintptr_t)A & 15)) return LFM_ERR_ALIGN;
+  // 16-byte operand chunks; the epilogue stores (and reads the residual) four columns at a time at m * ldc + n
+  if ((lda % 8) || (ldw % 8) || (ldc % 4) || (((uintptr_t)A | (uintptr_t)W) & 15)) return LFM_ERR_ALIGN;
   return launch_gemm_auto(ASrcRowMajor{(const half_t*)A, lda, M, 0}, (const half_t*)W, ldw, M, N, K,
                           EpiResidF16{(half_t*)C, ldc, bias, (const half_t*)resid, scale}, (hipStream_t)stream);
 }
@@ -138,7 +139,7 @@ static int linear2_f16_impl(const void* A1, int K1, const void* A2, int K2, cons
                             const void* resid, float scale, lfm_stream_t stream) {
   if (!A1 || !A2 || !W || !C) return LFM_ERR_ARG;
   if (K1 <= 0 || K2 <= 0 || (K1 % 64) || (K2 % 8)) return LFM_ERR_SHAPE;
-  if (((uintptr_t)A1 | (uintptr_t)A2) & 15) return LFM_ERR_ALIGN;
+  if ((ldw % 8) || (ldc % 4) || (((uintptr_t)A1 | (uintptr_t)A2 | (uintptr_t)W) & 15)) return LFM_ERR_ALIGN;
   return launch_gemm_auto(ASrcRowMajor2{(const half_t*)A1, (const half_t*)A2, K1, K2, M, 0}, (const half_t*)W, ldw, M, N, K1 + K2,
                           EpiResidF16{(half_t*)C, ldc, bias, (const half_t*)resid, scale}, (hipStream_t)stream);
 }
