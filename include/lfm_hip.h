@@ -394,6 +394,26 @@ int lfm_groupnorm2_f16(const void* xa, int Ca, const void* xb, int Cb, void* y, 
 int lfm_avgpool2_f16(const void* x, void* y, int N, int Ho, int Wo, int C, lfm_stream_t stream);
 /* y[N,Ho,Wo,C] = nearest-2x upsample of x[N,Ho/2,Wo/2,C]: EDM Conv2d(up=True, kernel=0) skip path (models/EDM.py:117-121) */
 int lfm_upsample2_f16(const void* x, void* y, int N, int Ho, int Wo, int C, lfm_stream_t stream);
+/* The [1,3,3,1] resampling filter of NCSN++ (EDM Conv2d with resample_filter = [1,3,3,1], models/EDM.py:96-98; f2 = outer(f, f) / 64), csrc/fir_resample.h.
+ * NHWC fp16, C % 8 == 0 (LFM_ERR_SHAPE), x / y / resid 16-byte aligned (LFM_ERR_ALIGN), both before any launch; fp32 arithmetic, one rounding to fp16.
+ *
+ * lfm_fir_down2_f16: y[N,Ho,Wo,C] = ((sum_{a,b<4} f2[a][b] x[2 oy - pad + a][2 ox - pad + b]) (+ bias[c]) (+ resid)) * scale, zeros outside x.
+ *   pad 1: x is [N,2Ho,2Wo,C] -- Conv2d(down=True) not fused, conv0 and skip of a `down` UNetBlock (:124-127);
+ *   pad 0: x is [N,2Ho+2,2Wo+2,C], the output of a 3x3 convolution at padding 2 -- the second half of Conv2d(down=True, fused_resample=True), the
+ *          aux_residual of the residual encoder (:116-118), whose bias is added AFTER the filter (:130-131).
+ *   bias fp32 [C] or NULL, resid fp16 on the output grid or NULL, scale applied in fp32: (x + aux_residual(aux)) / sqrt(2) of SongUNet.forward (:686) in the
+ *   same pass.  bias = resid = NULL and scale = 1: the bare filter. */
+int lfm_fir_down2_f16(const void* x, void* y, const float* bias, const void* resid, float scale, int N, int Ho, int Wo, int C, int pad,
+                      lfm_stream_t stream);
+/* y[N,Ho,Wo,C] = conv_transpose2d(x[N,Ho/2,Wo/2,C], 4 f2, stride 2, padding 1): Conv2d(up=True) not fused, conv0 and skip of an `up` UNetBlock (:120-123).
+ * Per axis y[2i] = (3 x[i] + x[i-1]) / 4, y[2i+1] = (3 x[i] + x[i+1]) / 4, zeros outside.  Ho, Wo even. */
+int lfm_fir_up2_f16(const void* x, void* y, int N, int Ho, int Wo, int C, lfm_stream_t stream);
+/* y[N,H+2,W+2,C] = x[N,H,W,C] inside a one-pixel border of zeros.  A pad-1 3x3 convolution (lfm_conv3x3_f16, mode 0, any path) of y on the (H+2) x (W+2)
+ * grid IS the padding-2 convolution of x that the fused down path starts with (models/EDM.py:117).  C % 8 == 0, 16-byte aligned. */
+int lfm_zero_border_f16(const void* x, void* y, int N, int H, int W, int C, lfm_stream_t stream);
+/* The same for fp32 planes, y[planes,H+2,W+2] = x[planes,H,W]: the NCHW network input (planes = N * Cin) that the first aux_residual convolves through
+ * lfm_conv3x3_in_f32.  Made by a kernel, not by a slice copy into a zeroed buffer: captured graphs of the UNets hold kernel nodes only. */
+int lfm_zero_border_f32(const float* x, float* y, int planes, int H, int W, lfm_stream_t stream);
 /* out[p][0:Ca | Ca:Ca+Cb] = a[p], b[p]   (th.cat([h, hs.pop()], dim=1), unet.py:649) */
 int lfm_concat_channels_f16(const void* a, const void* b, void* out, long pixels, int Ca, int Cb, lfm_stream_t stream);
 /* y = x + e[n][c] broadcast over the pixels of image n (ResBlock without scale-shift norm: h + emb_out[..., None, None], unet.py:233-235);
@@ -426,6 +446,13 @@ int lfm_time_embed(const float* t, int t_len, const float* w0, const float* b0, 
 int lfm_song_embed(const float* t, int t_len, const float* w0, const float* b0, const float* w1, const float* b1, const float* label_table,
                    const float* label_bias, float label_scale, const int64_t* y, int label_rows, float* scratch_h1, float* emb, void* emb_f16, int N,
                    int F, int E, lfm_stream_t stream);
+/* NCSN++ mapping network of SongUNet (embedding_type = "fourier": FourierEmbedding models/EDM.py:512-522 in place of the positional table; the rest of
+ * :663-675 as lfm_song_embed):  in = [sin(t g) | cos(t g)] (+ label term),  g_i = fl32(fl32(2 pi) * freqs[i]),  t g_i rounded to fp32 once more -- the
+ * reference's two fp32 roundings; freqs fp32 [F / 2] (the buffer map_noise.freqs, ~16 N(0,1): arguments of several hundred radians, full-range sine and
+ * cosine).  F = noise_channels = 2 * model_channels for the preset.  Every other argument, the outputs and the NaN-poisoning as lfm_song_embed. */
+int lfm_fourier_embed(const float* t, int t_len, const float* freqs, const float* w0, const float* b0, const float* w1, const float* b1,
+                      const float* label_table, const float* label_bias, float label_scale, const int64_t* y, int label_rows, float* scratch_h1,
+                      float* emb, void* emb_f16, int N, int F, int E, lfm_stream_t stream);
 
 /* ------------------------------------------------------------------ solver helpers (device-resident time grid)
  * Advance the captured step:  s = *step;  t_cur[0] = ts[s];  t_next[0] = ts[s+1];  dt_cur[0] = dts[s];  *step = s+1.

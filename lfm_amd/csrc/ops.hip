@@ -673,6 +673,10 @@ extern "C" int lfm_upsample2_f16(const void* x, void* y, int N, int Ho, int Wo, 
   return LFM_OK;
 }
 
+// ------------------------------------------------------------------ [1,3,3,1] FIR resampling and the zero-border copy (EDM Conv2d with the NCSN++ filter,
+// models/EDM.py:96-132): lfm_fir_down2_f16, lfm_fir_up2_f16, lfm_zero_border_f16, lfm_zero_border_f32
+#include "fir_resample.h"
+
 // ------------------------------------------------------------------ h + emb_out[..., None, None] (ResBlock without scale-shift norm, unet.py:233-235)
 __global__ void add_image_vec_kernel(const half8_t* __restrict__ x, const float* __restrict__ e, long e_stride, half8_t* __restrict__ y, int HW,
                                      int C8, long total) {
@@ -781,7 +785,12 @@ extern "C" int lfm_time_embed(const float* t, int t_len, const float* w0, const 
 // N x E values per evaluation: the correctly-rounded exp and a true division (silu_f's v_exp_f32 / v_rcp_f32 are ~2 ulp each, and this network has two
 // SiLUs in sequence where lfm_time_embed has one)
 __device__ __forceinline__ float silu_exact_f(float x) { return x / (1.0f + expf(-x)); }
-__global__ __launch_bounds__(256) void song_embed1_kernel(const float* __restrict__ t, int t_len, const float* __restrict__ w0, const float* __restrict__ b0,
+// FOURIER (NCSN++, FourierEmbedding models/EDM.py:512-522): the argument is t * (fl32(2 pi) * freqs[i]) with the reference's two fp32 roundings -- the table
+// in fp32 first, then the product with t -- instead of t * f_i; freqs ~ 16 N(0, 1), so the arguments reach several hundred radians: sinf / cosf reduce the
+// full range (the fast intrinsics do not)
+template <bool FOURIER>
+__global__ __launch_bounds__(256) void song_embed1_kernel(const float* __restrict__ t, int t_len, const float* __restrict__ freqs,
+                                                          const float* __restrict__ w0, const float* __restrict__ b0,
                                                           const float* __restrict__ label_table, const float* __restrict__ label_bias, float label_scale,
                                                           const int64_t* __restrict__ y, int label_rows, float* __restrict__ h1, int F, int E) {
   const int r = blockIdx.y, lane = threadIdx.x & 63;
@@ -800,7 +809,13 @@ __global__ __launch_bounds__(256) void song_embed1_kernel(const float* __restric
   float s = 0.f;
   for (int k = lane; k < 2 * half; k += 64) {
     const int i = k < half ? k : k - half;
-    const float a = tv * expf(-9.210340371976184f * (float)i / (float)(half - 1));
+    float a;
+    if (FOURIER) {
+      const float f2pi = 6.2831855f * freqs[i];  // rounded to fp32 before the product with t, as (2 * np.pi * self.freqs).to(x.dtype) is
+      a = tv * f2pi;
+    } else {
+      a = tv * expf(-9.210340371976184f * (float)i / (float)(half - 1));
+    }
     float v = k < half ? sinf(a) : cosf(a);
     if (lab) v += label_scale * lab[k] + label_bias[k];
     s += w[k] * v;
@@ -825,18 +840,34 @@ __global__ __launch_bounds__(256) void song_embed2_kernel(const float* __restric
   }
 }
 
-extern "C" int lfm_song_embed(const float* t, int t_len, const float* w0, const float* b0, const float* w1, const float* b1, const float* label_table,
-                              const float* label_bias, float label_scale, const int64_t* y, int label_rows, float* scratch_h1, float* emb,
-                              void* emb_f16, int N, int F, int E, lfm_stream_t stream) {
+static int song_embed_impl(const float* t, int t_len, const float* freqs, const float* w0, const float* b0, const float* w1, const float* b1,
+                           const float* label_table, const float* label_bias, float label_scale, const int64_t* y, int label_rows, float* scratch_h1,
+                           float* emb, void* emb_f16, int N, int F, int E, lfm_stream_t stream) {
   if (!t || !w0 || !b0 || !w1 || !b1 || !scratch_h1 || !emb || !emb_f16) return LFM_ERR_ARG;
   if ((label_table != nullptr) != (y != nullptr) || (label_table != nullptr) != (label_bias != nullptr)) return LFM_ERR_ARG;
   if (label_table && label_rows <= 0) return LFM_ERR_SHAPE;
   if (N <= 0 || F < 4 || (F & 1) || E <= 0 || (t_len != 1 && t_len != N)) return LFM_ERR_SHAPE;  // F >= 4: the endpoint table divides by F / 2 - 1
   hipStream_t st = (hipStream_t)stream;
-  hipLaunchKernelGGL(song_embed1_kernel, dim3(cdiv(E, 4), N), dim3(256), 0, st, t, t_len, w0, b0, label_table, label_bias, label_scale, y, label_rows,
-                     scratch_h1, F, E);
+  if (freqs)
+    hipLaunchKernelGGL(song_embed1_kernel<true>, dim3(cdiv(E, 4), N), dim3(256), 0, st, t, t_len, freqs, w0, b0, label_table, label_bias, label_scale, y,
+                       label_rows, scratch_h1, F, E);
+  else
+    hipLaunchKernelGGL(song_embed1_kernel<false>, dim3(cdiv(E, 4), N), dim3(256), 0, st, t, t_len, freqs, w0, b0, label_table, label_bias, label_scale, y,
+                       label_rows, scratch_h1, F, E);
   LFM_CHECK_LAUNCH();
   hipLaunchKernelGGL(song_embed2_kernel, dim3(cdiv(E, 4), N), dim3(256), 0, st, scratch_h1, w1, b1, emb, (half_t*)emb_f16, E);
   LFM_CHECK_LAUNCH();
   return LFM_OK;
+}
+extern "C" int lfm_song_embed(const float* t, int t_len, const float* w0, const float* b0, const float* w1, const float* b1, const float* label_table,
+                              const float* label_bias, float label_scale, const int64_t* y, int label_rows, float* scratch_h1, float* emb,
+                              void* emb_f16, int N, int F, int E, lfm_stream_t stream) {
+  return song_embed_impl(t, t_len, nullptr, w0, b0, w1, b1, label_table, label_bias, label_scale, y, label_rows, scratch_h1, emb, emb_f16, N, F, E, stream);
+}
+// NCSN++ mapping network: the same with the Fourier features [sin(t g) | cos(t g)], g_i = fl32(2 pi) freqs[i], freqs fp32 [F / 2] (map_noise.freqs)
+extern "C" int lfm_fourier_embed(const float* t, int t_len, const float* freqs, const float* w0, const float* b0, const float* w1, const float* b1,
+                                 const float* label_table, const float* label_bias, float label_scale, const int64_t* y, int label_rows,
+                                 float* scratch_h1, float* emb, void* emb_f16, int N, int F, int E, lfm_stream_t stream) {
+  if (!freqs) return LFM_ERR_ARG;
+  return song_embed_impl(t, t_len, freqs, w0, b0, w1, b1, label_table, label_bias, label_scale, y, label_rows, scratch_h1, emb, emb_f16, N, F, E, stream);
 }

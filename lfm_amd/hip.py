@@ -180,6 +180,16 @@ def lib():
     L.lfm_linear2_scaled_f16.argtypes = [V, I, V, I, V, LG, V, LG, I, I, V, V, F, V]
     L.lfm_song_embed.restype = I
     L.lfm_song_embed.argtypes = [V, I, V, V, V, V, V, V, F, V, I, V, V, V, I, I, I, V]
+    L.lfm_fourier_embed.restype = I
+    L.lfm_fourier_embed.argtypes = [V, I, V, V, V, V, V, V, V, F, V, I, V, V, V, I, I, I, V]
+    L.lfm_fir_down2_f16.restype = I
+    L.lfm_fir_down2_f16.argtypes = [V, V, V, V, F, I, I, I, I, I, V]
+    L.lfm_fir_up2_f16.restype = I
+    L.lfm_fir_up2_f16.argtypes = [V, V, I, I, I, I, V]
+    L.lfm_zero_border_f16.restype = I
+    L.lfm_zero_border_f16.argtypes = [V, V, I, I, I, I, V]
+    L.lfm_zero_border_f32.restype = I
+    L.lfm_zero_border_f32.argtypes = [V, V, I, I, I, V]
     L.lfm_vae_groupnorm_f16.restype = I
     L.lfm_vae_groupnorm_f16.argtypes = [V, V, V, V, V, C.c_size_t, I, I, I, I, V]
     L.lfm_vae_conv3x3_gn_f16.restype = I
@@ -408,6 +418,38 @@ def unet_attention(qkv, out, N, T, heads, ch):
         raise LfmHipError(f"UNet attention: no kernel serves T = {T} tokens x {ch} channels per head (limit: channels per head % 16 == 0 and <= 256 for any "
                           f"token count; other widths only while min(T, 64) * (T + 1) * 4 + 4 * T * (ch + 2) <= {160 * 1024} bytes of LDS)")
     check(lib().lfm_attention_small_f16(ptr(qkv), ptr(out), N, T, heads, ch, stream_ptr(qkv.device)), "lfm_attention_small_f16")
+    return out
+
+
+def fir_down2(x, N, Ho, Wo, C, pad=1, bias=None, resid=None, scale=1.0, out=None):
+    """lfm_fir_down2_f16: the [1,3,3,1] filter at stride 2 of x fp16 NHWC [N, 2Ho + 2 - 2pad, 2Wo + 2 - 2pad, C] onto the Ho x Wo grid,
+    out = (filtered + bias + resid) * scale (bias fp32 [C], resid fp16 [N*Ho*Wo, C], both optional)."""
+    require_gpu(x, "fir_down2")
+    if out is None:
+        out = torch.empty(N * Ho * Wo, C, dtype=torch.float16, device=x.device)
+    check(lib().lfm_fir_down2_f16(ptr(x), ptr(out), ptr(bias), ptr(resid), float(scale), N, Ho, Wo, C, pad, stream_ptr(x.device)), "lfm_fir_down2_f16")
+    return out
+
+
+def fir_up2(x, N, Ho, Wo, C, out=None):
+    """lfm_fir_up2_f16: the transposed [1,3,3,1] filter, x fp16 NHWC [N, Ho/2, Wo/2, C] -> [N*Ho*Wo, C]."""
+    require_gpu(x, "fir_up2")
+    if out is None:
+        out = torch.empty(N * Ho * Wo, C, dtype=torch.float16, device=x.device)
+    check(lib().lfm_fir_up2_f16(ptr(x), ptr(out), N, Ho, Wo, C, stream_ptr(x.device)), "lfm_fir_up2_f16")
+    return out
+
+
+def zero_border(x, N, H, W, C):
+    """x inside a one-pixel border of zeros: fp16 NHWC [N*H*W, C] -> [N*(H+2)*(W+2), C] (lfm_zero_border_f16), or fp32 NCHW [N, C, H, W] ->
+    [N, C, H+2, W+2] (lfm_zero_border_f32)."""
+    require_gpu(x, "zero_border")
+    if x.dtype == torch.float32:
+        out = torch.empty(N, C, H + 2, W + 2, device=x.device)
+        check(lib().lfm_zero_border_f32(ptr(x), ptr(out), N * C, H, W, stream_ptr(x.device)), "lfm_zero_border_f32")
+    else:
+        out = torch.empty(N * (H + 2) * (W + 2), C, dtype=torch.float16, device=x.device)
+        check(lib().lfm_zero_border_f16(ptr(x), ptr(out), N, H, W, C, stream_ptr(x.device)), "lfm_zero_border_f16")
     return out
 
 

@@ -17,14 +17,31 @@ liblfm_hip.so as the origin-ADM UNet (``lfm_amd/models/unet.py``):
 
 Built: ``use_context=False``, ``augment_dim=0``, channels that are multiples of 64 (the implicit-GEMM contract).
 
-``SongUNet`` (``model_type == "ddpm++"``, reference :532-706) is built for the DDPM++ settings only -- positional embedding, standard encoder and
+``SongUNet`` (``model_type == "ddpm++"``, reference :532-706) is built for the DDPM++ settings -- positional embedding, standard encoder and
 decoder, the [1,1] resample filter, ``channel_mult_noise=1`` -- on the same host-sequenced ops (``_EDMUNet`` holds what the two classes share).  What
 differs from the ADM: the mapping network (``lfm_song_embed``: [sin | cos] table with endpoint, the label term with a bias added BEFORE the first linear, a
 SiLU after the second), the non-adaptive FiLM ``silu(norm1(x + affine(emb)))`` (``lfm_add_image_vec_f16`` + GroupNorm), one attention head over the whole
 width (at most 256 channels: the streamed attention kernel's limit), a 1x1 skip convolution after every resample (``resample_proj``), and
 ``skip_scale = sqrt(0.5)`` on both residual sums, applied in fp32 by the scaled epilogues (``lfm_conv3x3_scaled_f16_ws``, ``lfm_linear_scaled_f16``,
-``lfm_linear2_scaled_f16``).  It has no ``forward_with_cfg``, as in the reference.  ``ncsn++`` stays refused: the reference cannot construct it either
-(``config.num_blocks`` is not a flag).
+``lfm_linear2_scaled_f16``).  It has no ``forward_with_cfg``, as in the reference.
+
+The other preset of the class, NCSN++ (``model_type == "ncsn++"``, reference :865-884: ``embedding_type="fourier"``, ``channel_mult_noise=2``,
+``encoder_type="residual"``, ``decoder_type="standard"``, ``resample_filter=[1,3,3,1]``), is built as a whole; every mixed combination, the two ``skip``
+types and ``augment_dim != 0`` stay refused by name.  What it adds to DDPM++:
+
+* the [1,3,3,1] filter in ``Conv2d(up / down)`` (:120-127): ``lfm_fir_down2_f16`` / ``lfm_fir_up2_f16`` on both branches of a resampling block, the
+  3x3 convolution in mode 0 (the fused nearest-2x of mode 1 belongs to the [1,1] filter);
+* the residual encoder (:611-621, :685-686): after every ``down`` block ``x = skips[-1] = aux = (x + aux_residual(aux)) / sqrt(2)``, where
+  ``aux_residual`` is ``Conv2d(kernel=3, down=True, fused_resample=True)`` -- the convolution at PADDING 2, then the filter at stride 2 without padding,
+  the bias after the filter (:116-118, :130-131).  Here: a zero-border copy, the existing pad-1 convolution on the (H+2) x (W+2) map
+  (``lfm_conv3x3_in_f32`` for the first one, whose input is the fp32 NCHW network input), and ``lfm_fir_down2_f16(pad=0)`` whose epilogue adds the bias
+  and the block's output and scales by sqrt(1/2) (``_conv_pad2_fir_down``);
+* the Fourier mapping network (:512-522): ``lfm_fourier_embed`` on the ``map_noise.freqs`` buffer, ``noise_channels = 2 * model_channels`` wide.
+
+``get_edm_network`` reads ``config.num_blocks`` for this preset, as the reference does; neither its parsers nor the drivers here have such a flag, so
+the preset is reached through ``create_network`` / ``SongUNet`` from code, and the drivers keep refusing ``--model_type ncsn++`` by name (the two
+driver files, ``test_flow_latent.py`` and ``test_flow_latent_ddp.py``, are deliberately left byte for byte as they were: a ``--num_blocks`` flag there is a
+change of its own).
 """
 import numpy as np
 import torch
@@ -56,7 +73,9 @@ class Linear(nn.Module):  # EDM.py:43-56 (parameter container)
 
 
 class Conv2d(nn.Module):  # EDM.py:63-98 (parameter container)
-    def __init__(self, in_channels, out_channels, kernel, bias=True, up=False, down=False, resample_filter=(1, 1),
+    reads_network_input = False  # set on the first aux_residual of an NCSN++ encoder: its input is the fp32 NCHW network input, not an fp16 NHWC map
+
+    def __init__(self, in_channels, out_channels, kernel, bias=True, up=False, down=False, resample_filter=(1, 1), fused_resample=False,
                  init_mode="kaiming_normal", init_weight=1, init_bias=0):
         assert not (up and down)
         super().__init__()
@@ -64,8 +83,12 @@ class Conv2d(nn.Module):  # EDM.py:63-98 (parameter container)
         kw = dict(mode=init_mode, fan_in=in_channels * kernel * kernel, fan_out=out_channels * kernel * kernel)
         self.weight = nn.Parameter(_weight_init([out_channels, in_channels, kernel, kernel], **kw) * init_weight) if kernel else None
         self.bias = nn.Parameter(_weight_init([out_channels], **kw) * init_bias) if kernel and bias else None
-        if tuple(resample_filter) != (1, 1):
-            raise NotImplementedError("only the [1,1] resample filter of DhariwalUNet is built")
+        if tuple(resample_filter) not in ((1, 1), (1, 3, 3, 1)):
+            raise NotImplementedError("only the [1,1] (DhariwalUNet, DDPM++) and [1,3,3,1] (NCSN++) resample filters are built")
+        if fused_resample and not (down and kernel == 3 and tuple(resample_filter) == (1, 3, 3, 1)):
+            raise NotImplementedError("fused_resample is built for the 3x3 down convolution under the [1,3,3,1] filter only (NCSN++'s aux_residual)")
+        self.fir = tuple(resample_filter) == (1, 3, 3, 1)  # the 4-tap kernels (lfm_fir_down2_f16 / lfm_fir_up2_f16) instead of the 2x2 mean / nearest 2x
+        self.fused_resample = fused_resample
         f = torch.as_tensor(resample_filter, dtype=torch.float32)
         f = f.ger(f).unsqueeze(0).unsqueeze(1) / f.sum().square()
         self.register_buffer("resample_filter", f if up or down else None)
@@ -80,10 +103,16 @@ class GroupNorm(nn.Module):  # EDM.py:139-151
         self.bias = nn.Parameter(torch.zeros(num_channels))
 
 
+class FourierEmbedding(nn.Module):  # EDM.py:512-522 (buffer container: ``map_noise.freqs`` of an NCSN++ state dict)
+    def __init__(self, num_channels, scale=16):
+        super().__init__()
+        self.register_buffer("freqs", torch.randn(num_channels // 2) * scale)
+
+
 class UNetBlock(nn.Module):  # EDM.py:188-292 (parameter container)
     def __init__(self, in_channels, out_channels, emb_channels, up=False, down=False, attention=False, num_heads=None,
-                 channels_per_head=64, dropout=0, skip_scale=1, eps=1e-5, resample_proj=False, adaptive_scale=True, init=None, init_zero=None,
-                 init_attn=None, scaled_epilogue=False):
+                 channels_per_head=64, dropout=0, skip_scale=1, eps=1e-5, resample_filter=(1, 1), resample_proj=False, adaptive_scale=True, init=None,
+                 init_zero=None, init_attn=None, scaled_epilogue=False):
         super().__init__()
         init, init_zero = init or {}, init_zero or dict(init_weight=0)
         self.in_channels, self.out_channels, self.up, self.down = in_channels, out_channels, up, down
@@ -92,13 +121,14 @@ class UNetBlock(nn.Module):  # EDM.py:188-292 (parameter container)
         if skip_scale != 1 and not scaled_epilogue:  # only SongUNet sequences its residual sums over the scaled epilogues
             raise NotImplementedError("skip_scale != 1 is built for SongUNet only (DhariwalUNet uses 1)")
         self.norm0 = GroupNorm(in_channels, eps=eps)
-        self.conv0 = Conv2d(in_channels, out_channels, 3, up=up, down=down, **init)
+        self.conv0 = Conv2d(in_channels, out_channels, 3, up=up, down=down, resample_filter=resample_filter, **init)
         self.affine = Linear(emb_channels, out_channels * (2 if adaptive_scale else 1), **init)
         self.norm1 = GroupNorm(out_channels, eps=eps)
         self.conv1 = Conv2d(out_channels, out_channels, 3, **init_zero)
         self.skip = None
         if out_channels != in_channels or up or down:
-            self.skip = Conv2d(in_channels, out_channels, 1 if resample_proj or out_channels != in_channels else 0, up=up, down=down, **init)
+            self.skip = Conv2d(in_channels, out_channels, 1 if resample_proj or out_channels != in_channels else 0, up=up, down=down,
+                               resample_filter=resample_filter, **init)
         if self.num_heads:
             self.norm2 = GroupNorm(out_channels, eps=eps)
             self.qkv = Conv2d(out_channels, out_channels * 3, 1, **(init_attn if init_attn is not None else init))
@@ -120,6 +150,12 @@ class _EDMUNet(HipUNetHost):
             pre = "enc." if group is self.enc else "dec."
             for name, b in group.items():
                 if b is out_norm or b is out_conv:  # SongUNet keeps its output layers inside `dec` (aux_norm / aux_conv): packed by the host layer
+                    continue
+                if isinstance(b, Conv2d) and b.fused_resample:  # NCSN++'s aux_residual: (weights, a zero bias for the convolution, the bias added AFTER the filter)
+                    if b.reads_network_input:  # fp32 NCHW in: the layout lfm_conv3x3_in_f32 reads
+                        P[pre + name] = (f32(b.weight, dev), torch.zeros(b.out_channels, device=dev), f32(b.bias, dev))
+                    else:
+                        P[pre + name] = (pack_conv3(b, dev)[0], None, f32(b.bias, dev))
                     continue
                 if isinstance(b, Conv2d):
                     P[pre + name] = (f32(b.weight, dev), f32(b.bias, dev))
@@ -156,13 +192,16 @@ class _EDMUNet(HipUNetHost):
             t = self._gn2(pair[0], pair[1], N, H * W, p["gn0"], None, True, g0, eps)
         else:
             t = self._gn(x, N, H * W, Cin, p["gn0"], None, True, g0, eps)
-        if b.down:  # Conv2d(down=True): a 2x2 mean, then the 3x3 convolution (EDM.py:96-125), on both branches
+        fir = b.conv0.fir  # the [1,3,3,1] filter (NCSN++): lfm_fir_down2_f16 / lfm_fir_up2_f16 on both branches, the convolution in mode 0
+        if b.down:  # Conv2d(down=True): a 2x2 mean (or the 4-tap filter), then the 3x3 convolution (EDM.py:96-125), on both branches
             H, W = H // 2, W // 2
-            t = self._resample(t, N, H, W, Cin, False)
-            orig = self._resample(orig, N, H, W, Cin, False)
-        elif b.up:  # Conv2d(up=True): nearest 2x fused into the convolution
+            t = self._resample(t, N, H, W, Cin, False, fir)
+            orig = self._resample(orig, N, H, W, Cin, False, fir)
+        elif b.up:  # Conv2d(up=True): nearest 2x fused into the convolution (the [1,1] filter only)
             H, W = H * 2, W * 2
-        h = self._conv(t, p["c0"], N, H, W, Cin, Cout, mode=1 if b.up else 0)
+            if fir:
+                t = self._resample(t, N, H, W, Cin, True, True)
+        h = self._conv(t, p["c0"], N, H, W, Cin, Cout, mode=1 if b.up and not fir else 0)
         fo, fw = self._packed["aff_all"][2][name]
         film = film_all[:, fo:fo + fw]  # fp32 [N, 2*Cout] = [scale | shift] (or [N, Cout]): this block's columns of the one affine GEMM (row stride = all blocks' columns)
         if b.adaptive_scale:
@@ -171,7 +210,7 @@ class _EDMUNet(HipUNetHost):
             hs = self._add_image_vec(h, film, N, H * W, Cout)
             t = self._gn(hs, N, H * W, Cout, p["gn1"], None, True, g1, eps)
         if b.up:  # skip(orig): nearest 2x upsample of the input (conv_transpose with the all-ones 2x2 filter), then the 1x1 convolution where there is one
-            orig = self._resample(orig, N, H, W, Cin, True)
+            orig = self._resample(orig, N, H, W, Cin, True, fir)
         if pair is not None:
             skip = self._linear2(pair[0], pair[1], p["skip"])
         else:
@@ -190,8 +229,12 @@ class _EDMUNet(HipUNetHost):
         N, Cin, H, W = x.shape
         emb_f16 = self._embed(t, N, y, drop_half_label, x.device)  # fp16 [N, E]: what every block's `affine` reads
         film_all = hip.gemm_f16(emb_f16, P["aff_all"][0], P["aff_all"][1], epilogue=2)  # fp32 [N, all blocks' affine columns]
-        skips, h = [], None
+        skips, h, aux = [], None, x  # aux: the residual encoder's second stream (NCSN++), the network input until the first aux_residual
         for name, b in self.enc.items():
+            if name.endswith("_aux_residual"):  # x = skips[-1] = aux = (x + aux_residual(aux)) / sqrt(2) (EDM.py:685-686): aux is one level up, 2H x 2W
+                h = skips[-1] = aux = self._conv_pad2_fir_down(aux, P["enc." + name], N, 2 * H, 2 * W, b.in_channels, b.out_channels, h, float(np.sqrt(0.5)),
+                                                                   nchw_f32=b.reads_network_input)
+                continue
             if isinstance(b, Conv2d):
                 h = self._conv_in(x, P["enc." + name], N, H, W, Cin)
             else:
@@ -301,20 +344,27 @@ class DhariwalUNet(_EDMUNet):
 
 
 class SongUNet(_EDMUNet):
-    """DDPM++ (reference EDM.py:532-706 as ``get_edm_network`` builds it for ``model_type == "ddpm++"``, :886-905)."""
+    """DDPM++ and NCSN++ (reference EDM.py:532-706 as ``get_edm_network`` builds it for ``model_type == "ddpm++"``, :886-905, and ``"ncsn++"``, :865-884):
+    exactly these two combinations of the five architecture settings; a mixed one is refused by the name of its first departure from DDPM++."""
 
     _what = "SongUNet"
+    NCSNPP = dict(embedding_type="fourier", channel_mult_noise=2, encoder_type="residual", decoder_type="standard", resample_filter=(1, 3, 3, 1))
 
     def __init__(self, img_resolution, in_channels, out_channels, label_dim=0, augment_dim=0, model_channels=128, channel_mult=(1, 2, 2, 2),
                  channel_mult_emb=4, num_blocks=4, attn_resolutions=(16,), dropout=0.10, label_dropout=0, embedding_type="positional",
                  channel_mult_noise=1, encoder_type="standard", decoder_type="standard", resample_filter=(1, 1)):
         super().__init__()
         self._init_host_state()
+        resample_filter = tuple(resample_filter)
+        got_all = dict(embedding_type=embedding_type, channel_mult_noise=channel_mult_noise, encoder_type=encoder_type, decoder_type=decoder_type,
+                       resample_filter=resample_filter)
+        ncsnpp = got_all == self.NCSNPP  # the whole preset or none of it: nobody has a model of a mixed kind
         for what, got, built in (("embedding_type", embedding_type, "positional"), ("channel_mult_noise", channel_mult_noise, 1),
                                  ("encoder_type", encoder_type, "standard"), ("decoder_type", decoder_type, "standard"),
-                                 ("resample_filter", tuple(resample_filter), (1, 1)), ("augment_dim", augment_dim, 0)):
-            if got != built:
-                raise NotImplementedError(f"SongUNet: {what}={got!r} is not built; only the ddpm++ settings are ({what}={built!r})")
+                                 ("resample_filter", resample_filter, (1, 1)), ("augment_dim", augment_dim, 0)):
+            if got != built and not (ncsnpp and what != "augment_dim"):
+                raise NotImplementedError(f"SongUNet: {what}={got!r} is not built; only the ddpm++ settings ({what}={built!r}) and the ncsn++ preset "
+                                          "as a whole (SongUNet.NCSNPP) are")
         widths = [model_channels * m for m in channel_mult]
         if any(w % 64 for w in widths):
             raise NotImplementedError(f"SongUNet: channel counts {widths} must all be multiples of 64 (the implicit-GEMM convolutions' contract)")
@@ -328,17 +378,19 @@ class SongUNet(_EDMUNet):
         self.img_resolution, self.in_channels, self.out_channels, self.model_channels = img_resolution, in_channels, out_channels, model_channels
         emb_channels = model_channels * channel_mult_emb
         noise_channels = model_channels * channel_mult_noise
-        self.emb_channels = emb_channels
+        self.emb_channels, self.noise_channels = emb_channels, noise_channels
         init = dict(init_mode="xavier_uniform")
         init_zero = dict(init_mode="xavier_uniform", init_weight=1e-5)
         init_attn = dict(init_mode="xavier_uniform", init_weight=np.sqrt(0.2))
-        bk = dict(emb_channels=emb_channels, num_heads=1, dropout=dropout, skip_scale=np.sqrt(0.5), eps=1e-6, resample_proj=True, adaptive_scale=False,
-                  init=init, init_zero=init_zero, init_attn=init_attn, scaled_epilogue=True)
+        bk = dict(emb_channels=emb_channels, num_heads=1, dropout=dropout, skip_scale=np.sqrt(0.5), eps=1e-6, resample_filter=resample_filter,
+                  resample_proj=True, adaptive_scale=False, init=init, init_zero=init_zero, init_attn=init_attn, scaled_epilogue=True)
+        if ncsnpp:  # registered first, as in the reference: `map_noise.freqs` leads the state dict (the positional embedding has no buffer and no module here)
+            self.map_noise = FourierEmbedding(noise_channels)
         self.map_label = Linear(label_dim, noise_channels, **init) if label_dim else None
         self.map_layer0 = Linear(noise_channels, emb_channels, **init)
         self.map_layer1 = Linear(emb_channels, emb_channels, **init)
         self.enc = nn.ModuleDict()
-        cout = in_channels
+        cout = caux = in_channels
         for level, mult in enumerate(channel_mult):
             res = img_resolution >> level
             if level == 0:
@@ -346,10 +398,14 @@ class SongUNet(_EDMUNet):
                 self.enc[f"{res}x{res}_conv"] = Conv2d(cin, cout, 3, **init)
             else:
                 self.enc[f"{res}x{res}_down"] = UNetBlock(cout, cout, down=True, **bk)
+                if ncsnpp:  # encoder_type == "residual" (EDM.py:611-621): the first one reads the network input, every later one `cout` channels
+                    self.enc[f"{res}x{res}_aux_residual"] = Conv2d(caux, cout, 3, down=True, resample_filter=resample_filter, fused_resample=True, **init)
+                    self.enc[f"{res}x{res}_aux_residual"].reads_network_input = level == 1  # `aux` is the fp32 NCHW network input until the first one has run
+                    caux = cout
             for idx in range(num_blocks):
                 cin, cout = cout, model_channels * mult
                 self.enc[f"{res}x{res}_block{idx}"] = UNetBlock(cin, cout, attention=(res in attn_resolutions), **bk)
-        skips = [b.out_channels for b in self.enc.values()]
+        skips = [b.out_channels for name, b in self.enc.items() if "aux" not in name]
         self.dec = nn.ModuleDict()
         for level, mult in reversed(list(enumerate(channel_mult))):
             res = img_resolution >> level
@@ -386,9 +442,10 @@ class SongUNet(_EDMUNet):
         P["time"] = tuple(f32(t, dev) for t in (self.map_layer0.weight, self.map_layer0.bias, self.map_layer1.weight, self.map_layer1.bias))
         # map_label(one_hot(y) * sqrt(L)) = sqrt(L) * W[:, y] + b: rows of W^T, the scale and the bias go to the kernel as they are (all fp32)
         P["label"] = (f32(self.map_label.weight, dev).t().contiguous(), f32(self.map_label.bias, dev)) if self.map_label is not None else None
+        P["freqs"] = f32(self.map_noise.freqs, dev) if hasattr(self, "map_noise") else None  # NCSN++: the Fourier table instead of the positional one
 
     def _embed(self, t, N, y, drop_half_label, dev):
-        P, E, F = self._packed, self.emb_channels, self.model_channels
+        P, E, F = self._packed, self.emb_channels, self.noise_channels
         lab, yy = None, None
         if P["label"] is not None and y is not None:  # y=None on a conditional model: the label term is left out (the label_dim=0 model on the same weights)
             lab, yy = P["label"], y.to(dev, torch.long).contiguous()
@@ -397,10 +454,12 @@ class SongUNet(_EDMUNet):
         emb_f16 = torch.empty(N, E, device=dev, dtype=torch.float16)
         h1 = torch.empty(N, E, device=dev)
         tw = P["time"]
-        hip.check(hip.lib().lfm_song_embed(hip.ptr(t), t.numel(), hip.ptr(tw[0]), hip.ptr(tw[1]), hip.ptr(tw[2]), hip.ptr(tw[3]),
-                                           hip.ptr(lab[0] if lab else None), hip.ptr(lab[1] if lab else None), float(np.sqrt(max(self.label_dim, 1))),
-                                           hip.ptr(yy), self.label_dim, hip.ptr(h1), hip.ptr(emb), hip.ptr(emb_f16), N, F, E, hip.stream_ptr(dev)),
-                  "lfm_song_embed")
+        rest = (hip.ptr(tw[0]), hip.ptr(tw[1]), hip.ptr(tw[2]), hip.ptr(tw[3]), hip.ptr(lab[0] if lab else None), hip.ptr(lab[1] if lab else None),
+                float(np.sqrt(max(self.label_dim, 1))), hip.ptr(yy), self.label_dim, hip.ptr(h1), hip.ptr(emb), hip.ptr(emb_f16), N, F, E, hip.stream_ptr(dev))
+        if P["freqs"] is not None:
+            hip.check(hip.lib().lfm_fourier_embed(hip.ptr(t), t.numel(), hip.ptr(P["freqs"]), *rest), "lfm_fourier_embed")
+        else:
+            hip.check(hip.lib().lfm_song_embed(hip.ptr(t), t.numel(), *rest), "lfm_song_embed")
         return emb_f16
 
     def forward(self, noise_labels, x, y=None, augment_labels=None, **kwargs):
@@ -409,17 +468,22 @@ class SongUNet(_EDMUNet):
 
 
 def get_edm_network(config):
-    """Reference models/EDM.py:864-939: ``adm`` -> DhariwalUNet, ``ddpm++`` -> SongUNet, each with the reference's argument list."""
+    """Reference models/EDM.py:864-939: ``adm`` -> DhariwalUNet, ``ddpm++`` and ``ncsn++`` -> SongUNet, each with the reference's argument list."""
     common = dict(img_resolution=config.image_size // config.f, in_channels=config.num_in_channels, out_channels=config.num_out_channels,
                   label_dim=config.label_dim, augment_dim=0, model_channels=config.nf, channel_mult=config.ch_mult, channel_mult_emb=4,
-                  num_blocks=config.num_res_blocks, attn_resolutions=config.attn_resolutions, dropout=config.dropout,
-                  label_dropout=config.label_dropout)
-    if config.model_type == "ddpm++":
-        m = SongUNet(embedding_type="positional", channel_mult_noise=1, encoder_type="standard", decoder_type="standard", resample_filter=[1, 1], **common)
+                  attn_resolutions=config.attn_resolutions, dropout=config.dropout, label_dropout=config.label_dropout)
+    if config.model_type in ("ddpm++", "ncsn++"):
+        if config.model_type == "ddpm++":
+            m = SongUNet(embedding_type="positional", channel_mult_noise=1, encoder_type="standard", decoder_type="standard", resample_filter=[1, 1],
+                         num_blocks=config.num_res_blocks, **common)
+        else:  # the reference reads config.num_blocks here (:875), not num_res_blocks, and no driver has such a flag
+            if getattr(config, "num_blocks", None) is None:
+                raise NotImplementedError("model_type 'ncsn++' needs config.num_blocks: the reference (models/EDM.py:875) reads that name, not "
+                                          "num_res_blocks, and no parser sets it")
+            m = SongUNet(num_blocks=config.num_blocks, **common, **SongUNet.NCSNPP)
         if getattr(config, "random_weights", False):
             m.redraw_small_()
         return m
     if config.model_type != "adm":
-        raise NotImplementedError(f"model_type {config.model_type!r}: ncsn++ (the reference reads config.num_blocks, which is not a flag) and adm_context "
-                                  "are out of scope (SURVEY.md §2)")
-    return DhariwalUNet(**common)
+        raise NotImplementedError(f"model_type {config.model_type!r}: adm_context is out of scope (SURVEY.md §2)")
+    return DhariwalUNet(num_blocks=config.num_res_blocks, **common)

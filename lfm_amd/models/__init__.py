@@ -5,9 +5,10 @@ from .DiT import DiT, DiT_models
 def create_network(config):
     """``create_network(args) -> nn.Module`` with the reference's dispatch (models/__init__.py:6-17).
 
-    DiT-*, ``--use_origin_adm`` (guided-diffusion ``UNetModel``), the EDM ``adm`` (``DhariwalUNet``) and ``ddpm++``
-    (``SongUNet`` with the DDPM++ settings) are built on the HIP path.  ``ncsn++`` (the reference cannot construct it either) and
-    ``--layout`` (UNetModelAttn) are out of scope and raise instead of silently falling back to anything.
+    DiT-*, ``--use_origin_adm`` (guided-diffusion ``UNetModel``), the EDM ``adm`` (``DhariwalUNet``), ``ddpm++`` and
+    ``ncsn++`` (``SongUNet`` with the DDPM++ settings or the whole NCSN++ preset; the latter reads ``config.num_blocks``, as in the
+    reference) are built on the HIP path.  ``--layout`` (UNetModelAttn) is out of scope and raises instead of silently falling back to
+    anything.
     """
     if getattr(config, "use_origin_adm", False):
         return get_flow_model(config)

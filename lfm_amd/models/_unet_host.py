@@ -166,12 +166,25 @@ class HipUNetHost(PackedModule):
                                                     hip.stream_ptr(h.device)), "lfm_concat_channels_f16")
         return cat
 
-    def _resample(self, x, N, Ho, Wo, C, up):
-        """Nearest 2x (`up`) or 2x2 mean, to the Ho x Wo OUTPUT grid."""
+    def _resample(self, x, N, Ho, Wo, C, up, fir=False):
+        """Nearest 2x (`up`) or 2x2 mean, to the Ho x Wo OUTPUT grid; `fir`: the [1,3,3,1] filter in either direction instead (NCSN++)."""
+        if fir:
+            return hip.fir_up2(x, N, Ho, Wo, C) if up else hip.fir_down2(x, N, Ho, Wo, C)
         y = torch.empty(N * Ho * Wo, C, dtype=torch.float16, device=x.device)
         fn, what = (hip.lib().lfm_upsample2_f16, "lfm_upsample2_f16") if up else (hip.lib().lfm_avgpool2_f16, "lfm_avgpool2_f16")
         hip.check(fn(hip.ptr(x), hip.ptr(y), N, Ho, Wo, C, hip.stream_ptr(x.device)), what)
         return y
+
+    def _conv_pad2_fir_down(self, x, wb, N, H, W, Cin, Cout, resid, scale, nchw_f32=False):
+        """EDM's Conv2d(kernel=3, down=True, fused_resample=True) under the [1,3,3,1] filter, with a residual epilogue: the 3x3 convolution at PADDING 2
+        (the pad-1 convolution of x inside a zero border, on the (H+2) x (W+2) grid), then the filter at stride 2 without padding onto H/2 x W/2, then
+        (. + bias + resid) * scale.  `x`: fp16 NHWC [N*H*W, Cin], or (`nchw_f32`) the fp32 NCHW network input.  `wb` = (weights, the convolution's zero bias, the late bias)."""
+        xb = hip.zero_border(x, N, H, W, Cin)
+        if nchw_f32:
+            full = self._conv_in(xb, wb, N, H + 2, W + 2, Cin)
+        else:
+            full = self._conv(xb, wb, N, H + 2, W + 2, Cin, Cout)
+        return hip.fir_down2(full, N, H // 2, W // 2, Cout, pad=0, bias=wb[2], resid=resid, scale=scale)
 
     def _add_image_vec(self, x, vec, N, HW, C):
         """x + vec[:, None, None]: `vec` fp32 [N, C], a column slice of the stacked projection."""

@@ -25,9 +25,9 @@ def _emb_hook(m, store):
     return m.map_layer1.register_forward_hook(hook)
 
 
-def golden_song(ref_edm, cfg, batch, with_solve):
+def golden_song(ref_edm, cfg, batch, with_solve, load=sc.load_seeded):
     m = ref_edm.SongUNet(**cfg).eval()
-    rec = {"cfg": cfg, "state_seed": sc.STATE_SEED, "state_checksum": sc.load_seeded(m), "params": sum(p.numel() for p in m.parameters()),
+    rec = {"cfg": cfg, "state_seed": sc.STATE_SEED, "state_checksum": load(m), "params": sum(p.numel() for p in m.parameters()),
            "keys": [(k, tuple(v.shape)) for k, v in m.state_dict().items()]}
     g = torch.Generator().manual_seed(31 + batch)
     R, C = cfg["img_resolution"], cfg["in_channels"]
