@@ -432,6 +432,25 @@ int lfm_attention_small_f16(const void* qkv, void* out, int N, int T, int heads,
 /* Which kernel lfm_attention_small_f16 runs for this shape with 16-byte aligned operands under the calling thread's flags (LFM_DBG_UNET_ATT_VALU decides
  * first: 1 or LFM_ERR_SHAPE) and the library options: 1 / 2 / 3 as above, or LFM_ERR_SHAPE.  No launch; usable without a GPU. */
 int lfm_unet_attention_plan(int N, int T, int heads, int ch);
+/* Cross-attention of the SpatialTransformer (guided_diffusion/attention.py:177-215, CrossAttention with a context; csrc/unet_cross_attention_kernel.h):
+ *   out[n*Tq + i][head*ch + c] = softmax_j(q_i . k_j / sqrt(ch)) v_j over the Tk keys of image n.
+ * Q fp16 rows [N*Tq] ldq elements apart; K and V fp16 rows [N*Tk] ldkv apart -- they may be two column slices of one projection buffer, hence one ld; out
+ * fp16 rows [N*Tq] ldo apart; columns [head][ch] everywhere.  fp32 scores and softmax, P and V in fp16, 1 / sum applied to the fp32 accumulators: the
+ * arithmetic and the 64-key block order of the streamed kernel of lfm_attention_small_f16 (bit-identical to it where Tq == Tk).  Any Tq >= 1 and Tk >= 1;
+ * ch % 16 == 0, ch <= 256, every ld >= heads*ch (LFM_ERR_SHAPE); the four pointers 16-byte aligned and every ld % 8 == 0 (LFM_ERR_ALIGN); both checked before
+ * any launch.  No mask argument.  No workspace, no allocation, no synchronisation: graph-capturable. */
+int lfm_cross_attention_f16(const void* Q, long ldq, const void* K, const void* V, long ldkv, void* out, long ldo, int N, int Tq, int Tk, int heads,
+                            int ch, lfm_stream_t stream);
+/* 1 when lfm_cross_attention_f16 serves this shape (with aligned operands), LFM_ERR_SHAPE otherwise.  No launch; usable without a GPU. */
+int lfm_cross_attention_plan(int N, int Tq, int Tk, int heads, int ch);
+/* nn.LayerNorm(C) on fp16 rows: y[m] = (x[m] - mean) / sqrt(var + eps) * gamma + beta, x and y dense fp16 [M, C], gamma / beta fp32 [C].  fp32 statistics
+ * in two passes (mean, then the centred sum of squares; biased variance), one rounding to fp16; one wave per row (csrc/token_ops.h).  C % 8 == 0
+ * (LFM_ERR_SHAPE); x, y, gamma, beta 16-byte aligned (LFM_ERR_ALIGN).  No workspace, graph-capturable. */
+int lfm_layernorm_f16(const void* x, void* y, const float* gamma, const float* beta, long M, int C, float eps, lfm_stream_t stream);
+/* GEGLU (attention.py:85-92): y[m][i] = h[m][i] * gelu(h[m][I + i]) with the exact (erf) GELU of F.gelu's default -- not the tanh form.  h fp16 rows [M]
+ * ldh elements apart, 2I columns used; y dense fp16 [M, I].  fp32 arithmetic, one rounding.  I % 8 == 0, ldh >= 2I (LFM_ERR_SHAPE); ldh % 8 == 0 and h, y
+ * 16-byte aligned (LFM_ERR_ALIGN).  No workspace, graph-capturable. */
+int lfm_geglu_f16(const void* h, long ldh, void* y, long M, int I, lfm_stream_t stream);
 /* emb = time_embed(timestep_embedding(t, F)) (+ label_emb[y]) (nn.py:103-121, unet.py:633-641): fp32 [N,E] and fp16 silu(emb).
  * label_table has label_rows rows; a label outside [0, label_rows) (an IndexError in the reference) poisons its row with NaN. */
 int lfm_time_embed(const float* t, int t_len, const float* w0, const float* b0, const float* w2, const float* b2, const float* label_table,

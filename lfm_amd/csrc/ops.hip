@@ -722,6 +722,11 @@ extern "C" int lfm_concat_channels_f16(const void* a, const void* b, void* out, 
 // ------------------------------------------------------------------ attention (QKVAttentionLegacy, unet.py:310-334): lfm_attention_small_f16, lfm_unet_attention_plan
 #include "unet_attention_dispatch.h"
 
+// ------------------------------------------------------------------ SpatialTransformer (attention.py:85-280): lfm_cross_attention_f16, lfm_cross_attention_plan;
+// lfm_layernorm_f16, lfm_geglu_f16
+#include "unet_cross_attention_kernel.h"
+#include "token_ops.h"
+
 // ------------------------------------------------------------------ timestep embedding MLP (nn.py:103-121 + unet.py:633-641)
 // emb[r] = W2 silu(W0 [cos(t f) | sin(t f)] + b0) + b2 (+ label_emb[y[r]]);  also emits fp16 silu(emb) for the ResBlock emb_layers
 __global__ __launch_bounds__(256) void time_embed1_kernel(const float* __restrict__ t, int t_len, const float* __restrict__ w0,

@@ -168,6 +168,14 @@ def lib():
     L.lfm_attention_small_f16.argtypes = [V, V, I, I, I, I, V]
     L.lfm_unet_attention_plan.restype = I
     L.lfm_unet_attention_plan.argtypes = [I, I, I, I]
+    L.lfm_cross_attention_f16.restype = I
+    L.lfm_cross_attention_f16.argtypes = [V, LG, V, V, LG, V, LG, I, I, I, I, I, V]
+    L.lfm_cross_attention_plan.restype = I
+    L.lfm_cross_attention_plan.argtypes = [I, I, I, I, I]
+    L.lfm_layernorm_f16.restype = I
+    L.lfm_layernorm_f16.argtypes = [V, V, V, V, LG, I, F, V]
+    L.lfm_geglu_f16.restype = I
+    L.lfm_geglu_f16.argtypes = [V, LG, V, LG, I, V]
     L.lfm_time_embed.restype = I
     L.lfm_time_embed.argtypes = [V, I, V, V, V, V, V, V, I, V, V, V, I, I, I, V]
     L.lfm_conv3x3_scaled_f16_ws.restype = I
@@ -418,6 +426,67 @@ def unet_attention(qkv, out, N, T, heads, ch):
         raise LfmHipError(f"UNet attention: no kernel serves T = {T} tokens x {ch} channels per head (limit: channels per head % 16 == 0 and <= 256 for any "
                           f"token count; other widths only while min(T, 64) * (T + 1) * 4 + 4 * T * (ch + 2) <= {160 * 1024} bytes of LDS)")
     check(lib().lfm_attention_small_f16(ptr(qkv), ptr(out), N, T, heads, ch, stream_ptr(qkv.device)), "lfm_attention_small_f16")
+    return out
+
+
+def cross_attention_plan(N, Tq, Tk, heads, ch):
+    """1 when lfm_cross_attention_f16 serves this shape (include/lfm_hip.h: any Tq, Tk >= 1; channels per head % 16 == 0 and <= 256), else LFM_ERR_SHAPE (-1)
+    (no launch, no GPU needed)."""
+    return lib().lfm_cross_attention_plan(int(N), int(Tq), int(Tk), int(heads), int(ch))
+
+
+def cross_attention(Q, K, V, N, Tq, Tk, heads, ch, out=None):
+    """lfm_cross_attention_f16: Q fp16 [N*Tq, heads*ch], K and V fp16 [N*Tk, heads*ch] -- row-strided views are read in place; K and V share a row stride
+    (two column slices of one projection) -- -> out fp16 [N*Tq, heads*ch]; a shape the kernel does not serve is named with its limit."""
+    require_gpu(Q, "cross_attention")
+    if cross_attention_plan(N, Tq, Tk, heads, ch) < 0:
+        raise LfmHipError(f"cross-attention: no kernel serves {Tq} queries x {Tk} keys x {ch} channels per head (limit: channels per head % 16 == 0 and "
+                          "<= 256, any positive token counts)")
+    if out is None:
+        out = torch.empty(N * Tq, heads * ch, dtype=torch.float16, device=Q.device)
+    C_ = heads * ch
+    for name, t, rows in (("Q", Q, N * Tq), ("K", K, N * Tk), ("V", V, N * Tk), ("out", out, N * Tq)):
+        if t.dtype != torch.float16 or tuple(t.shape) != (rows, C_) or t.stride(1) != 1 or t.device != Q.device:
+            raise LfmHipError(f"cross-attention: {name} must be fp16 [{rows}, {C_}] with unit column stride on {Q.device}, got {t.dtype} {tuple(t.shape)} "
+                              f"strides {t.stride()} on {t.device}")
+    if K.stride(0) != V.stride(0):
+        raise LfmHipError(f"cross-attention: K and V must share a row stride (two column slices of one buffer), got {K.stride(0)} and {V.stride(0)}")
+    check(lib().lfm_cross_attention_f16(ptr(Q), Q.stride(0), ptr(K), ptr(V), K.stride(0), ptr(out), out.stride(0), N, Tq, Tk, heads, ch,
+                                        stream_ptr(Q.device)), "lfm_cross_attention_f16")
+    return out
+
+
+def layernorm(x, gamma, beta, eps=1e-5, out=None):
+    """lfm_layernorm_f16: nn.LayerNorm(C) on dense fp16 rows [M, C] (gamma, beta fp32 [C]) -> fp16 [M, C]."""
+    require_gpu(x, "layernorm")
+    M, C = x.shape
+    if C % 8:
+        raise LfmHipError(f"layernorm: {C} channels (limit: channels % 8 == 0)")
+    if out is None:
+        out = torch.empty(M, C, dtype=torch.float16, device=x.device)
+    for name, t in (("x", x), ("out", out)):  # the kernel walks dense rows: a column slice of a wider buffer would be misread or overwritten
+        if t.dtype != torch.float16 or tuple(t.shape) != (M, C) or t.stride() != (C, 1) or t.device != x.device:
+            raise LfmHipError(f"layernorm: {name} must be dense fp16 [{M}, {C}] on {x.device}, got {t.dtype} {tuple(t.shape)} strides {t.stride()} on {t.device}")
+    for name, t in (("gamma", gamma), ("beta", beta)):
+        if t.dtype != torch.float32 or tuple(t.shape) != (C,) or t.stride() != (1,) or t.device != x.device:
+            raise LfmHipError(f"layernorm: {name} must be dense fp32 [{C}] on {x.device}, got {t.dtype} {tuple(t.shape)} on {t.device}")
+    check(lib().lfm_layernorm_f16(ptr(x), ptr(out), ptr(gamma), ptr(beta), M, C, float(eps), stream_ptr(x.device)), "lfm_layernorm_f16")
+    return out
+
+
+def geglu(h, out=None):
+    """lfm_geglu_f16: h fp16 [M, 2I] = [value | gate] (rows may be strided) -> value * gelu(gate) fp16 [M, I], the exact (erf) GELU."""
+    require_gpu(h, "geglu")
+    M, I2 = h.shape
+    if I2 % 16:
+        raise LfmHipError(f"geglu: {I2} columns (limit: half of them % 8 == 0)")
+    if out is None:
+        out = torch.empty(M, I2 // 2, dtype=torch.float16, device=h.device)
+    if h.dtype != torch.float16 or h.stride(1) != 1:
+        raise LfmHipError(f"geglu: h must be fp16 with unit column stride, got {h.dtype} strides {h.stride()}")
+    if out.dtype != torch.float16 or tuple(out.shape) != (M, I2 // 2) or out.stride() != (I2 // 2, 1) or out.device != h.device:
+        raise LfmHipError(f"geglu: out must be dense fp16 [{M}, {I2 // 2}] on {h.device}, got {out.dtype} {tuple(out.shape)} strides {out.stride()} on {out.device}")
+    check(lib().lfm_geglu_f16(ptr(h), h.stride(0), ptr(out), M, I2 // 2, stream_ptr(h.device)), "lfm_geglu_f16")
     return out
 
 

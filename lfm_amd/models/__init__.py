@@ -5,10 +5,10 @@ from .DiT import DiT, DiT_models
 def create_network(config):
     """``create_network(args) -> nn.Module`` with the reference's dispatch (models/__init__.py:6-17).
 
-    DiT-*, ``--use_origin_adm`` (guided-diffusion ``UNetModel``), the EDM ``adm`` (``DhariwalUNet``), ``ddpm++`` and
-    ``ncsn++`` (``SongUNet`` with the DDPM++ settings or the whole NCSN++ preset; the latter reads ``config.num_blocks``, as in the
-    reference) are built on the HIP path.  ``--layout`` (UNetModelAttn) is out of scope and raises instead of silently falling back to
-    anything.
+    DiT-*, ``--use_origin_adm`` (guided-diffusion ``UNetModel``; with ``--layout`` the ``UNetModelAttn`` whose attention blocks are
+    SpatialTransformers with cross-attention over a 512-feature context), the EDM ``adm`` (``DhariwalUNet``), ``ddpm++``
+    and ``ncsn++`` (``SongUNet`` with the DDPM++ settings or the whole NCSN++ preset; the latter reads ``config.num_blocks``, as in the
+    reference) are built on the HIP path: every branch of the reference's dispatch.
     """
     if getattr(config, "use_origin_adm", False):
         return get_flow_model(config)
@@ -25,13 +25,13 @@ def create_network(config):
 
 
 def get_flow_model(config):
-    """Origin-ADM constructor (reference models/__init__.py:20-70).  Flags the ``_ddp`` parser forgets
+    """Origin-ADM constructor (reference models/__init__.py:20-70): ``UNetModel``, or ``UNetModelAttn`` under ``--layout``.  Flags the ``_ddp`` parser forgets
     (``use_scale_shift_norm`` etc., test_flow_latent_ddp.py:210-212) default to the single-file parser's values."""
-    from .unet import UNetModel
+    from .unet import UNetModel, UNetModelAttn
 
-    if getattr(config, "layout", False):
-        raise NotImplementedError("--layout (UNetModelAttn with SpatialTransformer) is out of scope (SURVEY.md §2)")
-    return UNetModel(
+    # --layout: the reference's fixed SpatialTransformer settings (models/__init__.py:42-45)
+    layout = dict(use_spatial_transformer=True, transformer_depth=3, context_dim=512, legacy=True) if getattr(config, "layout", False) else {}
+    return (UNetModelAttn if layout else UNetModel)(
         image_size=config.image_size // 8,
         in_channels=config.num_in_channels,
         model_channels=config.nf,
@@ -51,6 +51,7 @@ def get_flow_model(config):
         use_scale_shift_norm=getattr(config, "use_scale_shift_norm", True),
         resblock_updown=getattr(config, "resblock_updown", False),
         use_new_attention_order=getattr(config, "use_new_attention_order", False),
+        **layout,
     )
 
 

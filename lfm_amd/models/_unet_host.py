@@ -1,4 +1,4 @@
-"""The host layer the three UNet backbones share (``UNetModel``, ``DhariwalUNet``, ``SongUNet``): the packed-operand / scratch state and its invalidation,
+"""The host layer the UNet backbones share (``UNetModel`` and ``UNetModelAttn``, ``DhariwalUNet``, ``SongUNet``): the packed-operand / scratch state and its invalidation,
 the weight-packing helpers, and ONE copy of every host-sequenced op over the NHWC-fp16 building blocks of liblfm_hip.so -- GroupNorm (one or two sources),
 3x3 convolution with its split-K workspace, linear (one or two sources), channel concat, 2x resampling, the FiLM add, attention, the fp32 input and output
 convolutions, the time embedding and the forward prologue.  A backbone keeps its parameter tree, what it packs under which names, its block body, its
