@@ -381,6 +381,22 @@ int lfm_linear_scaled_f16(const void* A, long lda, const void* W, long ldw, void
                           const void* resid, float scale, lfm_stream_t stream);
 int lfm_linear2_scaled_f16(const void* A1, int K1, const void* A2, int K2, const void* W, long ldw, void* C, long ldc, int M, int N,
                            const float* bias, const void* resid, float scale, lfm_stream_t stream);
+/* The linears of EDM's TransformerBlock (models/EDM.py:427-483; DhariwalUNet(use_context=True), model_type "adm_context").  Additions to ABI 4.
+ *
+ * lfm_linear_resid_vec_f16: C fp16 [M,N] = (A W^T + bias (+ resid) (+ vec[m / tokens][n])) * scale -- lfm_linear_scaled_f16 with one more fp32 row per image
+ *   in the sum: vec fp32, rows vec_stride floats apart, `tokens` rows of C per row of vec.  attn1.proj of a TransformerBlock: the cross-attention over a
+ *   ONE-key context is the same vector at every pixel, so both of the block's first two residual sums happen here.  vec = NULL or all zero is bit-identical
+ *   to lfm_linear_scaled_f16.  Alignment and shape as lfm_linear_scaled_f16; also vec 16-byte aligned with vec_stride % 4 == 0 (LFM_ERR_ALIGN), tokens > 0
+ *   and M % tokens == 0 (LFM_ERR_SHAPE), all before any launch.
+ * lfm_linear_silu_f16: C fp16 [M,N] = silu(A W^T + bias) (ff.layer0): x / (1 + exp(-x)) in fp32 on the accumulator, one rounding to fp16.  bias required.
+ * lfm_gather_rows_f32: out[r][0..cols) = table[y[r]][0..cols), r < N; table fp32 [rows, cols] dense, y int64 on the device, out rows out_stride floats
+ *   apart.  cols % 4 == 0, out_stride >= cols (LFM_ERR_SHAPE); table / out 16-byte aligned, out_stride % 4 == 0 (LFM_ERR_ALIGN).  No readback: graph-
+ *   capturable, and a replay follows labels rewritten in place.  Labels are validated by the caller; the kernel clamps to [0, rows) rather than read beyond
+ *   the table. */
+int lfm_linear_resid_vec_f16(const void* A, long lda, const void* W, long ldw, void* C, long ldc, int M, int N, int K, const float* bias,
+                             const void* resid, const float* vec, long vec_stride, int tokens, float scale, lfm_stream_t stream);
+int lfm_linear_silu_f16(const void* A, long lda, const void* W, long ldw, void* C, long ldc, int M, int N, int K, const float* bias, lfm_stream_t stream);
+int lfm_gather_rows_f32(const float* table, int rows, int cols, const void* y_int64, int N, float* out, long out_stride, lfm_stream_t stream);
 /* y = silu?( GroupNorm(groups <= 32)(x; gamma, beta, eps) * (1 + scale[n]) + shift[n] );  film = fp32 [N][scale(C) | shift(C)] rows film_stride apart,
  * or NULL (nn.py:17-19,93-100; scale-shift-norm unet.py:228-233).  scratch: lfm_groupnorm_scratch_bytes(N, C) bytes. */
 size_t lfm_groupnorm_scratch_bytes(int N, int C);

@@ -38,6 +38,9 @@ struct ActGeluTanh {  // two elements at a time on the packed-fp32 VALU (common.
     return (f32x4){a.x, a.y, c.x, c.y};
   }
 };
+struct ActSilu {  // x * sigmoid(x) in fp32 on the accumulator (silu_f, common.h: v_exp_f32 + v_rcp_f32), element by element: EDM FeedForward (models/EDM.py:438)
+  static __device__ __forceinline__ f32x4 apply(f32x4 v) { return (f32x4){silu_f(v.x), silu_f(v.y), silu_f(v.z), silu_f(v.w)}; }
+};
 
 // ------------------------------------------------------------------ bias epilogues
 template <class Act>
@@ -62,6 +65,7 @@ struct EpiBiasF16 : EpiBiasActF16<ActIdentity> {  // C = acc + bias -> fp16; bia
   __device__ __forceinline__ Aux load(int, int n) const { return bias ? *(const f32x4*)(bias + n) : (f32x4){0.f, 0.f, 0.f, 0.f}; }
 };
 struct EpiBiasGeluF16 : EpiBiasActF16<ActGeluTanh> {};  // C = gelu_tanh(acc + bias) -> fp16   (timm Mlp fc1, DiT.py:123-124)
+struct EpiBiasSiluF16 : EpiBiasActF16<ActSilu> {};      // C = silu(acc + bias) -> fp16   (EDM FeedForward.layer0, models/EDM.py:438)
 
 struct EpiBiasF32 {  // C = acc + bias -> fp32   (adaLN modulation table)
   float* C;

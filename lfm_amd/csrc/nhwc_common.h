@@ -98,6 +98,28 @@ struct EpiResidF16 {  // out = (acc + bias (+ residual)) * scale -> fp16
   }
 };
 
+// EpiResidF16 with a per-image fp32 row added to the sum: out = (acc + bias + resid + vec[m / tokens][n]) * scale -> fp16.  The `attn1.proj` linear of EDM's
+// TransformerBlock (models/EDM.py:477-483) under a one-key context: attn2(norm2(x), context) is the same vector u[label] at every pixel, so this one
+// epilogue performs x = attn1(norm1(x)) + x and x = attn2(..) + x (UNet section).  The row joins the bias in load(), in fp32 (bias + 0 is the
+// bias: a null or all-zero `vec` changes no bit of EpiResidF16's result); everything after load() IS EpiResidF16 -- same Aux, same rounding, same
+// 16-byte-store path, so the 256-row hand-over (epilogue_handover.h: per-(row, column) auxiliary loads ahead of a pass's stores) serves it unchanged.
+struct EpiResidVecF16 {
+  EpiResidF16 e;
+  const float* vec;  // may be null; rows vec_stride apart, vec_stride % 4 == 0 and 16-byte aligned (f32x4 loads)
+  long vec_stride;
+  int tokens;        // rows of C per row of vec
+  typedef EpiResidF16::Aux Aux;
+  __device__ __forceinline__ Aux load(int m, int n) const {
+    Aux a = e.load(m, n);
+    if (vec) a.b += *(const f32x4*)(vec + (long)(m / tokens) * vec_stride + n);
+    return a;
+  }
+  __device__ __forceinline__ void store(int m, int n, f32x4 v, const Aux& a) const { e.store(m, n, v, a); }
+  __device__ __forceinline__ bool wide_ok() const { return e.wide_ok(); }
+  __device__ __forceinline__ half8_t round8(f32x4 lo, f32x4 hi, const Aux& al, const Aux& ah) const { return e.round8(lo, hi, al, ah); }
+  __device__ __forceinline__ void store8(int m, int n, f32x4 lo, f32x4 hi, const Aux& al, const Aux& ah) const { e.store8(m, n, lo, hi, al, ah); }
+};
+
 struct EpiNCHWF32 {  // Cout <= 4 output conv (the VAE decoder's `.sample` image, the UNets' out conv): fp32 NCHW, channels beyond nch are padding
   float* out;
   const float* bias;  // [4]

@@ -152,6 +152,50 @@ extern "C" int lfm_linear2_scaled_f16(const void* A1, int K1, const void* A2, in
   return linear2_f16_impl(A1, K1, A2, K2, W, ldw, C, ldc, M, N, bias, resid, scale, stream);
 }
 
+// ------------------------------------------------------------------ the linears of EDM's TransformerBlock (models/EDM.py:427-483, `adm_context`)
+// C = (A W^T + bias (+ resid) (+ vec[m / tokens])) * scale: attn1.proj with both residual sums of the block's first two lines in one epilogue (EpiResidVecF16)
+extern "C" int lfm_linear_resid_vec_f16(const void* A, long lda, const void* W, long ldw, void* C, long ldc, int M, int N, int K, const float* bias,
+                                        const void* resid, const float* vec, long vec_stride, int tokens, float scale, lfm_stream_t stream) {
+  if (!A || !W || !C) return LFM_ERR_ARG;
+  if ((lda % 8) || (ldw % 8) || (ldc % 4) || (((uintptr_t)A | (uintptr_t)W) & 15)) return LFM_ERR_ALIGN;
+  if (vec && ((vec_stride % 4) || ((uintptr_t)vec & 15))) return LFM_ERR_ALIGN;  // four columns of a row of `vec` are one 16-byte load
+  if (tokens <= 0 || M <= 0 || (M % tokens)) return LFM_ERR_SHAPE;
+  return launch_gemm_auto(ASrcRowMajor{(const half_t*)A, lda, M, 0}, (const half_t*)W, ldw, M, N, K,
+                          EpiResidVecF16{EpiResidF16{(half_t*)C, ldc, bias, (const half_t*)resid, scale}, vec, vec_stride, tokens}, (hipStream_t)stream);
+}
+// C = silu(A W^T + bias): ff.layer0; SiLU in fp32 on the accumulator, one rounding to fp16
+extern "C" int lfm_linear_silu_f16(const void* A, long lda, const void* W, long ldw, void* C, long ldc, int M, int N, int K, const float* bias,
+                                   lfm_stream_t stream) {
+  if (!A || !W || !C || !bias) return LFM_ERR_ARG;
+  if ((lda % 8) || (ldw % 8) || (ldc % 4) || (((uintptr_t)A | (uintptr_t)W) & 15)) return LFM_ERR_ALIGN;
+  return launch_gemm_auto(ASrcRowMajor{(const half_t*)A, lda, M, 0}, (const half_t*)W, ldw, M, N, K, EpiBiasSiluF16{{(half_t*)C, ldc, bias}},
+                          (hipStream_t)stream);
+}
+
+// out[r][0 .. cols) = table[y[r]][0 .. cols): the rows of the stacked context table (one per TransformerBlock, column-wise) that this batch's labels name.
+// Plain 16-byte loads and stores, no host readback: safe under capture, and a replay follows labels rewritten in place.  A label outside [0, rows) is
+// the host's to refuse (hip.check_labels, before anything is enqueued); a replay cannot ask, so the kernel clamps instead of reading beyond the table.
+__global__ void gather_rows_f32_kernel(const f32x4* __restrict__ table, int rows, int cols4, const long long* __restrict__ y, f32x4* __restrict__ out,
+                                       long out_stride4, long total) {
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= total) return;
+  const long r = i / cols4;
+  const int c = (int)(i - r * cols4);
+  long long l = y[r];
+  l = l < 0 ? 0 : (l >= rows ? rows - 1 : l);
+  out[r * out_stride4 + c] = table[l * cols4 + c];
+}
+extern "C" int lfm_gather_rows_f32(const float* table, int rows, int cols, const void* y_int64, int N, float* out, long out_stride, lfm_stream_t stream) {
+  if (!table || !y_int64 || !out) return LFM_ERR_ARG;
+  if (rows <= 0 || cols <= 0 || N <= 0 || (cols % 4) || out_stride < cols) return LFM_ERR_SHAPE;
+  if ((out_stride % 4) || (((uintptr_t)table | (uintptr_t)out) & 15) || ((uintptr_t)y_int64 & 7)) return LFM_ERR_ALIGN;
+  const long total = (long)N * (cols / 4);
+  hipLaunchKernelGGL(gather_rows_f32_kernel, dim3(cdiv(total, 256)), dim3(256), 0, (hipStream_t)stream, (const f32x4*)table, rows, cols / 4,
+                     (const long long*)y_int64, (f32x4*)out, out_stride / 4, total);
+  LFM_CHECK_LAUNCH();
+  return LFM_OK;
+}
+
 // ------------------------------------------------------------------ first conv: fp32 NCHW (Cin <= 16) -> fp16 NHWC
 // Weights are transposed into LDS as [k = (c,ky,kx)][Cout] so the 8 output channels of a thread are two float4 reads per tap;
 // a block walks CI_PIX pixels (threads = Cout/8 channel-octets x pixel rows), input taps are L1-served broadcast loads.

@@ -186,6 +186,12 @@ def lib():
     L.lfm_linear_scaled_f16.argtypes = [V, LG, V, LG, V, LG, I, I, I, V, V, F, V]
     L.lfm_linear2_scaled_f16.restype = I
     L.lfm_linear2_scaled_f16.argtypes = [V, I, V, I, V, LG, V, LG, I, I, V, V, F, V]
+    L.lfm_linear_resid_vec_f16.restype = I
+    L.lfm_linear_resid_vec_f16.argtypes = [V, LG, V, LG, V, LG, I, I, I, V, V, V, LG, I, F, V]
+    L.lfm_linear_silu_f16.restype = I
+    L.lfm_linear_silu_f16.argtypes = [V, LG, V, LG, V, LG, I, I, I, V, V]
+    L.lfm_gather_rows_f32.restype = I
+    L.lfm_gather_rows_f32.argtypes = [V, I, I, V, I, V, LG, V]
     L.lfm_song_embed.restype = I
     L.lfm_song_embed.argtypes = [V, I, V, V, V, V, V, V, F, V, I, V, V, V, I, I, I, V]
     L.lfm_fourier_embed.restype = I
@@ -487,6 +493,46 @@ def geglu(h, out=None):
     if out.dtype != torch.float16 or tuple(out.shape) != (M, I2 // 2) or out.stride() != (I2 // 2, 1) or out.device != h.device:
         raise LfmHipError(f"geglu: out must be dense fp16 [{M}, {I2 // 2}] on {h.device}, got {out.dtype} {tuple(out.shape)} strides {out.stride()} on {out.device}")
     check(lib().lfm_geglu_f16(ptr(h), h.stride(0), ptr(out), M, I2 // 2, stream_ptr(h.device)), "lfm_geglu_f16")
+    return out
+
+
+def linear_resid_vec(x, w, bias, resid, vec, tokens, scale=1.0, out=None):
+    """lfm_linear_resid_vec_f16: fp16 (x w^T + bias + resid + vec[m // tokens]) * scale; `vec` fp32 [M / tokens, N], a column slice of a wider buffer is read
+    in place through its row stride (None: lfm_linear_scaled_f16's result)."""
+    require_gpu(x, "linear_resid_vec")
+    M, K = x.shape
+    N = w.shape[0]
+    if out is None:
+        out = torch.empty(M, N, dtype=torch.float16, device=x.device)
+    if vec is not None and (vec.dtype != torch.float32 or tuple(vec.shape) != (M // tokens, N) or vec.stride(1) != 1):
+        raise LfmHipError(f"linear_resid_vec: vec must be fp32 [{M // tokens}, {N}] with unit column stride, got {vec.dtype} {tuple(vec.shape)} strides {vec.stride()}")
+    check(lib().lfm_linear_resid_vec_f16(ptr(x), x.stride(0), ptr(w), w.stride(0), ptr(out), out.stride(0), M, N, K, ptr(bias), ptr(resid), ptr(vec),
+                                         vec.stride(0) if vec is not None else 0, int(tokens), float(scale), stream_ptr(x.device)), "lfm_linear_resid_vec_f16")
+    return out
+
+
+def linear_silu(x, w, bias, out=None):
+    """lfm_linear_silu_f16: fp16 silu(x w^T + bias), SiLU in fp32 on the accumulator."""
+    require_gpu(x, "linear_silu")
+    M, K = x.shape
+    N = w.shape[0]
+    if out is None:
+        out = torch.empty(M, N, dtype=torch.float16, device=x.device)
+    check(lib().lfm_linear_silu_f16(ptr(x), x.stride(0), ptr(w), w.stride(0), ptr(out), out.stride(0), M, N, K, ptr(bias), stream_ptr(x.device)),
+          "lfm_linear_silu_f16")
+    return out
+
+
+def gather_rows(table, y, out=None):
+    """lfm_gather_rows_f32: out[r] = table[y[r]]; table dense fp32 [rows, cols], y int64 on the device, out fp32 [N, cols] (rows may be strided).  The caller
+    validates the labels (check_labels); no readback here, so the call is capturable."""
+    require_gpu(table, "gather_rows")
+    rows, cols = table.shape
+    if table.dtype != torch.float32 or not table.is_contiguous() or y.dtype != torch.int64 or not y.is_contiguous() or y.device != table.device:
+        raise LfmHipError(f"gather_rows: table must be dense fp32 and y contiguous int64 on {table.device}, got {table.dtype} / {y.dtype} on {y.device}")
+    if out is None:
+        out = torch.empty(y.numel(), cols, device=table.device)
+    check(lib().lfm_gather_rows_f32(ptr(table), rows, cols, ptr(y), y.numel(), ptr(out), out.stride(0), stream_ptr(table.device)), "lfm_gather_rows_f32")
     return out
 
 

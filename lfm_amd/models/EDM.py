@@ -1,4 +1,4 @@
-"""EDM-style ADM UNet (``DhariwalUNet``), MI355X-native -- drop-in for the ``model_type == "adm"`` branch of
+"""EDM-style ADM UNet (``DhariwalUNet``), MI355X-native -- drop-in for the ``model_type == "adm"`` and ``"adm_context"`` branches of
 /root/reference/models/EDM.py (``DhariwalUNet`` :716-861, ``UNetBlock`` :188-292, ``get_edm_network`` :864-939): the
 backbone of ``test_args/{bed,ffhq,imnet}_adm.txt`` (USE_ORIGIN_ADM=false), including its own ``forward_with_cfg``.
 
@@ -15,7 +15,26 @@ liblfm_hip.so as the origin-ADM UNet (``lfm_amd/models/unet.py``):
 * the class embedding ``map_label(one_hot(y))`` (no bias) is a column lookup of ``map_label.weight``; the label dropped for the
   unconditional half under CFG (``drop_half_label``, EDM.py:825-826) is an extra all-zero row.
 
-Built: ``use_context=False``, ``augment_dim=0``, channels that are multiples of 64 (the implicit-GEMM contract).
+Built: ``augment_dim=0``, channels that are multiples of 64 (the implicit-GEMM contract); ``use_context`` either way.
+
+``use_context=True`` (``model_type == "adm_context"``, reference :295-483, :754-756, :820-829, :923-938): ``map_label`` is the DiT ``LabelEmbedder``
+(``map_label.embedding_table.weight``, ``label_dim + 1`` rows under label dropout); its output is NOT added to ``emb`` -- it is the ``context`` of every
+block, and ``emb`` is the time embedding alone.  Every block is a ``UNetBlockWithContext``: the conv / FiLM / conv / skip part of ``UNetBlock`` without
+attention of its own, then, where ``attention=True``, a ``TransformerBlock`` -- ``x = attn1(norm1(x)) + x; x = attn2(norm2(x), context) + x;
+x = ff(norm3(x)) + x`` with EDM GroupNorms, ``C // 64`` heads, separate 1x1 ``q`` / ``k`` / ``v`` convolutions and a ``Linear -> SiLU -> Linear`` feed-forward.
+
+* ``attn2`` has exactly ONE key (the context becomes ``[N, emb, 1, 1]``), and a softmax over one finite score is exactly 1: its output is
+  ``proj.W (v.W ctx[n] + v.b) + proj.b`` at every pixel, independent of x, ``norm2``, ``q`` and ``k``.  That vector depends on the label only, so it is
+  tabulated over the label table at pack time (float64 on the host, fp32 on the device, all blocks side by side: ``pack_context_tables``); one
+  ``lfm_gather_rows_f32`` per forward takes the batch's rows.  ``attn2.q``, ``attn2.k`` and ``norm2`` are parameters (a reference ``state_dict`` loads with
+  ``strict=True``) that the arithmetic never reads.  The identity needs finite scores.
+* the three ``attn1`` convolutions are packed as one qkv weight, rows ``[head][q | k | v][ch]``; ``attn1.proj`` runs through ``lfm_linear_resid_vec_f16``,
+  whose epilogue ``(acc + bias + x + u[m / tokens]) * scale`` performs both residual sums; ``ff.layer0`` through ``lfm_linear_silu_f16``; ``ff.layer1``
+  through the existing residual linear (``HipUNetHost._transformer``).
+* labels are required (``y=None`` and ``label_dim=0`` are refused: the reference crashes there) and validated on the host against the table's rows
+  before anything is enqueued.  ``forward_with_cfg`` passes ``y`` through untouched: the reference ignores ``drop_half_label`` under ``use_context``, so the
+  second half is conditioned on whatever ``y[N/2:]`` holds.  The drivers pass class 0 there for every non-DiT model, as the reference's do (not the extra
+  row ``label_dim`` that label dropout trains); a caller who wants that row passes it.
 
 ``SongUNet`` (``model_type == "ddpm++"``, reference :532-706) is built for the DDPM++ settings -- positional embedding, standard encoder and
 decoder, the [1,1] resample filter, ``channel_mult_noise=1`` -- on the same host-sequenced ops (``_EDMUNet`` holds what the two classes share).  What
@@ -43,12 +62,15 @@ the preset is reached through ``create_network`` / ``SongUNet`` from code, and t
 driver files, ``test_flow_latent.py`` and ``test_flow_latent_ddp.py``, are deliberately left byte for byte as they were: a ``--num_blocks`` flag there is a
 change of its own).
 """
+from functools import partial
+
 import numpy as np
 import torch
 import torch.nn as nn
 
 from .. import hip
-from ._unet_host import HipUNetHost, f16, f32, pack_conv1, pack_conv3, pack_gn, stack_rows
+from ._unet_host import HipUNetHost, f16, f32, pack_conv1, pack_conv3, pack_gn, pack_context_tables, pack_qkv_separate, stack_rows
+from .DiT import LabelEmbedder
 
 
 def _weight_init(shape, mode, fan_in, fan_out):  # EDM.py:27-36
@@ -135,6 +157,50 @@ class UNetBlock(nn.Module):  # EDM.py:188-292 (parameter container)
             self.proj = Conv2d(out_channels, out_channels, 1, **init_zero)
 
 
+class CrossAttention(nn.Module):  # EDM.py:370-406 (parameter container); context_channels=None: self-attention
+    def __init__(self, query_channels, context_channels=None, num_heads=None, channels_per_head=64, init=None, init_zero=None, init_attn=None):
+        super().__init__()
+        init, init_zero = init or {}, init_zero or dict(init_weight=0)
+        self.num_heads = num_heads if num_heads is not None else query_channels // channels_per_head
+        context_channels = query_channels if context_channels is None else context_channels
+        qkv_init = init_attn if init_attn is not None else init
+        self.q = Conv2d(query_channels, query_channels, 1, **qkv_init)
+        self.k = Conv2d(context_channels, query_channels, 1, **qkv_init)
+        self.v = Conv2d(context_channels, query_channels, 1, **qkv_init)
+        self.proj = Conv2d(query_channels, query_channels, 1, **init_zero)
+
+
+class FeedForward(nn.Module):  # EDM.py:427-440 (parameter container): Linear(C, 4C) -> SiLU -> Linear(4C, C) on tokens
+    def __init__(self, in_channels, out_channels=None, channel_mult=4, init=None):
+        super().__init__()
+        inner = int(in_channels * channel_mult)
+        self.layer0 = Linear(in_channels, inner, **(init or {}))
+        self.layer1 = Linear(inner, in_channels if out_channels is None else out_channels, **(init or {}))
+
+
+class TransformerBlock(nn.Module):  # EDM.py:443-483 (parameter container; registration order = the reference's state-dict order)
+    def __init__(self, in_channels, context_channels, num_heads=None, channels_per_head=64, eps=1e-5, init=None, init_zero=None, init_attn=None):
+        super().__init__()
+        kw = dict(num_heads=num_heads, channels_per_head=channels_per_head, init=init, init_zero=init_zero, init_attn=init_attn)
+        self.attn1 = CrossAttention(in_channels, None, **kw)
+        self.attn2 = CrossAttention(in_channels, context_channels, **kw)  # one key: only v and proj enter the arithmetic (module docstring)
+        self.ff = FeedForward(in_channels, init=init)
+        self.norm1 = GroupNorm(in_channels, eps=eps)
+        self.norm2 = GroupNorm(in_channels, eps=eps)  # loaded, never read: attn2's output does not depend on its query
+        self.norm3 = GroupNorm(in_channels, eps=eps)
+        self.in_channels, self.eps = in_channels, eps
+
+
+class UNetBlockWithContext(UNetBlock):  # EDM.py:295-367 (parameter container): UNetBlock without its own attention, then a TransformerBlock where attention=True
+    def __init__(self, in_channels, out_channels, emb_channels, context_channels, up=False, down=False, attention=False, num_heads=None,
+                 channels_per_head=64, **kw):
+        super().__init__(in_channels, out_channels, emb_channels, up=up, down=down, attention=False, **kw)
+        self.use_transformer = bool(attention)
+        if self.use_transformer:
+            self.transformer = TransformerBlock(out_channels, context_channels, num_heads=num_heads, channels_per_head=channels_per_head, eps=self.eps,
+                                                init=kw.get("init"), init_zero=kw.get("init_zero"), init_attn=kw.get("init_attn"))
+
+
 class _EDMUNet(HipUNetHost):
     """What DhariwalUNet and SongUNet share on top of the UNets' host layer (``_unet_host.py``): what is packed, the host-sequenced UNetBlock and the encoder /
     decoder walk.  A subclass builds the parameter tree and provides ``_out_modules`` (the output GroupNorm and convolution), ``_pack_mapping`` and ``_embed``
@@ -145,7 +211,7 @@ class _EDMUNet(HipUNetHost):
     # ---- packing ------------------------------------------------------------------------------------------------------
     def _pack_blocks(self, P, dev):
         out_norm, out_conv = self._out_modules()
-        aff = {}
+        aff, ctx = {}, {}
         for group in (self.enc, self.dec):
             pre = "enc." if group is self.enc else "dec."
             for name, b in group.items():
@@ -168,13 +234,20 @@ class _EDMUNet(HipUNetHost):
                     perm = torch.arange(3 * C).reshape(b.num_heads, ch, 3).permute(0, 2, 1).reshape(-1)
                     d.update(gn_attn=pack_gn(b.norm2, dev), qkv=(f16(b.qkv.weight.reshape(3 * C, C)[perm], dev), f32(b.qkv.bias[perm], dev)),
                              proj=pack_conv1(b.proj, dev))
+                if getattr(b, "use_transformer", False):  # adm_context: the device half of the TransformerBlock; its attn2 goes into the context table below
+                    tb = b.transformer
+                    d["tf"] = dict(gn1=pack_gn(tb.norm1, dev), qkv=pack_qkv_separate(tb.attn1, dev), proj=pack_conv1(tb.attn1.proj, dev), gn3=pack_gn(tb.norm3, dev),
+                                   ff0=(f16(tb.ff.layer0.weight, dev), f32(tb.ff.layer0.bias, dev)), ff1=(f16(tb.ff.layer1.weight, dev), f32(tb.ff.layer1.bias, dev)))
+                    ctx[pre + name] = tb.attn2
                 P[pre + name] = d
                 aff[pre + name] = (f16(b.affine.weight, dev), f32(b.affine.bias, dev))
         P["aff_all"] = stack_rows(aff)  # every block's `affine` projection of the embedding (EDM.py:263-265)
+        # every TransformerBlock's attn2 as a table over the label rows, stacked column-wise (None: no context model)
+        P["ctx_all"] = pack_context_tables(ctx, self.map_label.embedding_table.weight, dev) if ctx else None
         self._pack_mapping(P, dev)
 
     # ---- blocks -----------------------------------------------------------------------------------------------------------
-    def _block(self, name, b, x, N, H, W, film_all):
+    def _block(self, name, b, x, N, H, W, film_all, ctx_all=None):
         """UNetBlock.forward (EDM.py:258-292).  Returns (out, H, W).  `x` may be the pair (h, skip) of a decoder block: its channel concat is then read in place
         by the block's two consumers -- the first GroupNorm and the 1x1 skip convolution -- as in the origin-ADM UNet (round 6; the concat kernel was 2 % of an
         evaluation at the ffhq_adm size)."""
@@ -219,6 +292,11 @@ class _EDMUNet(HipUNetHost):
         if b.num_heads:
             del t  # dead from here on: its block of a captured graph's memory pool goes to the attention's tensors
             x = self._attention(x, p, N, H * W, b.num_heads, Cout, b.norm2.num_groups, eps, ss)
+        elif getattr(b, "use_transformer", False):  # UNetBlockWithContext (EDM.py:364-366): x = transformer(x, context) * skip_scale
+            del t
+            tb = b.transformer
+            co, cw = self._packed["ctx_all"][1][name]
+            x = self._transformer(x, p["tf"], ctx_all[:, co:co + cw], N, H * W, tb.attn1.num_heads, Cout, tb.norm1.num_groups, tb.eps, ss)
         return x, H, W
 
     # ---- forward ----------------------------------------------------------------------------------------------------------
@@ -229,6 +307,8 @@ class _EDMUNet(HipUNetHost):
         N, Cin, H, W = x.shape
         emb_f16 = self._embed(t, N, y, drop_half_label, x.device)  # fp16 [N, E]: what every block's `affine` reads
         film_all = hip.gemm_f16(emb_f16, P["aff_all"][0], P["aff_all"][1], epilogue=2)  # fp32 [N, all blocks' affine columns]
+        # adm_context: the N label rows of the stacked context table, fp32 [N, all TransformerBlocks' channels]; each block reads its column slice
+        ctx_all = hip.gather_rows(P["ctx_all"][0], y) if P["ctx_all"] is not None else None
         skips, h, aux = [], None, x  # aux: the residual encoder's second stream (NCSN++), the network input until the first aux_residual
         for name, b in self.enc.items():
             if name.endswith("_aux_residual"):  # x = skips[-1] = aux = (x + aux_residual(aux)) / sqrt(2) (EDM.py:685-686): aux is one level up, 2H x 2W
@@ -238,7 +318,7 @@ class _EDMUNet(HipUNetHost):
             if isinstance(b, Conv2d):
                 h = self._conv_in(x, P["enc." + name], N, H, W, Cin)
             else:
-                h, H, W = self._block("enc." + name, b, h, N, H, W, film_all)
+                h, H, W = self._block("enc." + name, b, h, N, H, W, film_all, ctx_all)
             skips.append(h)
         for name, b in self.dec.items():
             if not isinstance(b, UNetBlock):  # SongUNet's aux_norm / aux_conv: the output layers below
@@ -246,7 +326,7 @@ class _EDMUNet(HipUNetHost):
             if h.shape[1] != b.in_channels:
                 s = skips.pop()
                 h = (h, s)  # torch.cat([x, skips.pop()], dim=1) (EDM.py:840-842): consumed in place by the block where its shape allows it
-            h, H, W = self._block("dec." + name, b, h, N, H, W, film_all)
+            h, H, W = self._block("dec." + name, b, h, N, H, W, film_all, ctx_all)
         out_norm = self._out_modules()[0]
         return self._out(h, N, H, W, out_norm.num_groups, out_norm.eps)
 
@@ -258,9 +338,11 @@ class DhariwalUNet(_EDMUNet):
                  channel_mult_emb=4, num_blocks=3, attn_resolutions=(32, 16, 8), dropout=0.10, label_dropout=0, use_context=False):
         super().__init__()
         self._init_host_state()
-        if use_context or augment_dim:
-            raise NotImplementedError("use_context / augment_dim are not used by the sampling path and are not built")
-        self.label_dim, self.label_dropout = label_dim, label_dropout
+        if augment_dim:
+            raise NotImplementedError("augment_dim is not used by the sampling path and is not built")
+        if use_context and not label_dim:  # the reference builds it and crashes in forward (map_label is None there, and it is called)
+            raise ValueError("DhariwalUNet(use_context=True) needs label_dim > 0: the context IS the label embedding")
+        self.label_dim, self.label_dropout, self.use_context = label_dim, label_dropout, bool(use_context)
         self.img_resolution, self.in_channels, self.out_channels, self.model_channels = img_resolution, in_channels, out_channels, model_channels
         emb_channels = model_channels * channel_mult_emb
         self.emb_channels = emb_channels
@@ -269,7 +351,12 @@ class DhariwalUNet(_EDMUNet):
         bk = dict(emb_channels=emb_channels, channels_per_head=64, dropout=dropout, init=init, init_zero=init_zero)
         self.map_layer0 = Linear(model_channels, emb_channels, **init)
         self.map_layer1 = Linear(emb_channels, emb_channels, **init)
-        self.map_label = Linear(label_dim, emb_channels, bias=False, init_mode="kaiming_normal", init_weight=np.sqrt(label_dim)) if label_dim else None
+        if use_context:  # EDM.py:754-756: the DiT label embedder (label_dim + 1 rows under label_dropout), its output the CONTEXT of every block, not a term of emb
+            self.map_label = LabelEmbedder(label_dim, emb_channels, label_dropout)
+            UNetBlock_ = partial(UNetBlockWithContext, context_channels=emb_channels)
+        else:
+            self.map_label = Linear(label_dim, emb_channels, bias=False, init_mode="kaiming_normal", init_weight=np.sqrt(label_dim)) if label_dim else None
+            UNetBlock_ = UNetBlock
         self.enc = nn.ModuleDict()
         cout = in_channels
         for level, mult in enumerate(channel_mult):
@@ -278,23 +365,23 @@ class DhariwalUNet(_EDMUNet):
                 cin, cout = cout, model_channels * mult
                 self.enc[f"{res}x{res}_conv"] = Conv2d(cin, cout, 3, **init)
             else:
-                self.enc[f"{res}x{res}_down"] = UNetBlock(cout, cout, down=True, **bk)
+                self.enc[f"{res}x{res}_down"] = UNetBlock_(cout, cout, down=True, **bk)
             for idx in range(num_blocks):
                 cin, cout = cout, model_channels * mult
-                self.enc[f"{res}x{res}_block{idx}"] = UNetBlock(cin, cout, attention=(res in attn_resolutions), **bk)
+                self.enc[f"{res}x{res}_block{idx}"] = UNetBlock_(cin, cout, attention=(res in attn_resolutions), **bk)
         skips = [b.out_channels for b in self.enc.values()]
         self.dec = nn.ModuleDict()
         for level, mult in reversed(list(enumerate(channel_mult))):
             res = img_resolution >> level
             if level == len(channel_mult) - 1:
-                self.dec[f"{res}x{res}_in0"] = UNetBlock(cout, cout, attention=True, **bk)
-                self.dec[f"{res}x{res}_in1"] = UNetBlock(cout, cout, **bk)
+                self.dec[f"{res}x{res}_in0"] = UNetBlock_(cout, cout, attention=True, **bk)
+                self.dec[f"{res}x{res}_in1"] = UNetBlock_(cout, cout, **bk)
             else:
-                self.dec[f"{res}x{res}_up"] = UNetBlock(cout, cout, up=True, **bk)
+                self.dec[f"{res}x{res}_up"] = UNetBlock_(cout, cout, up=True, **bk)
             for idx in range(num_blocks + 1):
                 cin = cout + skips.pop()
                 cout = model_channels * mult
-                self.dec[f"{res}x{res}_block{idx}"] = UNetBlock(cin, cout, attention=(res in attn_resolutions), **bk)
+                self.dec[f"{res}x{res}_block{idx}"] = UNetBlock_(cin, cout, attention=(res in attn_resolutions), **bk)
         self.out_norm = GroupNorm(cout)
         self.out_conv = Conv2d(cout, out_channels, 3, **init_zero)
 
@@ -303,13 +390,15 @@ class DhariwalUNet(_EDMUNet):
 
     def _pack_mapping(self, P, dev):
         P["time"] = tuple(f32(t, dev) for t in (self.map_layer0.weight, self.map_layer0.bias, self.map_layer1.weight, self.map_layer1.bias))
-        if self.map_label is not None:  # [label_dim + 1, E]: column lookup + one all-zero row for the dropped label
+        if self.use_context:  # the label embedding is the context (P["ctx_all"], packed with the blocks): emb is the time embedding alone
+            P["label"] = None
+        elif self.map_label is not None:  # [label_dim + 1, E]: column lookup + one all-zero row for the dropped label
             P["label"] = torch.cat([f32(self.map_label.weight, dev).t(), torch.zeros(1, self.emb_channels, device=dev)], 0).contiguous()
         else:
             P["label"] = None
 
     def _embed(self, t, N, y, drop_half_label, dev):
-        yy = None
+        yy = None  # (context mode: P["label"] is None -- the labels went into the context rows, and drop_half_label is ignored as in the reference, EDM.py:821-829)
         if self._packed["label"] is not None and y is not None:
             yy = y.to(dev, torch.long).clone()
             if drop_half_label:
@@ -318,7 +407,20 @@ class DhariwalUNet(_EDMUNet):
 
     def forward(self, noise_labels, x, y=None, augment_labels=None, drop_half_label=False, **kwargs):
         """v = model(t, x, y) (EDM.py:808-845)."""
-        return self._forward(noise_labels, x, y, drop_half_label)
+        return self._forward(noise_labels, x, self._context_labels(y, x), drop_half_label)
+
+    def _context_labels(self, y, x):
+        """Context mode: the labels as the gather kernel reads them (int64 on x's device), validated against the embedding table's rows on the host before
+        anything is enqueued; y=None is refused (the reference calls map_label(None) and crashes).  Otherwise y as it came."""
+        if not self.use_context:
+            return y
+        if y is None:
+            raise ValueError("DhariwalUNet(use_context=True).forward needs labels y: the context of every TransformerBlock is their embedding")
+        yy = y.to(x.device, torch.long).contiguous()
+        if yy.numel() != x.shape[0]:
+            raise ValueError(f"DhariwalUNet(use_context=True): {yy.numel()} labels for a batch of {x.shape[0]}")
+        hip.check_labels(yy, self.map_label.embedding_table.num_embeddings, self._what)
+        return yy
 
     def _cfg_coef(self, cfg_scale, dev):
         """[s, 1 - s] on the device, made once per (scale, device): a stream capture refuses the host-to-device copy of a fresh one (the captured solver
@@ -330,7 +432,10 @@ class DhariwalUNet(_EDMUNet):
         return table[key]
 
     def forward_with_cfg(self, noise_labels, x, y=None, augment_labels=None, cfg_scale=1.0, **kwargs):
-        """EDM.py:847-861: x[:N/2] evaluated with labels y (first half) and with the label dropped (second half)."""
+        """EDM.py:847-861: x[:N/2] evaluated with labels y (first half) and with the label dropped (second half).  In context mode the reference's
+        ``drop_half_label`` is ignored (:821-829): the second half is conditioned on whatever y[N/2:] holds -- the caller's null label (the drivers pass class 0
+        for every non-DiT model, as the reference's do; the extra row ``label_dim`` is what label dropout trained) -- and y passes through untouched."""
+        y = self._context_labels(y, x)
         n2 = len(x) // 2
         xin = x.contiguous().float().clone()
         xin[n2:].copy_(xin[:n2])  # combined = cat([half, half])
@@ -468,7 +573,8 @@ class SongUNet(_EDMUNet):
 
 
 def get_edm_network(config):
-    """Reference models/EDM.py:864-939: ``adm`` -> DhariwalUNet, ``ddpm++`` and ``ncsn++`` -> SongUNet, each with the reference's argument list."""
+    """Reference models/EDM.py:864-939: ``adm`` and ``adm_context`` -> DhariwalUNet (the latter with ``use_context=True``), ``ddpm++`` and ``ncsn++`` ->
+    SongUNet, each with the reference's argument list."""
     common = dict(img_resolution=config.image_size // config.f, in_channels=config.num_in_channels, out_channels=config.num_out_channels,
                   label_dim=config.label_dim, augment_dim=0, model_channels=config.nf, channel_mult=config.ch_mult, channel_mult_emb=4,
                   attn_resolutions=config.attn_resolutions, dropout=config.dropout, label_dropout=config.label_dropout)
@@ -484,6 +590,6 @@ def get_edm_network(config):
         if getattr(config, "random_weights", False):
             m.redraw_small_()
         return m
-    if config.model_type != "adm":
-        raise NotImplementedError(f"model_type {config.model_type!r}: adm_context is out of scope (SURVEY.md §2)")
-    return DhariwalUNet(num_blocks=config.num_res_blocks, **common)
+    if config.model_type not in ("adm", "adm_context"):
+        raise NotImplementedError(f"model_type {config.model_type!r} is not one of the reference's: adm, adm_context, ddpm++, ncsn++")
+    return DhariwalUNet(num_blocks=config.num_res_blocks, use_context=config.model_type == "adm_context", **common)

@@ -6,7 +6,7 @@ def create_network(config):
     """``create_network(args) -> nn.Module`` with the reference's dispatch (models/__init__.py:6-17).
 
     DiT-*, ``--use_origin_adm`` (guided-diffusion ``UNetModel``; with ``--layout`` the ``UNetModelAttn`` whose attention blocks are
-    SpatialTransformers with cross-attention over a 512-feature context), the EDM ``adm`` (``DhariwalUNet``), ``ddpm++``
+    SpatialTransformers with cross-attention over a 512-feature context), the EDM ``adm`` and ``adm_context`` (``DhariwalUNet``; the latter with ``use_context=True``), ``ddpm++``
     and ``ncsn++`` (``SongUNet`` with the DDPM++ settings or the whole NCSN++ preset; the latter reads ``config.num_blocks``, as in the
     reference) are built on the HIP path: every branch of the reference's dispatch.
     """

@@ -84,6 +84,45 @@ def stack_rows(wbs):
     return torch.cat([w for w, _ in wbs.values()], 0).contiguous(), torch.cat([b for _, b in wbs.values()], 0).contiguous(), offs
 
 
+def qkv_rows_separate(q, k, v, heads):
+    """Three [C, ...] tensors whose rows are [head][ch] (EDM CrossAttention's q / k / v: ``reshape(N * heads, C // heads, -1)``) -> one [3C, ...] tensor with
+    rows [head][q | k | v][ch], the layout lfm_attention_small_f16 reads."""
+    C = q.shape[0]
+    return torch.stack([q, k, v], 0).reshape(3, heads, C // heads, *q.shape[1:]).transpose(0, 1).reshape(3 * C, *q.shape[1:])
+
+
+def pack_qkv_separate(attn, dev):
+    """The three 1x1 convolutions of a self-attention CrossAttention (EDM.py:388-405) as ONE qkv linear."""
+    C = attn.q.weight.shape[0]
+    w = qkv_rows_separate(*(m.weight.detach().reshape(C, -1) for m in (attn.q, attn.k, attn.v)), attn.num_heads)
+    b = qkv_rows_separate(*(m.bias.detach() for m in (attn.q, attn.k, attn.v)), attn.num_heads)
+    return f16(w, dev), f32(b, dev)
+
+
+def context_table(attn2, table):
+    """A cross-attention over ONE key (EDM TransformerBlock.attn2 on a [N, E, 1, 1] context): the softmax over a single finite score is exactly 1, so its
+    output is proj(v(context)) at every query, whatever the query, the q and k weights and the norm in front are.  Over all rows E[label] of the label table:
+    U[label] = proj.W (v.W E[label] + v.b) + proj.b, in float64 on the host -> fp32 [rows, C]."""
+    d = torch.float64
+    C = attn2.v.weight.shape[0]
+    E = table.detach().cpu().to(d)
+    vw, pw = attn2.v.weight.detach().cpu().to(d).reshape(C, -1), attn2.proj.weight.detach().cpu().to(d).reshape(C, C)
+    val = E @ vw.t() + attn2.v.bias.detach().cpu().to(d)
+    return (val @ pw.t() + attn2.proj.bias.detach().cpu().to(d)).float()
+
+
+def pack_context_tables(attn2s, table, dev):
+    """{name: attn2} -> (fp32 [rows, sum of C] on the device: every block's context_table side by side, {name: (column offset, C)}).  One gather per forward
+    takes the batch's label rows; each block then reads its column slice -- as `stack_rows` does for the blocks' `affine`."""
+    offs, off, cols = {}, 0, []
+    for name, a in attn2s.items():
+        u = context_table(a, table)
+        offs[name] = (off, u.shape[1])
+        off += u.shape[1]
+        cols.append(u)
+    return torch.cat(cols, 1).contiguous().to(dev), offs
+
+
 class HipUNetHost(PackedModule):
     """A subclass builds the parameter tree, calls ``_init_host_state()``, and provides ``_what`` (its name in error messages), ``_out_modules()`` (the output
     GroupNorm and convolution) and ``_pack_blocks(P, dev)`` (everything else it packs)."""
@@ -200,6 +239,21 @@ class HipUNetHost(PackedModule):
         a = torch.empty(N * T, C, dtype=torch.float16, device=x.device)
         hip.unet_attention(qkv, a, N, T, heads, C // heads)
         return self._linear(a, p["proj"], resid=x, scale=scale)
+
+    def _transformer(self, x, p, u, N, T, heads, C, groups=32, eps=1e-5, scale=1.0):
+        """EDM TransformerBlock (EDM.py:477-483) on the [N*T, C] token layout the NHWC activations already have, times `scale`:
+            x = attn1(norm1(x)) + x;  x = attn2(norm2(x), context) + x;  x = ff(norm3(x)) + x.
+        `u` fp32 [N, C] (a column slice of the gathered context rows) IS attn2's output at every token of image n (`context_table`), so the attn1.proj epilogue
+        (acc + bias + x + u[m // T]) performs the first two lines; ff.layer0 carries the SiLU in its epilogue, ff.layer1 the last residual sum."""
+        t = self._gn(x, N, T, C, p["gn1"], None, False, groups, eps)
+        qkv = self._linear(t, p["qkv"])
+        a = torch.empty(N * T, C, dtype=torch.float16, device=x.device)
+        hip.unet_attention(qkv, a, N, T, heads, C // heads)
+        x = hip.linear_resid_vec(a, p["proj"][0], p["proj"][1], x, u, T)
+        del t, qkv, a
+        t = self._gn(x, N, T, C, p["gn3"], None, False, groups, eps)
+        h = hip.linear_silu(t, p["ff0"][0], p["ff0"][1])
+        return self._linear(h, p["ff1"], resid=x, scale=scale)
 
     def _conv_in(self, x, wb, N, H, W, Cin):
         """The first 3x3 convolution: fp32 NCHW in, fp16 NHWC out."""
