@@ -329,6 +329,33 @@ size_t lfm_vae_mid_attention_workspace_bytes(int n, int T);
 int lfm_vae_mid_attention_f16(const void* x, void* out, const float* gn_gamma, const float* gn_beta, const void* q_w, const float* q_b,
                               const void* k_w, const float* k_b, const void* v_w, const float* v_b, const void* o_w, const float* o_b,
                               void* workspace, size_t workspace_bytes, int n, int T, lfm_stream_t stream);
+/* Test entry points for four more stages of the first-stage VAE, each running the decoder's / encoder's own host code on the caller's buffers.  Additions
+ * to ABI 4.  All refuse before any launch: a null pointer (LFM_ERR_ARG), a shape outside the stated limits (LFM_ERR_SHAPE), a tensor that is not 16-byte
+ * or a workspace that is not 256-byte aligned (LFM_ERR_ALIGN), a workspace below *_workspace_bytes (LFM_ERR_WORKSPACE; 0 for a refused shape).
+ *
+ * lfm_vae_conv_in_f16: diffusers AutoencoderKL.post_quant_conv (1x1, 4 -> 4) followed by Decoder.conv_in (3x3, pad 1, 4 -> 512) in one kernel:
+ *   z fp32 NCHW [n,4,R,R] -> out fp16 NHWC [n,R,R,512]; pq_w fp32 [4][4], pq_b [4], cin_w fp32 [512][4][3][3], cin_b [512].  conv_in pads
+ *   post_quant_conv(z) with zeros, so the 1x1 (its bias included) is skipped outside the image.  Any R >= 1 (R % 8 is lfm_vae_decode's rule). */
+int lfm_vae_conv_in_f16(const float* pq_w, const float* pq_b, const float* cin_w, const float* cin_b, const float* z, void* out, int n, int R,
+                        lfm_stream_t stream);
+/* lfm_vae_downsample_f16: diffusers Downsample2D(use_conv=True, padding=0) of the encoder: F.pad(x, (0, 1, 0, 1)) then a 3x3 convolution at stride 2, i.e.
+ *   out[oy][ox] reads x[2 oy + ky][2 ox + kx], zero beyond the bottom row and the right column.  x fp16 NHWC [n,2Ho,2Wo,C], w fp16 [C][9][C], bias fp32
+ *   [C], out fp16 [n,Ho,Wo,C]; C % 64 == 0.  Runs on the GEMM kernel the calling thread's lfm_gemm_select asks for. */
+size_t lfm_vae_downsample_workspace_bytes(int n, int Ho, int Wo, int C);
+int lfm_vae_downsample_f16(const void* x, const void* w, const float* bias, void* out, void* workspace, size_t workspace_bytes, int n, int Ho, int Wo,
+                           int C, lfm_stream_t stream);
+/* lfm_vae_resnets_f16: n_res (1 .. 3) diffusers ResnetBlock2D (temb None: GroupNorm+SiLU -> conv1 -> GroupNorm+SiLU -> conv2 + (conv_shortcut of) x) in
+ *   sequence on the drivers' four rotating buffers: x fp16 NHWC [n,H,W,r[0].cin] -> out [n,H,W,r[n_res-1].cout]; widths in {128, 256, 512}, r[i].cout ==
+ *   r[i+1].cin, sc_w required where cin != cout.  chain_stats 1 (decoder): conv2 leaves the GroupNorm statistics of its output for the next resnet where its
+ *   kernel can; 0 (encoder): every GroupNorm runs its own pass.  *last_slabs (may be NULL) = the statistics slabs per image the last conv2 left (0: none). */
+size_t lfm_vae_resnets_workspace_bytes(int n, int H, int W);
+int lfm_vae_resnets_f16(const lfm_vae_resnet* r, int n_res, const void* x, void* out, void* workspace, size_t workspace_bytes, int n, int H, int W,
+                        int chain_stats, int* last_slabs, lfm_stream_t stream);
+/* lfm_vae_conv_moments_f32: diffusers Encoder.conv_out (3x3, pad 1, 512 -> 8) with AutoencoderKL.quant_conv (1x1, 8 -> 8) folded into its weights by the
+ *   caller: in fp16 NHWC [n,H,W,512], w8 fp16 [8][9][512], b8 fp32 [8] -> moments fp32 NCHW [n,8,H,W] (no fp16 rounding of the result). */
+size_t lfm_vae_conv_moments_workspace_bytes(int n, int H, int W);
+int lfm_vae_conv_moments_f32(const void* in, const void* w8, const float* b8, float* moments, void* workspace, size_t workspace_bytes, int n, int H,
+                             int W, lfm_stream_t stream);
 
 /* u8 NHWC = trunc(clamp((x+1)/2, 0, 1) * 255) of fp32 NCHW images (test_flow_latent_ddp.py:131-135). */
 int lfm_images_to_uint8(const float* x, uint8_t* out, int N, int H, int W, lfm_stream_t stream);

@@ -23,9 +23,7 @@ from . import hip
 BLOCK_OUT = (128, 256, 512, 512)
 
 
-class _Res(C.Structure):
-    _fields_ = [(n, C.c_void_p) for n in ("n1_g", "n1_b", "c1_w", "c1_b", "n2_g", "n2_b", "c2_w", "c2_b", "sc_w", "sc_b")] + [
-        ("cin", C.c_int), ("cout", C.c_int)]
+_Res = hip.VaeResnet
 
 
 class _VaeWeights(C.Structure):

@@ -518,20 +518,30 @@ extern "C" int lfm_vae_mid_attention_f16(const void* x, void* out, const float* 
 }
 
 // post_quant_conv + conv_in: z [n,4,R,R] fp32 NCHW -> out fp16 NHWC [n,R,R,512]
-static int vae_conv_in(const lfm_vae_weights* w, const float* z, half_t* out, int n, int R, hipStream_t st) {
+static int vae_conv_in(const float* pq_w, const float* pq_b, const float* cin_w, const float* cin_b, const float* z, half_t* out, int n, int R,
+                       hipStream_t st) {
   if (!lfm_kernel_lds<&vae_conv_in_kernel>(36 * 512 * 4)) return LFM_ERR_LAUNCH;
   // batch 1 (--measure_time: run_sampling(1, ..), reference test_flow_latent.py:223-246): 1024 pixels are FOUR blocks of 256 pixels -- 183 us for 38 MFLOP
   // (profiles/r06_latency_mode.txt); 16 pixels per block put them on 64 CUs
   const long pixels = (long)n * R * R;
   const int ppb = pixels >= 256L * VCI_PIX ? VCI_PIX : (pixels >= 64L * VCI_PIX ? 64 : 16);
-  hipLaunchKernelGGL(vae_conv_in_kernel, dim3(cdiv(pixels, ppb)), dim3(256), 36 * 512 * 4, st, z, w->pq_w, w->pq_b, w->cin_w, w->cin_b, out, n, R, 512, ppb);
+  hipLaunchKernelGGL(vae_conv_in_kernel, dim3(cdiv(pixels, ppb)), dim3(256), 36 * 512 * 4, st, z, pq_w, pq_b, cin_w, cin_b, out, n, R, 512, ppb);
   LFM_CHECK_LAUNCH();
   return LFM_OK;
 }
 
+// ---- test entry point: the decoder's first kernel on the caller's tensors
+extern "C" int lfm_vae_conv_in_f16(const float* pq_w, const float* pq_b, const float* cin_w, const float* cin_b, const float* z, void* out, int n, int R,
+                                   lfm_stream_t stream) {
+  if (!pq_w || !pq_b || !cin_w || !cin_b || !z || !out) return LFM_ERR_ARG;
+  if (n <= 0 || R <= 0 || (long)n * R * R * 512 >= (1L << 31)) return LFM_ERR_SHAPE;  // any R: R % 8 is lfm_vae_decode's rule
+  if (((uintptr_t)pq_w | (uintptr_t)pq_b | (uintptr_t)cin_w | (uintptr_t)cin_b | (uintptr_t)z | (uintptr_t)out) & 15) return LFM_ERR_ALIGN;
+  return vae_conv_in(pq_w, pq_b, cin_w, cin_b, z, (half_t*)out, n, R, (hipStream_t)stream);
+}
+
 // one chunk of images: z [n,4,R,R] -> out [n,3,8R,8R]
 static int vae_decode_chunk(VaeCtx& c, const lfm_vae_weights* w, const float* z, float* out, int R) {
-  RC(vae_conv_in(w, z, c.x, c.n, R, c.st));
+  RC(vae_conv_in(w->pq_w, w->pq_b, w->cin_w, w->cin_b, z, c.x, c.n, R, c.st));
   int H = R;
   RC(c.resnet(&w->mid[0], H, H));
   RC(c.mid_attention(w, R * R));
@@ -589,6 +599,124 @@ int VaeCtx::conv_down(const void* w, const float* b, int Ho, int Wo, int C) {
   return LFM_OK;
 }
 
+// encoder conv_out with quant_conv folded in: in fp16 NHWC [n,H,W,512] -> moments fp32 NCHW [n,8,H,W]; w8 fp16 [8][9][512], b8 fp32 [8].  Eight live columns
+// of one 128-column tile; a 128-row tile may span several images (EpiMomentsNCHW scatters per row).
+static int vae_conv_moments(const half_t* in, const half_t* zeros, const void* w8, const float* b8, float* moments, int n, int H, int W, hipStream_t st) {
+  const int M = n * H * W;
+  return launch_gemm_tn(ASrcConv<0>{in, zeros, H, W, 512, M}, (const half_t*)w8, 9L * 512, M, 8, 9 * 512, EpiMomentsNCHW{moments, b8, H * W, 8}, st);
+}
+
+// ---- test entry points: the encoder's downsampling convolution and its last convolution, and a run of resnets of either network, on the drivers' own
+// host code.  Workspace of the two convolutions: 256 B of zeros (the padding rows of the gather).
+extern "C" size_t lfm_vae_downsample_workspace_bytes(int n, int Ho, int Wo, int C) {
+  if (n <= 0 || Ho <= 0 || Wo <= 0 || C <= 0 || (C % 64) || 4L * n * Ho * Wo * C >= (1L << 31)) return 0;
+  return 256;
+}
+
+extern "C" int lfm_vae_downsample_f16(const void* x, const void* w, const float* bias, void* out, void* workspace, size_t workspace_bytes, int n, int Ho,
+                                      int Wo, int C, lfm_stream_t stream) {
+  if (!x || !w || !bias || !out || !workspace) return LFM_ERR_ARG;
+  const size_t need = lfm_vae_downsample_workspace_bytes(n, Ho, Wo, C);
+  if (!need) return LFM_ERR_SHAPE;
+  if (((uintptr_t)x | (uintptr_t)w | (uintptr_t)bias | (uintptr_t)out) & 15) return LFM_ERR_ALIGN;
+  if ((uintptr_t)workspace & 255) return LFM_ERR_ALIGN;
+  if (workspace_bytes < need) return LFM_ERR_WORKSPACE;
+  VaeCtx c{};
+  c.ws.zeros = (half_t*)workspace;
+  c.n = n;
+  c.st = (hipStream_t)stream;
+  c.x = (half_t*)x;  // conv_down reads x and writes t1, then rotates: the result is in `out` and nothing is written to the caller's x
+  c.t1 = (half_t*)out;
+  if (lfm_zero_async(c.ws.zeros, 256, c.st)) return LFM_ERR_LAUNCH;
+  return c.conv_down(w, bias, Ho, Wo, C);
+}
+
+extern "C" size_t lfm_vae_conv_moments_workspace_bytes(int n, int H, int W) {
+  if (n <= 0 || H <= 0 || W <= 0 || (long)n * H * W * 512 >= (1L << 31)) return 0;
+  return 256;
+}
+
+extern "C" int lfm_vae_conv_moments_f32(const void* in, const void* w8, const float* b8, float* moments, void* workspace, size_t workspace_bytes, int n,
+                                        int H, int W, lfm_stream_t stream) {
+  if (!in || !w8 || !b8 || !moments || !workspace) return LFM_ERR_ARG;
+  const size_t need = lfm_vae_conv_moments_workspace_bytes(n, H, W);
+  if (!need) return LFM_ERR_SHAPE;
+  if (((uintptr_t)in | (uintptr_t)w8 | (uintptr_t)b8 | (uintptr_t)moments) & 15) return LFM_ERR_ALIGN;
+  if ((uintptr_t)workspace & 255) return LFM_ERR_ALIGN;
+  if (workspace_bytes < need) return LFM_ERR_WORKSPACE;
+  if (lfm_zero_async(workspace, 256, (hipStream_t)stream)) return LFM_ERR_LAUNCH;
+  return vae_conv_moments((const half_t*)in, (const half_t*)workspace, w8, b8, moments, n, H, W, (hipStream_t)stream);
+}
+
+// Workspace of the resnets: [zeros 256 B][stats n x 32 x {mean, rstd}][part: per image the larger of the convolution epilogues' slabs
+// (2 ceil(HW / 256) x Cmax / 4 pairs) and the statistics pass's (VGN_MAX_SLABS x 128)][four rotating buffers of n HW Cmax halves], Cmax = 512.
+static size_t vae_resnets_test_carve(int n, int HW, void* ws, VaeCtx* c) {
+  const size_t buf = (size_t)n * HW * 512 * 2;
+  const size_t conv_pairs = 2 * (size_t)cdiv(HW, 256) * 128, stat_pairs = (size_t)VGN_MAX_SLABS * 128;
+  const size_t part_pairs = (size_t)n * (conv_pairs > stat_pairs ? conv_pairs : stat_pairs);
+  size_t off = 0;
+  char* base = (char*)ws;
+  auto take = [&](size_t bytes) {
+    char* p = base ? base + off : nullptr;
+    off += a256(bytes);
+    return p;
+  };
+  half_t* zeros = (half_t*)take(256);
+  float* stats = (float*)take((size_t)n * 64 * 4);
+  float* part = (float*)take(part_pairs * 8);
+  half_t* b[4];
+  for (int i = 0; i < 4; ++i) b[i] = (half_t*)take(buf);
+  if (c) {
+    c->ws.zeros = zeros;
+    c->ws.stats = stats;
+    c->ws.part = part;
+    c->ws.part_pairs = part_pairs;
+    c->x = b[0];
+    c->t1 = b[1];
+    c->t2 = b[2];
+    c->t3 = b[3];
+  }
+  return off;
+}
+
+extern "C" size_t lfm_vae_resnets_workspace_bytes(int n, int H, int W) {
+  if (n <= 0 || H <= 0 || W <= 0 || (long)n * H * W * 512 >= (1L << 31)) return 0;
+  return vae_resnets_test_carve(n, H * W, nullptr, nullptr);
+}
+
+extern "C" int lfm_vae_resnets_f16(const lfm_vae_resnet* r, int n_res, const void* x, void* out, void* workspace, size_t workspace_bytes, int n, int H,
+                                   int W, int chain_stats, int* last_slabs, lfm_stream_t stream) {
+  if (!r || !x || !out || !workspace) return LFM_ERR_ARG;
+  if (n_res < 1 || n_res > 3) return LFM_ERR_SHAPE;
+  uintptr_t bits = (uintptr_t)x | (uintptr_t)out;
+  for (int i = 0; i < n_res; ++i) {
+    const lfm_vae_resnet& q = r[i];
+    if (!q.n1_g || !q.n1_b || !q.c1_w || !q.c1_b || !q.n2_g || !q.n2_b || !q.c2_w || !q.c2_b || (q.sc_w && !q.sc_b)) return LFM_ERR_ARG;
+    auto width = [](int ch) { return ch == 128 || ch == 256 || ch == 512; };
+    if (!width(q.cin) || !width(q.cout)) return LFM_ERR_SHAPE;
+    if ((q.cin != q.cout && !q.sc_w) || (i && r[i - 1].cout != q.cin)) return LFM_ERR_SHAPE;  // the identity skip needs equal widths
+    bits |= (uintptr_t)q.n1_g | (uintptr_t)q.n1_b | (uintptr_t)q.c1_w | (uintptr_t)q.c1_b | (uintptr_t)q.n2_g | (uintptr_t)q.n2_b | (uintptr_t)q.c2_w |
+            (uintptr_t)q.c2_b | (uintptr_t)q.sc_w | (uintptr_t)q.sc_b;
+  }
+  const size_t need = lfm_vae_resnets_workspace_bytes(n, H, W);
+  if (!need) return LFM_ERR_SHAPE;
+  if (bits & 15) return LFM_ERR_ALIGN;
+  if ((uintptr_t)workspace & 255) return LFM_ERR_ALIGN;
+  if (workspace_bytes < need) return LFM_ERR_WORKSPACE;
+  VaeCtx c{};
+  vae_resnets_test_carve(n, H * W, workspace, &c);
+  c.n = n;
+  c.st = (hipStream_t)stream;
+  c.x_slabs = 0;
+  c.chain_stats = chain_stats != 0;
+  if (lfm_zero_async(c.ws.zeros, 256, c.st)) return LFM_ERR_LAUNCH;
+  if (hipMemcpyAsync(c.x, x, (size_t)n * H * W * r[0].cin * 2, hipMemcpyDeviceToDevice, c.st) != hipSuccess) return LFM_ERR_LAUNCH;
+  for (int i = 0; i < n_res; ++i) RC(c.resnet(&r[i], H, W));
+  if (hipMemcpyAsync(out, c.x, (size_t)n * H * W * r[n_res - 1].cout * 2, hipMemcpyDeviceToDevice, c.st) != hipSuccess) return LFM_ERR_LAUNCH;
+  if (last_slabs) *last_slabs = c.x_slabs;
+  return LFM_OK;
+}
+
 // one chunk of images: x [n,3,8R,8R] -> moments [n,8,R,R]
 static int vae_encode_chunk(VaeCtx& c, const lfm_vae_enc_weights* w, const float* x, float* moments, int R) {
   int H = 8 * R;
@@ -604,9 +732,7 @@ static int vae_encode_chunk(VaeCtx& c, const lfm_vae_enc_weights* w, const float
   RC(c.mid_attention(w, H * H));
   RC(c.resnet(&w->mid[1], H, H));
   RC(c.gn(c.x, c.t1, w->no_g, w->no_b, H * H, 512, true, 0));
-  const int M = c.n * H * H;
-  return launch_gemm_tn(ASrcConv<0>{c.t1, c.ws.zeros, H, H, 512, M}, (const half_t*)w->cout_w, 9L * 512, M, 8, 9 * 512,
-                        EpiMomentsNCHW{moments, w->cout_b, H * H, 8}, c.st);
+  return vae_conv_moments(c.t1, c.ws.zeros, w->cout_w, w->cout_b, moments, c.n, H, H, c.st);
 }
 
 extern "C" int lfm_vae_encode(const lfm_vae_enc_weights* w, void* workspace, size_t workspace_bytes, const float* x, float* moments, int N, int R,

@@ -33,6 +33,11 @@ class DitCall(C.Structure):
                 ("cond_rows", C.c_int), ("fold_ln", C.c_int), ("gemm_select", C.c_int)]  # ABI 4; zero = "as before" (ctypes zero-fills omitted fields)
 
 
+class VaeResnet(C.Structure):  # include/lfm_hip.h: lfm_vae_resnet
+    _fields_ = [(n, C.c_void_p) for n in ("n1_g", "n1_b", "c1_w", "c1_b", "n2_g", "n2_b", "c2_w", "c2_b", "sc_w", "sc_b")] + [
+        ("cin", C.c_int), ("cout", C.c_int)]
+
+
 ABI_VERSION = 4  # include/lfm_hip.h: lfm_abi_version()
 CALL_OFF, CALL_ON = 1, 2  # lfm_dit_call.fold_ln
 
@@ -212,6 +217,20 @@ def lib():
     L.lfm_vae_mid_attention_workspace_bytes.argtypes = [I, I]
     L.lfm_vae_mid_attention_f16.restype = I
     L.lfm_vae_mid_attention_f16.argtypes = [V] * 13 + [C.c_size_t, I, I, V]
+    L.lfm_vae_conv_in_f16.restype = I
+    L.lfm_vae_conv_in_f16.argtypes = [V] * 6 + [I, I, V]
+    L.lfm_vae_downsample_workspace_bytes.restype = C.c_size_t
+    L.lfm_vae_downsample_workspace_bytes.argtypes = [I, I, I, I]
+    L.lfm_vae_downsample_f16.restype = I
+    L.lfm_vae_downsample_f16.argtypes = [V] * 5 + [C.c_size_t, I, I, I, I, V]
+    L.lfm_vae_resnets_workspace_bytes.restype = C.c_size_t
+    L.lfm_vae_resnets_workspace_bytes.argtypes = [I, I, I]
+    L.lfm_vae_resnets_f16.restype = I
+    L.lfm_vae_resnets_f16.argtypes = [C.POINTER(VaeResnet), I, V, V, V, C.c_size_t, I, I, I, I, C.POINTER(C.c_int), V]
+    L.lfm_vae_conv_moments_workspace_bytes.restype = C.c_size_t
+    L.lfm_vae_conv_moments_workspace_bytes.argtypes = [I, I, I]
+    L.lfm_vae_conv_moments_f32.restype = I
+    L.lfm_vae_conv_moments_f32.argtypes = [V] * 5 + [C.c_size_t, I, I, I, V]
     _lib = L
     return L
 

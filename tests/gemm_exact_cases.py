@@ -196,20 +196,26 @@ def linear_case(M, N, K):
 
 # ------------------------------------------------------------------------------------------------ lfm_conv3x3*_f16_ws
 def conv_input_size(H, W, mode):
-    """Input map of an OUTPUT size H x W: the same (mode 0), half (mode 1: nearest-2x upsample fused), double (mode 2: stride 2)."""
-    return {0: (H, W), 1: (H // 2, W // 2), 2: (2 * H, 2 * W)}[mode]
+    """Input map of an OUTPUT size H x W: the same (mode 0), half (mode 1: nearest-2x upsample fused), double (modes 2, 3: stride 2)."""
+    return {0: (H, W), 1: (H // 2, W // 2), 2: (2 * H, 2 * W), 3: (2 * H, 2 * W)}[mode]
 
 
-def conv_ref(x, Wt, bias, resid, N, H, W, Cin, mode):
-    """3x3 convolution (pad 1) of NHWC int64 x with Wt [Cout, 9 Cin] (k = tap * Cin + ci, tap = ky * 3 + kx) as an int64 im2col product + bias + resid.
-    mode 1: on the nearest-2x upsampled input; mode 2: stride 2 -- output (oy, ox) reads input (2 oy + ky - 1, 2 ox + kx - 1)."""
+def conv_cols(x, N, H, W, Cin, mode):
+    """The im2col matrix [N H W, 9 Cin] (k = tap * Cin + ci, tap = ky * 3 + kx) of NHWC x (any dtype) for an OUTPUT size H x W.  Modes 0 - 2 pad by one
+    pixel all round; mode 1: on the nearest-2x upsampled input; mode 2: stride 2 -- output (oy, ox) reads input (2 oy + ky - 1, 2 ox + kx - 1); mode 3:
+    stride 2 on the input padded (0, 1, 0, 1) (diffusers Downsample2D) -- reads (2 oy + ky, 2 ox + kx), zero beyond the bottom row and the right column."""
     Hi, Wi = conv_input_size(H, W, mode)
     x = x.reshape(N, Hi, Wi, Cin)
     if mode == 1:
         x = x.repeat_interleave(2, 1).repeat_interleave(2, 2)
-    xp = torch.nn.functional.pad(x, (0, 0, 1, 1, 1, 1))
-    s = 2 if mode == 2 else 1
-    cols = torch.cat([xp[:, ky:ky + s * H:s, kx:kx + s * W:s, :] for ky in range(3) for kx in range(3)], -1).reshape(N * H * W, 9 * Cin)
+    xp = torch.nn.functional.pad(x, (0, 0, 0, 1, 0, 1) if mode == 3 else (0, 0, 1, 1, 1, 1))
+    s = 2 if mode >= 2 else 1
+    return torch.cat([xp[:, ky:ky + s * H:s, kx:kx + s * W:s, :] for ky in range(3) for kx in range(3)], -1).reshape(N * H * W, 9 * Cin)
+
+
+def conv_ref(x, Wt, bias, resid, N, H, W, Cin, mode):
+    """3x3 convolution of NHWC int64 x with Wt [Cout, 9 Cin] as an int64 im2col product (conv_cols: the modes) + bias + resid."""
+    cols = conv_cols(x, N, H, W, Cin, mode)
     out = exact_mm(cols, Wt) + bias
     mag = abs_mm(cols, Wt) + bias.abs()
     if resid is not None:
