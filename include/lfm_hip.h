@@ -113,6 +113,14 @@ typedef struct lfm_dit_call {
  * split-K GEMMs (reserved for every max_batch, so the requirement is monotone: a workspace sized for max_batch serves every smaller batch). */
 size_t lfm_dit_workspace_bytes(const lfm_dit_shape* shape, int max_batch);
 
+/* Where an evaluation at `batch` keeps its intermediate results inside the workspace (tests and tools read them back after a forward): byte offsets of
+ * X (fp32 [M, D] residual stream), A, A2 (fp16 [M, D]), QKVH (fp16: Q | K | Vt, later the [M, H] fc1 activation), mod (fp32 [rows, J]), ln_part
+ * (fp32 [M][D / 256][2]), cen[0], cen[1] (fp32 [M]), uvq, uvf, in this order, into offsets_out[0 .. min(n, LFM_DIT_WS_BUFFERS)); 0 where the shape has no such
+ * buffer (X itself is at 0).  The offsets depend on the batch of the CALL, not on the size of the workspace.  Returns LFM_DIT_WS_BUFFERS or an error; no
+ * launch; usable without a GPU. */
+#define LFM_DIT_WS_BUFFERS 10
+int lfm_dit_workspace_layout(const lfm_dit_shape* shape, int batch, size_t* offsets_out, int n);
+
 /* Replaces DiT.forward / DiT.forward_with_cfg (models/DiT.py:252-290) as called by the solver closure
  * `denoiser` (test_flow_latent.py:55-59) and sampler/karras_sample.py:42-46. */
 int lfm_dit_forward(const lfm_dit_shape* shape, const lfm_dit_weights* w, void* workspace, size_t workspace_bytes,

@@ -169,7 +169,7 @@ static DitWs carve(const lfm_dit_shape* s, const DitDims& d, void* ws, bool sizi
   char* base = (char*)ws;
   DitWs w;
   auto take = [&](size_t bytes) {
-    char* p = base ? base + off : nullptr;
+    char* p = (char*)((uintptr_t)base + off);  // with a null base the pointers ARE the byte offsets (lfm_dit_workspace_layout)
     off += align_up(bytes, 256);
     return p;
   };
@@ -234,6 +234,20 @@ extern "C" int lfm_abi_version(void) { return LFM_ABI_VERSION; }  // 2: lfm_time
 extern "C" size_t lfm_dit_workspace_bytes(const lfm_dit_shape* shape, int max_batch) {
   if (check_shape(shape) != LFM_OK || max_batch <= 0) return 0;
   return carve(shape, dit_dims(shape, max_batch), nullptr, true).total;
+}
+
+// Byte offsets of the buffers an evaluation at `batch` reads and writes inside its workspace, from carve() itself (tests read intermediate results back).
+extern "C" int lfm_dit_workspace_layout(const lfm_dit_shape* shape, int batch, size_t* offsets_out, int n) {
+  const int rc = check_shape(shape);
+  if (rc) return rc;
+  if (!offsets_out || n < 0) return LFM_ERR_ARG;
+  if (batch <= 0) return LFM_ERR_SHAPE;
+  const DitWs w = carve(shape, dit_dims(shape, batch), nullptr);
+  const bool fold_ops = dit_fold_capable(shape);
+  const void* bufs[LFM_DIT_WS_BUFFERS] = {w.X, w.A, fold_ops ? w.A2 : nullptr, w.QKVH, w.mod, w.ln_part, w.cen[0], w.cen[1], fold_ops ? w.uvq : nullptr,
+                                          fold_ops ? w.uvf : nullptr};
+  for (int i = 0; i < n && i < LFM_DIT_WS_BUFFERS; ++i) offsets_out[i] = (size_t)(uintptr_t)bufs[i];
+  return LFM_DIT_WS_BUFFERS;
 }
 
 extern "C" int lfm_dit_attention_hd(const void* Q, const void* K, const void* Vt, void* O, int batch, int heads, int head_dim, int T,

@@ -107,7 +107,9 @@ struct EpiGateResidF32 : EpiGateResid {};
 // PRODUCER = the gated-residual GEMM that updates x (proj, fc2; EpiGateResidMod): its epilogue already holds the new x in registers, so it also
 //   writes A' = fp16((x - c)(1 + s)) -- the consumer's A operand -- and per-row partials (sum x, sum (x - c)^2) of its 256 columns into a fixed slot
 //   part[m][tile_n] (plain stores, deterministic).  c = cen[m] = the row mean BEFORE this update (written by the previous consumer), so x - c is
-//   centred up to the mean shift of one residual update: no cancellation in the fp16 rounding of A' or in the one-pass variance.
+//   centred up to the mean shift of one residual update: no cancellation in the fp16 rounding of A' or in the one-pass variance -- while that shift
+//   r = |mu - c| / std stays below ~1.  The operand error grows like r 2^-11 (measured: the fc1 activation leaves the per-forward budget at r = 6 .. 8;
+//   DESIGN.md, "Folded LayerNorm-modulate"; tests/test_gpu_dit_ln.py holds every piece to a bound that grows with the row's own r).
 // CONSUMER = the GEMM that reads A' (qkv, fc1; rowstat epilogues below): before its K loop every tile reduces its 256 rows' partials to
 //   a = rstd, b = -rstd (mu - c) in LDS (and tile column 0 publishes mu as the next producer's c); its epilogue evaluates a * acc + (b * u + v).
 // No inter-workgroup synchronisation, no second pass over x: both LN-modulate launches of a block (2 x 100 MB of HBM traffic) disappear for

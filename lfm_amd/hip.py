@@ -80,6 +80,8 @@ def lib():
         raise LfmHipError(f"{path} has ABI {L.lfm_abi_version()}, this package binds ABI {ABI_VERSION}: rebuild it (python -m lfm_amd._build --force)")
     L.lfm_dit_workspace_bytes.restype = C.c_size_t
     L.lfm_dit_workspace_bytes.argtypes = [C.POINTER(DitShape), C.c_int]
+    L.lfm_dit_workspace_layout.restype = C.c_int
+    L.lfm_dit_workspace_layout.argtypes = [C.POINTER(DitShape), C.c_int, C.POINTER(C.c_size_t), C.c_int]
     L.lfm_dit_forward.restype = C.c_int
     L.lfm_dit_forward.argtypes = [C.POINTER(DitShape), C.POINTER(DitWeights), C.c_void_p, C.c_size_t, C.POINTER(DitCall), C.c_void_p]
     L.lfm_gemm_f16.restype = C.c_int
@@ -399,6 +401,19 @@ def dit_plan(shape, batch, t_len=1, labels=False, fold_ln=0, gemm_select=0):
     plan = C.c_int(-1)
     check(lib().lfm_dit_plan(C.byref(shape), C.byref(call), C.byref(plan)), "lfm_dit_plan")
     return plan.value
+
+
+DIT_WS_BUFFERS = ("X", "A", "A2", "QKVH", "mod", "ln_part", "cen0", "cen1", "uvq", "uvf")  # include/lfm_hip.h: lfm_dit_workspace_layout
+
+
+def dit_workspace_layout(shape, batch):
+    """{buffer name: byte offset} inside the workspace of an evaluation at this batch (csrc/dit.hip: carve; 0 where the shape has no such buffer; no GPU needed)."""
+    offs = (C.c_size_t * len(DIT_WS_BUFFERS))()
+    rc = lib().lfm_dit_workspace_layout(C.byref(shape), int(batch), offs, len(DIT_WS_BUFFERS))
+    if rc < 0:
+        check(rc, "lfm_dit_workspace_layout")
+    assert rc == len(DIT_WS_BUFFERS), rc
+    return dict(zip(DIT_WS_BUFFERS, (int(o) for o in offs)))
 
 
 GEMM_CAP_V6, GEMM_CAP_FITS = 1, 2  # lfm_gemm_plan caps: row-major A and an epilogue the one-wave-per-SIMD kernel serves; operands within 32-bit buffer offsets

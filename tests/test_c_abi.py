@@ -43,6 +43,10 @@ int main(void) {
   c.gemm_select = LFM_CALL_GEMM_SELECT(5); c.fold_ln = LFM_CALL_OFF;
   rc = lfm_dit_call_settings(&c, &sel, &fold);
   printf("percall rc %d sel %d fold %d\n", rc, sel, fold);
+  lfm_dit_shape s = {1, 512, 8, 2, 4, 32, 2048, 1};
+  size_t offs[LFM_DIT_WS_BUFFERS];
+  rc = lfm_dit_workspace_layout(&s, 2, offs, LFM_DIT_WS_BUFFERS);  /* host only */
+  printf("layout rc %d X %zu A %zu bytes %zu\n", rc, offs[0], offs[1], lfm_dit_workspace_bytes(&s, 2));
   return 0;
 }
 """
@@ -108,6 +112,8 @@ def test_c_caller_sees_abi_4_and_call_scoped_settings(c_report):
     assert line[3:9] == ["rc", "0", "sel", "0", "fold", "1"], line  # zero-initialised call = library defaults (automatic kernels, fold on)
     per = [x for x in c_report["lines"] if x.startswith("percall ")][0].split()
     assert per[1:] == ["rc", "0", "sel", "5", "fold", "0"], per
+    lay = [x for x in c_report["lines"] if x.startswith("layout ")][0].split()
+    assert lay[1:7] == ["rc", "10", "X", "0", "A", str(2 * 256 * 512 * 4)] and int(lay[8]) > int(lay[6]), lay  # lfm_dit_workspace_layout from C
 
 
 def _header_struct_fields(name):

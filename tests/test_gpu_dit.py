@@ -751,10 +751,12 @@ def test_trained_like_dynamic_range(dev, fold):
     ref = dit_ref.dit_forward(sd, cfg, t, x[:k])
     err = rel_l2(out[:k].cpu(), ref)
     assert err < 2e-3, err
-    # the fc1 activation of the last block: fp16 [M, H] at the start of the Q | K | V^T region (csrc/dit.hip::carve: X fp32, A fp16, then QKVH)
+    # the fc1 activation of the last block: fp16 [M, H] at the start of the Q | K | V^T region (hip.dit_workspace_layout: csrc/dit.hip's own carve)
     M, H = batch * 256, cfg.mlp_hidden
     ws = m._ws[1]
-    off = M * D * 4 + M * D * 2
+    lay = hip.dit_workspace_layout(m.shape_struct(), batch)
+    assert lay["X"] == 0
+    off = lay["QKVH"]
     hb = ws[off:off + M * H * 2].view(torch.float16)
     print(f"dynamic range (fold={fold}): fc1 activation peak {float(hb.abs().max()):.1f}, residual peak {float(ws[:M * D * 4].view(torch.float32).abs().max()):.0f}, "
           f"rel-L2 vs oracle {err:.2e}")

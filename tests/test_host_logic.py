@@ -283,6 +283,39 @@ def test_dit_workspace_requirement_is_monotone_in_the_batch():
     assert L.lfm_dit_workspace_bytes(C.byref(bad), 1) == 0
 
 
+def test_dit_workspace_layout_is_the_drivers_carve():
+    """lfm_dit_workspace_layout (host only): the offsets of the buffers a forward at this batch uses, in the order of the header, 256-byte aligned, disjoint,
+    inside lfm_dit_workspace_bytes, depending on the batch; buffers only the folded path has are 0 for shapes that never fold; bad arguments are refused."""
+    import ctypes as C
+
+    from lfm_amd import hip
+
+    L = hip.lib()
+    fold = hip.DitShape(depth=2, hidden=512, heads=8, mlp_hidden=2048, patch=2, in_ch=4, res=32, label_rows=5)
+    plain = hip.DitShape(depth=2, hidden=384, heads=6, mlp_hidden=1536, patch=2, in_ch=4, res=16, label_rows=5)
+    assert hip.DIT_WS_BUFFERS == ("X", "A", "A2", "QKVH", "mod", "ln_part", "cen0", "cen1", "uvq", "uvf")
+    for s, B in ((fold, 1), (fold, 3), (fold, 96), (plain, 1), (plain, 7)):
+        lay = hip.dit_workspace_layout(s, B)
+        M, D, H = B * (s.res // s.patch) ** 2, s.hidden, s.mlp_hidden
+        J = s.depth * 6 * D + 2 * D
+        folds = D % 256 == 0
+        size = {"X": M * D * 4, "A": M * D * 2, "A2": M * D * 2, "QKVH": max(3 * M * D, M * H) * 2, "mod": B * J * 4, "ln_part": M * ((D + 255) // 256) * 8,
+                "cen0": M * 4, "cen1": M * 4, "uvq": s.depth * 2 * B * 3 * D * 4, "uvf": s.depth * 2 * B * H * 4}
+        assert lay["X"] == 0 and lay["A"] == M * D * 4 + (-M * D * 4) % 256  # X first, A behind it (what test_trained_like_dynamic_range once computed by hand)
+        present = [n for n in hip.DIT_WS_BUFFERS if folds or n not in ("A2", "uvq", "uvf")]
+        assert all(lay[n] == 0 for n in hip.DIT_WS_BUFFERS if n not in present)
+        spans = sorted((lay[n], lay[n] + size[n], n) for n in present)
+        assert all(a % 256 == 0 for a, _, _ in spans)
+        assert all(e0 <= a1 for (_, e0, _), (a1, _, _) in zip(spans, spans[1:])), spans  # disjoint
+        assert spans[-1][1] <= L.lfm_dit_workspace_bytes(C.byref(s), B)
+    assert hip.dit_workspace_layout(fold, 2)["A"] == 2 * hip.dit_workspace_layout(fold, 1)["A"]  # the batch of the call decides
+    two = (C.c_size_t * 2)(7, 7)
+    assert L.lfm_dit_workspace_layout(C.byref(fold), 1, two, 2) == len(hip.DIT_WS_BUFFERS) and list(two) == [0, hip.dit_workspace_layout(fold, 1)["A"]]
+    assert L.lfm_dit_workspace_layout(C.byref(fold), 0, two, 2) == -1 and L.lfm_dit_workspace_layout(C.byref(fold), 1, None, 2) == -5
+    bad = hip.DitShape(depth=28, hidden=1280, heads=16, mlp_hidden=5120, patch=2, in_ch=4, res=32, label_rows=1)  # head_dim 80: no kernel
+    assert L.lfm_dit_workspace_layout(C.byref(bad), 1, two, 2) == -1
+
+
 # ----------------------------------------------------------------------------- ADVICE r1: label bounds, buffer ownership, invalidation
 def test_label_bounds_raise_like_nn_embedding():
     from lfm_amd import hip
