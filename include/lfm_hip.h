@@ -290,6 +290,10 @@ typedef struct lfm_vae_weights {
   const void* cout_w; const float* cout_b; /* decoder.conv_out padded to 4 outputs: fp16 [4][9][128], fp32 [4] */
 } lfm_vae_weights;
 
+/* Every VAE entry point lays its workspace out in one order -- four rotating activation buffers, {mean, rstd} per image and group, the partial
+ * GroupNorm statistics in 8-byte {mean, M2} pairs, 256 B of zeros, the attention scores -- each piece rounded up to 256 bytes (a(v) below), a piece
+ * the call does not use left out.
+ * lfm_vae_workspace_bytes(R, c) = 4 a(c (8R)^2 512) + a(c 256) + a(c max((8R)^2 / 2, 8192) 8) + 256 + a(c R^4 4); 0 if R <= 0, c <= 0 or R % 8. */
 size_t lfm_vae_workspace_bytes(int R, int chunk);
 
 /* out[N,3,8R,8R] fp32 NCHW = decode(z[N,4,R,R] fp32 NCHW); images are processed `chunk` at a time so the
@@ -317,8 +321,9 @@ int lfm_vae_encode(const lfm_vae_enc_weights* w, void* workspace, size_t workspa
                    int chunk, lfm_stream_t stream);
 
 /* Test entry points for the decoder's GroupNorm (32 groups, eps 1e-6), running the decoder's own host code.  Workspace (256-byte aligned):
- * 256 B + n x 256 B (rounded up to 256) + the partial-statistics room in 8-byte pairs -- the decoder gives lfm_vae_workspace_bytes' share, and the
- * statistics pass takes up to 512 slabs per image when n < 16 and that room allows it, else 64 (at least n x 64 x C / 4 pairs are required).
+ * 256 B + n x 256 B (rounded up to 256) + the partial-statistics room in 8-byte pairs, used in whole 256-byte pieces -- the decoder gives
+ * lfm_vae_workspace_bytes' share, and the statistics pass takes up to 512 slabs per image when n < 16 and that room allows it, else 64 (at least
+ * n x 64 x C / 4 pairs are required).
  * lfm_vae_groupnorm_f16: y = silu?(GroupNorm(x) * gamma + beta), x, y fp16 NHWC [n, HW, C], C in {128, 256, 512}; statistics by their own pass. */
 int lfm_vae_groupnorm_f16(const void* x, void* y, const float* gamma, const float* beta, void* workspace, size_t workspace_bytes, int n, int HW, int C,
                           int silu, lfm_stream_t stream);
@@ -332,7 +337,8 @@ int lfm_vae_conv3x3_gn_f16(const void* in, const void* w, const float* bias, con
 /* Test entry point for the mid-block attention of the decoder and the encoder, running their own host code (GroupNorm -> q, k, v -> softmax(q k^T / sqrt(512)) v
  * -> to_out + x): x, out fp16 NHWC [n, T, 512]; weights fp16 [512][512] row-major [out][in] as lfm_vae_weights holds them; biases and GroupNorm
  * parameters fp32; all 16-byte aligned.  T % 64 == 0 (the decoder's T = R^2 with R % 8 == 0).  Workspace (256-byte aligned):
- * lfm_vae_mid_attention_workspace_bytes(n, T), 0 for a shape that is refused. */
+ * lfm_vae_mid_attention_workspace_bytes(n, T) = 256 + a(n 256) + a(n max(32 T, 8192) 8) + 4 a(n T (512 + max(512, T)) 2) + a(n T^2 4), the
+ * statistics room being the decoder's share per image at R^2 = T; 0 if n <= 0, T <= 0 or T % 64. */
 size_t lfm_vae_mid_attention_workspace_bytes(int n, int T);
 int lfm_vae_mid_attention_f16(const void* x, void* out, const float* gn_gamma, const float* gn_beta, const void* q_w, const float* q_b,
                               const void* k_w, const float* k_b, const void* v_w, const float* v_b, const void* o_w, const float* o_b,
@@ -340,6 +346,8 @@ int lfm_vae_mid_attention_f16(const void* x, void* out, const float* gn_gamma, c
 /* Test entry points for four more stages of the first-stage VAE, each running the decoder's / encoder's own host code on the caller's buffers.  Additions
  * to ABI 4.  All refuse before any launch: a null pointer (LFM_ERR_ARG), a shape outside the stated limits (LFM_ERR_SHAPE), a tensor that is not 16-byte
  * or a workspace that is not 256-byte aligned (LFM_ERR_ALIGN), a workspace below *_workspace_bytes (LFM_ERR_WORKSPACE; 0 for a refused shape).
+ * Every VAE entry point with a workspace refuses in this order, lfm_vae_decode and lfm_vae_encode included: a workspace that is both misaligned and
+ * short is LFM_ERR_ALIGN (those two answered LFM_ERR_WORKSPACE for it before they shared the set-up of the others).
  *
  * lfm_vae_conv_in_f16: diffusers AutoencoderKL.post_quant_conv (1x1, 4 -> 4) followed by Decoder.conv_in (3x3, pad 1, 4 -> 512) in one kernel:
  *   z fp32 NCHW [n,4,R,R] -> out fp16 NHWC [n,R,R,512]; pq_w fp32 [4][4], pq_b [4], cin_w fp32 [512][4][3][3], cin_b [512].  conv_in pads
@@ -355,7 +363,9 @@ int lfm_vae_downsample_f16(const void* x, const void* w, const float* bias, void
 /* lfm_vae_resnets_f16: n_res (1 .. 3) diffusers ResnetBlock2D (temb None: GroupNorm+SiLU -> conv1 -> GroupNorm+SiLU -> conv2 + (conv_shortcut of) x) in
  *   sequence on the drivers' four rotating buffers: x fp16 NHWC [n,H,W,r[0].cin] -> out [n,H,W,r[n_res-1].cout]; widths in {128, 256, 512}, r[i].cout ==
  *   r[i+1].cin, sc_w required where cin != cout.  chain_stats 1 (decoder): conv2 leaves the GroupNorm statistics of its output for the next resnet where its
- *   kernel can; 0 (encoder): every GroupNorm runs its own pass.  *last_slabs (may be NULL) = the statistics slabs per image the last conv2 left (0: none). */
+ *   kernel can; 0 (encoder): every GroupNorm runs its own pass.  *last_slabs (may be NULL) = the statistics slabs per image the last conv2 left (0: none).
+ *   lfm_vae_resnets_workspace_bytes(n, H, W) = 256 + a(n 256) + a(n max(2 ceil(H W / 256) 128, 8192) 8) + 4 a(n H W 512 2); 0 if an argument is <= 0
+ *   or n H W 512 >= 2^31. */
 size_t lfm_vae_resnets_workspace_bytes(int n, int H, int W);
 int lfm_vae_resnets_f16(const lfm_vae_resnet* r, int n_res, const void* x, void* out, void* workspace, size_t workspace_bytes, int n, int H, int W,
                         int chain_stats, int* last_slabs, lfm_stream_t stream);

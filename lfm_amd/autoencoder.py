@@ -81,17 +81,21 @@ def _resnet(cin, cout):
     return m
 
 
+def _attention():
+    att = nn.Module()
+    att.group_norm = nn.GroupNorm(32, 512, eps=1e-6)
+    att.to_q, att.to_k, att.to_v = nn.Linear(512, 512), nn.Linear(512, 512), nn.Linear(512, 512)
+    att.to_out = nn.ModuleList([nn.Linear(512, 512)])
+    return att
+
+
 class _Decoder(nn.Module):
     def __init__(self):
         super().__init__()
         self.conv_in = nn.Conv2d(4, 512, 3, padding=1)
         self.mid_block = nn.Module()
         self.mid_block.resnets = nn.ModuleList([_resnet(512, 512), _resnet(512, 512)])
-        att = nn.Module()
-        att.group_norm = nn.GroupNorm(32, 512, eps=1e-6)
-        att.to_q, att.to_k, att.to_v = nn.Linear(512, 512), nn.Linear(512, 512), nn.Linear(512, 512)
-        att.to_out = nn.ModuleList([nn.Linear(512, 512)])
-        self.mid_block.attentions = nn.ModuleList([att])
+        self.mid_block.attentions = nn.ModuleList([_attention()])
         self.up_blocks = nn.ModuleList()
         cin = 512
         for i, cout in enumerate(reversed(BLOCK_OUT)):
@@ -105,14 +109,6 @@ class _Decoder(nn.Module):
             cin = cout
         self.conv_norm_out = nn.GroupNorm(32, 128, eps=1e-6)
         self.conv_out = nn.Conv2d(128, 3, 3, padding=1)
-
-
-def _attention():
-    att = nn.Module()
-    att.group_norm = nn.GroupNorm(32, 512, eps=1e-6)
-    att.to_q, att.to_k, att.to_v = nn.Linear(512, 512), nn.Linear(512, 512), nn.Linear(512, 512)
-    att.to_out = nn.ModuleList([nn.Linear(512, 512)])
-    return att
 
 
 class _Encoder(nn.Module):
@@ -137,6 +133,43 @@ class _Encoder(nn.Module):
         self.mid_block.attentions = nn.ModuleList([_attention()])
         self.conv_norm_out = nn.GroupNorm(32, 512, eps=1e-6)
         self.conv_out = nn.Conv2d(512, 8, 3, padding=1)
+
+
+class _Packer:
+    """Device copies of parameters in the library's layouts; ``keep`` holds them for as long as the packed struct is used."""
+
+    def __init__(self, dev):
+        self.dev, self.keep = dev, []
+
+    def _ptr(self, t, dtype):
+        self.keep.append(t.detach().to(self.dev, dtype).contiguous())
+        return self.keep[-1].data_ptr()
+
+    def f32(self, t):
+        return self._ptr(t, torch.float32)
+
+    def f16(self, t):
+        return self._ptr(t, torch.float16)
+
+    def conv3(self, w):  # [Cout,Cin,3,3] -> [Cout, tap, Cin]
+        return self.f16(w.permute(0, 2, 3, 1).reshape(w.shape[0], -1))
+
+    def res(self, m):
+        f32, f16, conv3 = self.f32, self.f16, self.conv3
+        r = _Res()
+        r.n1_g, r.n1_b, r.c1_w, r.c1_b = f32(m.norm1.weight), f32(m.norm1.bias), conv3(m.conv1.weight), f32(m.conv1.bias)
+        r.n2_g, r.n2_b, r.c2_w, r.c2_b = f32(m.norm2.weight), f32(m.norm2.bias), conv3(m.conv2.weight), f32(m.conv2.bias)
+        if hasattr(m, "conv_shortcut"):
+            r.sc_w, r.sc_b = f16(m.conv_shortcut.weight.reshape(m.conv_shortcut.weight.shape[0], -1)), f32(m.conv_shortcut.bias)
+        r.cin, r.cout = m.conv1.in_channels, m.conv1.out_channels
+        return r
+
+    def attention(self, w, a):
+        """The mid-block attention's ten fields of ``w`` (_VaeWeights and _VaeEncWeights name them alike)."""
+        f32, f16 = self.f32, self.f16
+        w.at_g, w.at_b = f32(a.group_norm.weight), f32(a.group_norm.bias)
+        w.q_w, w.q_b, w.k_w, w.k_b = f16(a.to_q.weight), f32(a.to_q.bias), f16(a.to_k.weight), f32(a.to_k.bias)
+        w.v_w, w.v_b, w.o_w, w.o_b = f16(a.to_v.weight), f32(a.to_v.bias), f16(a.to_out[0].weight), f32(a.to_out[0].bias)
 
 
 class AutoencoderKL(nn.Module):
@@ -230,104 +263,70 @@ class AutoencoderKL(nn.Module):
         return super()._apply(fn, *a, **k)
 
     # ---- packing
+    def _packer(self):
+        hip.require_gpu(self.post_quant_conv.weight, "AutoencoderKL")
+        return _Packer(self.post_quant_conv.weight.device)
+
     @torch.no_grad()
     def _pack(self):
-        dev = self.post_quant_conv.weight.device
-        hip.require_gpu(self.post_quant_conv.weight, "AutoencoderKL")
-        keep = []
-
-        def f32(t):
-            keep.append(t.detach().to(dev, torch.float32).contiguous())
-            return keep[-1].data_ptr()
-
-        def f16(t):
-            keep.append(t.detach().to(dev, torch.float16).contiguous())
-            return keep[-1].data_ptr()
-
-        def conv3(w):  # [Cout,Cin,3,3] -> [Cout, tap, Cin]
-            return f16(w.permute(0, 2, 3, 1).reshape(w.shape[0], -1))
-
-        def res(m):
-            r = _Res()
-            r.n1_g, r.n1_b, r.c1_w, r.c1_b = f32(m.norm1.weight), f32(m.norm1.bias), conv3(m.conv1.weight), f32(m.conv1.bias)
-            r.n2_g, r.n2_b, r.c2_w, r.c2_b = f32(m.norm2.weight), f32(m.norm2.bias), conv3(m.conv2.weight), f32(m.conv2.bias)
-            if hasattr(m, "conv_shortcut"):
-                r.sc_w, r.sc_b = f16(m.conv_shortcut.weight.reshape(m.conv_shortcut.weight.shape[0], -1)), f32(m.conv_shortcut.bias)
-            r.cin, r.cout = m.conv1.in_channels, m.conv1.out_channels
-            return r
-
+        p = self._packer()
         d = self.decoder
         w = _VaeWeights()
-        w.pq_w, w.pq_b = f32(self.post_quant_conv.weight.reshape(4, 4)), f32(self.post_quant_conv.bias)
-        w.cin_w, w.cin_b = f32(d.conv_in.weight), f32(d.conv_in.bias)
-        w.mid[0], w.mid[1] = res(d.mid_block.resnets[0]), res(d.mid_block.resnets[1])
-        a = d.mid_block.attentions[0]
-        w.at_g, w.at_b = f32(a.group_norm.weight), f32(a.group_norm.bias)
-        w.q_w, w.q_b, w.k_w, w.k_b = f16(a.to_q.weight), f32(a.to_q.bias), f16(a.to_k.weight), f32(a.to_k.bias)
-        w.v_w, w.v_b, w.o_w, w.o_b = f16(a.to_v.weight), f32(a.to_v.bias), f16(a.to_out[0].weight), f32(a.to_out[0].bias)
+        w.pq_w, w.pq_b = p.f32(self.post_quant_conv.weight.reshape(4, 4)), p.f32(self.post_quant_conv.bias)
+        w.cin_w, w.cin_b = p.f32(d.conv_in.weight), p.f32(d.conv_in.bias)
+        w.mid[0], w.mid[1] = p.res(d.mid_block.resnets[0]), p.res(d.mid_block.resnets[1])
+        p.attention(w, d.mid_block.attentions[0])
         for i, blk in enumerate(d.up_blocks):
             for j in range(3):
-                w.up[i][j] = res(blk.resnets[j])
+                w.up[i][j] = p.res(blk.resnets[j])
             if i < 3:
-                w.ups_w[i], w.ups_b[i] = conv3(blk.upsamplers[0].conv.weight), f32(blk.upsamplers[0].conv.bias)
-        w.no_g, w.no_b = f32(d.conv_norm_out.weight), f32(d.conv_norm_out.bias)
-        cw = torch.zeros(4, 128, 3, 3, device=dev)
+                w.ups_w[i], w.ups_b[i] = p.conv3(blk.upsamplers[0].conv.weight), p.f32(blk.upsamplers[0].conv.bias)
+        w.no_g, w.no_b = p.f32(d.conv_norm_out.weight), p.f32(d.conv_norm_out.bias)
+        cw = torch.zeros(4, 128, 3, 3, device=p.dev)
         cw[:3] = d.conv_out.weight
-        cb = torch.zeros(4, device=dev)
+        cb = torch.zeros(4, device=p.dev)
         cb[:3] = d.conv_out.bias
-        w.cout_w, w.cout_b = conv3(cw), f32(cb)
-        self._packed = (w, keep)
+        w.cout_w, w.cout_b = p.conv3(cw), p.f32(cb)
+        self._packed = (w, p.keep)
         return self._packed
 
     @torch.no_grad()
     def _pack_enc(self):
         if not self.with_encoder:
             raise hip.LfmHipError("this AutoencoderKL was built without the encoder half: AutoencoderKL(with_encoder=True) / from_pretrained")
-        dev = self.post_quant_conv.weight.device
-        hip.require_gpu(self.post_quant_conv.weight, "AutoencoderKL")
-        keep = []
-
-        def f32(t):
-            keep.append(t.detach().to(dev, torch.float32).contiguous())
-            return keep[-1].data_ptr()
-
-        def f16(t):
-            keep.append(t.detach().to(dev, torch.float16).contiguous())
-            return keep[-1].data_ptr()
-
-        def conv3(w):
-            return f16(w.permute(0, 2, 3, 1).reshape(w.shape[0], -1))
-
-        def res(m):
-            r = _Res()
-            r.n1_g, r.n1_b, r.c1_w, r.c1_b = f32(m.norm1.weight), f32(m.norm1.bias), conv3(m.conv1.weight), f32(m.conv1.bias)
-            r.n2_g, r.n2_b, r.c2_w, r.c2_b = f32(m.norm2.weight), f32(m.norm2.bias), conv3(m.conv2.weight), f32(m.conv2.bias)
-            if hasattr(m, "conv_shortcut"):
-                r.sc_w, r.sc_b = f16(m.conv_shortcut.weight.reshape(m.conv_shortcut.weight.shape[0], -1)), f32(m.conv_shortcut.bias)
-            r.cin, r.cout = m.conv1.in_channels, m.conv1.out_channels
-            return r
-
+        p = self._packer()
         e = self.encoder
         w = _VaeEncWeights()
-        w.cin_w, w.cin_b = f32(e.conv_in.weight), f32(e.conv_in.bias)
+        w.cin_w, w.cin_b = p.f32(e.conv_in.weight), p.f32(e.conv_in.bias)
         for i, blk in enumerate(e.down_blocks):
             for j in range(2):
-                w.down[i][j] = res(blk.resnets[j])
+                w.down[i][j] = p.res(blk.resnets[j])
             if i < 3:
-                w.ds_w[i], w.ds_b[i] = conv3(blk.downsamplers[0].conv.weight), f32(blk.downsamplers[0].conv.bias)
-        w.mid[0], w.mid[1] = res(e.mid_block.resnets[0]), res(e.mid_block.resnets[1])
-        a = e.mid_block.attentions[0]
-        w.at_g, w.at_b = f32(a.group_norm.weight), f32(a.group_norm.bias)
-        w.q_w, w.q_b, w.k_w, w.k_b = f16(a.to_q.weight), f32(a.to_q.bias), f16(a.to_k.weight), f32(a.to_k.bias)
-        w.v_w, w.v_b, w.o_w, w.o_b = f16(a.to_v.weight), f32(a.to_v.bias), f16(a.to_out[0].weight), f32(a.to_out[0].bias)
-        w.no_g, w.no_b = f32(e.conv_norm_out.weight), f32(e.conv_norm_out.bias)
+                w.ds_w[i], w.ds_b[i] = p.conv3(blk.downsamplers[0].conv.weight), p.f32(blk.downsamplers[0].conv.bias)
+        w.mid[0], w.mid[1] = p.res(e.mid_block.resnets[0]), p.res(e.mid_block.resnets[1])
+        p.attention(w, e.mid_block.attentions[0])
+        w.no_g, w.no_b = p.f32(e.conv_norm_out.weight), p.f32(e.conv_norm_out.bias)
         # quant_conv (1x1, 8 -> 8) folded into conv_out (exact algebra, done in fp64 before the fp16 rounding of the GEMM operand)
-        q = self.quant_conv.weight.detach().double().reshape(8, 8).to(dev)
-        cw = torch.einsum("oi,ichw->ochw", q, e.conv_out.weight.detach().double().to(dev))
-        cb = q @ e.conv_out.bias.detach().double().to(dev) + self.quant_conv.bias.detach().double().to(dev)
-        w.cout_w, w.cout_b = conv3(cw.float()), f32(cb.float())
-        self._packed_enc = (w, keep)
+        q = self.quant_conv.weight.detach().double().reshape(8, 8).to(p.dev)
+        cw = torch.einsum("oi,ichw->ochw", q, e.conv_out.weight.detach().double().to(p.dev))
+        cb = q @ e.conv_out.bias.detach().double().to(p.dev) + self.quant_conv.bias.detach().double().to(p.dev)
+        w.cout_w, w.cout_b = p.conv3(cw.float()), p.f32(cb.float())
+        self._packed_enc = (w, p.keep)
         return self._packed_enc
+
+    def _run(self, name, w, x, R, out):
+        """``name`` (lfm_vae_encode / lfm_vae_decode) on x -> out, N images at latent size R, ``chunk`` images per pass in the shared workspace."""
+        N = x.shape[0]
+        # images per pass: bigger is faster (57.9 ms vs 65.9 ms per 64 images for 64 vs 16 at 256x256) and bounded by the
+        # 4 ping-pong activation buffers: auto = 64 images at 256x256 (8.6 GB), scaled by resolution (16 at 512x512)
+        chunk = min(self.decode_chunk or max(1, (64 * 32 * 32) // (R * R)), N, self._max_chunk(R))
+        L = hip.lib()
+        need = L.lfm_vae_workspace_bytes(R, chunk)
+        if self._ws is None or self._ws.numel() < need or self._ws.device != x.device:
+            self._ws = torch.empty(need, dtype=torch.uint8, device=x.device)
+        rc = getattr(L, name)(C.byref(w), hip.ptr(self._ws), self._ws.numel(), hip.ptr(x), hip.ptr(out), N, R, chunk, hip.stream_ptr(x.device))
+        hip.check(rc, name)
+        return out
 
     # ---- encode
     @torch.no_grad()
@@ -339,14 +338,7 @@ class AutoencoderKL(nn.Module):
         w, _ = self._packed_enc or self._pack_enc()
         x = x.contiguous().float()
         N, R = x.shape[0], x.shape[2] // 8
-        chunk = min(self.decode_chunk or max(1, (64 * 32 * 32) // (R * R)), N, self._max_chunk(R))
-        L = hip.lib()
-        need = L.lfm_vae_workspace_bytes(R, chunk)
-        if self._ws is None or self._ws.numel() < need or self._ws.device != x.device:
-            self._ws = torch.empty(need, dtype=torch.uint8, device=x.device)
-        moments = torch.empty(N, 8, R, R, device=x.device, dtype=torch.float32)
-        rc = L.lfm_vae_encode(C.byref(w), hip.ptr(self._ws), self._ws.numel(), hip.ptr(x), hip.ptr(moments), N, R, chunk, hip.stream_ptr(x.device))
-        hip.check(rc, "lfm_vae_encode")
+        moments = self._run("lfm_vae_encode", w, x, R, torch.empty(N, 8, R, R, device=x.device, dtype=torch.float32))
         dist = DiagonalGaussianDistribution(moments)
         return AutoencoderKLOutput(dist) if return_dict else (dist,)
 
@@ -359,17 +351,7 @@ class AutoencoderKL(nn.Module):
         w, _ = self._packed or self._pack()
         z = z.contiguous().float()
         N, R = z.shape[0], z.shape[2]
-        # images per pass: bigger is faster (57.9 ms vs 65.9 ms per 64 images for 64 vs 16 at 256x256) and bounded by the
-        # 4 ping-pong activation buffers: auto = 64 images at 256x256 (8.6 GB), scaled by resolution (16 at 512x512)
-        chunk = self.decode_chunk or max(1, (64 * 32 * 32) // (R * R))
-        chunk = min(chunk, N, self._max_chunk(R))
-        L = hip.lib()
-        need = L.lfm_vae_workspace_bytes(R, chunk)
-        if self._ws is None or self._ws.numel() < need or self._ws.device != z.device:
-            self._ws = torch.empty(need, dtype=torch.uint8, device=z.device)
-        out = torch.empty(N, 3, 8 * R, 8 * R, device=z.device, dtype=torch.float32)
-        rc = L.lfm_vae_decode(C.byref(w), hip.ptr(self._ws), self._ws.numel(), hip.ptr(z), hip.ptr(out), N, R, chunk, hip.stream_ptr(z.device))
-        hip.check(rc, "lfm_vae_decode")
+        out = self._run("lfm_vae_decode", w, z, R, torch.empty(N, 3, 8 * R, 8 * R, device=z.device, dtype=torch.float32))
         return DecoderOutput(out) if return_dict else (out,)
 
     def forward(self, z):

@@ -289,3 +289,15 @@ inline __global__ __launch_bounds__(256) void gn_stats_rows_kernel(GnIn in, floa
 static inline bool conv_halo_allowed(const void* out = nullptr, const void* resid = nullptr) {
   return lfm_gemm_selected() == 0 && !(lfm_gemm_debug_flags() & LFM_DBG_CONV_IMPLICIT_GEMM) && !(((uintptr_t)out | (uintptr_t)resid) & 15);
 }
+
+// The <= 4-channel output convolution (fp16 NHWC -> fp32 NCHW; w4 fp16 [4][9][Cin]) of the UNets and the VAE decoder: the halo-tiled kernel, or the
+// implicit GEMM on four columns where that one declines.  zeros: the caller's zero page.  (fp32 scalar stores: no alignment term in the gate.)
+static inline int launch_conv3x3_out(const half_t* in, const half_t* zeros, const half_t* w4, int N, int H, int W, int Cin, const EpiNCHWF32& eo,
+                                     hipStream_t st) {
+  if (conv_halo_allowed()) {
+    const int rc = launch_conv3x3_halo_out(in, zeros, w4, N, H, W, Cin, eo, st);
+    if (rc != 1) return rc;
+  }
+  const int M = N * H * W;
+  return launch_gemm_tn(ASrcConv<0>{in, zeros, H, W, Cin, M}, w4, 9L * Cin, M, 4, 9 * Cin, eo, st);
+}

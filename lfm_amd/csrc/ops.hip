@@ -106,13 +106,7 @@ extern "C" int lfm_conv3x3_out_f32(const void* in, const void* w4, const float* 
   if (N <= 0 || Cin % 64 || nch < 1 || nch > 4) return LFM_ERR_SHAPE;
   const half_t* z = zero_page();
   if (!z) return LFM_ERR_LAUNCH;
-  const int M = N * H * W;
-  const EpiNCHWF32 eo{out_nchw, bias4, H * W, nch};
-  if (conv_halo_allowed()) {  // (fp32 scalar stores: no alignment term)
-    const int rc = launch_conv3x3_halo_out((const half_t*)in, z, (const half_t*)w4, N, H, W, Cin, eo, (hipStream_t)stream);
-    if (rc != 1) return rc;
-  }
-  return launch_gemm_tn(ASrcConv<0>{(const half_t*)in, z, H, W, Cin, M}, (const half_t*)w4, 9L * Cin, M, 4, 9 * Cin, eo, (hipStream_t)stream);
+  return launch_conv3x3_out((const half_t*)in, z, (const half_t*)w4, N, H, W, Cin, EpiNCHWF32{out_nchw, bias4, H * W, nch}, (hipStream_t)stream);
 }
 
 static int linear_f16_impl(const void* A, long lda, const void* W, long ldw, void* C, long ldc, int M, int N, int K, const float* bias, const void* resid,

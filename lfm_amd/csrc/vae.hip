@@ -199,47 +199,74 @@ __global__ __launch_bounds__(256) void softmax_rows_kernel(const float* __restri
 static inline size_t a256(size_t v) { return (v + 255) / 256 * 256; }
 
 struct VaeWs {
-  half_t *b0, *b1, *b2, *b3;  // four ping-pong activation buffers of the largest size
-  float* stats;               // [chunk, 32, 2] {mean, rstd}
-  float* part;                // [chunk, VGN_MAX_SLABS, 128, 2] partial {mean, M2} of the two-stage GroupNorm statistics
-  half_t* zeros;              // 256 B
-  float* S;                   // [chunk, T, T] scores
-  size_t part_pairs;          // capacity of `part` in {mean, M2} pairs
-  size_t total;
+  half_t* b[4];       // four rotating activation buffers of the largest size
+  float* stats;       // [images, 32, 2] {mean, rstd}
+  float* part;        // [images, slabs, C / 4, 2] partial {mean, M2} of the two-stage GroupNorm statistics
+  half_t* zeros;      // 256 B
+  float* S;           // [images, T, T] scores
+  size_t part_pairs;  // capacity of `part` in {mean, M2} pairs
 };
 
-static VaeWs vae_carve(int R, int chunk, void* ws) {
-  // largest activation: 128 ch at 8R x 8R  ==  256 ch at 4R x 4R x 2 ... = chunk * (8R)^2 * 128 halves;
-  // the upsample conv of block 2 writes 256 ch at 8R x 8R: chunk * (8R)^2 * 256 halves -> size for that.
-  const size_t act = (size_t)chunk * (8 * R) * (8 * R) * 256 * 2;
-  const size_t T = (size_t)R * R;
+// What one call needs of its workspace.  Every entry point describes itself with one of these, vae_carve lays it out, and gn reads part_pairs from
+// it: the description alone decides how many statistics slabs a GroupNorm picks, so a stage entry point that gives part_pairs the decoder's value
+// sums in the decoder's order.
+struct VaeNeed {
+  size_t buf_bytes;    // each of the four rotating buffers (0: none)
+  size_t images;       // stats holds {mean, rstd} of 32 groups for this many images (0: none)
+  size_t part_pairs;   // room for partial statistics in {mean, M2} pairs (0: none, ws.part stays null and no convolution leaves statistics)
+  size_t score_bytes;  // the mid attention's fp32 scores (0: none)
+};
+
+static inline size_t max_sz(size_t a, size_t b) { return a > b ? a : b; }
+
+// lfm_vae_decode / lfm_vae_encode, `chunk` images per pass.  The largest activation is the upsample convolution's 256 channels at 8R x 8R.  part: per image
+// the larger of the convolution epilogues' 128-row slabs (2 HW / 256 x C / 4 half-octets, at most (8R)^2 x 256 / 512) and the statistics pass's
+// VGN_MAX_SLABS x 128.  A last, shorter pass keeps the room of `chunk` images (gn may then pick more slabs per image).
+static VaeNeed vae_need_coder(int R, int chunk) {
+  const size_t px = (size_t)(8 * R) * (8 * R), T = (size_t)R * R, c = (size_t)chunk;
+  return {c * px * 256 * 2, c, c * max_sz(px * 256 / 512, (size_t)VGN_MAX_SLABS * 128), c * T * T * 4};
+}
+// The mid-block attention alone: the buffers hold Q | K and V^T | P (n T (512 + max(512, T)) halves), part is the decoder's share per image at R^2 = T.
+static VaeNeed vae_need_attention(int n, int T) {
+  const size_t M = (size_t)n * T;
+  return {M * (512 + max_sz(T, 512)) * 2, (size_t)n, n * max_sz(32 * (size_t)T, (size_t)VGN_MAX_SLABS * 128), M * T * 4};
+}
+// A run of resnets up to 512 channels wide: part as in the decoder, with the epilogue slabs of a ragged map rounded up.
+static VaeNeed vae_need_resnets(int n, int HW) {
+  return {(size_t)n * HW * 512 * 2, (size_t)n, n * max_sz(2 * (size_t)cdiv(HW, 256) * 128, (size_t)VGN_MAX_SLABS * 128), 0};
+}
+// The two GroupNorm entry points: part is what the caller's bytes leave after stats and the zero page, in whole 256-byte pieces (32 pairs: every
+// count gn compares it with or divides it by is a multiple of 32).  Below `least_pairs` the description asks for that much, which no longer fits
+// into the caller's bytes: vae_setup answers LFM_ERR_WORKSPACE.
+static VaeNeed vae_need_gn(int n, size_t bytes, size_t least_pairs) {
+  const size_t fixed = 256 + a256((size_t)n * 256), room = bytes > fixed ? (bytes - fixed) / 256 * 32 : 0;
+  return {0, (size_t)n, max_sz(room, least_pairs), 0};
+}
+static const VaeNeed VAE_NEED_ZEROS{0, 0, 0, 0};  // the two bare convolutions: the zero page alone
+
+// The one layout: [four buffers][stats][part][zeros 256 B][scores], every piece rounded up to 256 bytes, an empty piece null.  Returns the total;
+// base null: sizes only.
+static size_t vae_carve(const VaeNeed& d, void* base, VaeWs* w) {
   size_t off = 0;
-  char* base = (char*)ws;
   auto take = [&](size_t bytes) {
-    char* p = base ? base + off : nullptr;
+    char* p = base && bytes ? (char*)base + off : nullptr;
     off += a256(bytes);
     return p;
   };
-  VaeWs w;
-  w.b0 = (half_t*)take(act);
-  w.b1 = (half_t*)take(act);
-  w.b2 = (half_t*)take(act);
-  w.b3 = (half_t*)take(act);
-  w.stats = (float*)take((size_t)chunk * 64 * 4);
-  // the larger of: the statistics kernel's slabs (VGN_MAX_SLABS x C / 4 <= 128 half-octets) and the convolution epilogues' 128-row slabs
-  // (2 HW / 256 per image x C / 4 half-octets: at most (8R)^2 * 256 / 512 for the 256-channel tensor at full resolution)
-  const size_t part_conv = (size_t)(8 * R) * (8 * R) * 256 / 512, part_stats = (size_t)VGN_MAX_SLABS * 128;
-  w.part_pairs = (size_t)chunk * (part_conv > part_stats ? part_conv : part_stats);
-  w.part = (float*)take(w.part_pairs * 2 * 4);
-  w.zeros = (half_t*)take(256);
-  w.S = (float*)take((size_t)chunk * T * T * 4);
-  w.total = off;
-  return w;
+  VaeWs o{};
+  for (half_t*& b : o.b) b = (half_t*)take(d.buf_bytes);
+  o.stats = (float*)take(d.images * 64 * 4);
+  o.part = (float*)take(d.part_pairs * 2 * 4);
+  o.part_pairs = d.part_pairs;
+  o.zeros = (half_t*)take(256);
+  o.S = (float*)take(d.score_bytes);
+  if (w) *w = o;
+  return off;
 }
 
 extern "C" size_t lfm_vae_workspace_bytes(int R, int chunk) {
   if (R <= 0 || chunk <= 0 || (R % 8)) return 0;
-  return vae_carve(R, chunk, nullptr).total;
+  return vae_carve(vae_need_coder(R, chunk), nullptr, nullptr);
 }
 
 #define RC(x)            \
@@ -255,8 +282,20 @@ struct VaeConv {  // a 3x3 convolution layer: w fp16 [Cout][9][Cin], b fp32 [Cou
   bool ups;
 };
 
+struct VaeAttn {  // the mid-block attention's parameters, as lfm_vae_weights and lfm_vae_enc_weights hold them
+  const float *at_g, *at_b;
+  const void* q_w;
+  const float* q_b;
+  const void* k_w;
+  const float* k_b;
+  const void* v_w;
+  const float* v_b;
+  const void* o_w;
+  const float* o_b;
+};
+
 // The host driver's state for n images: the carve, the stream, the four rotating activation buffers (x holds the current tensor) and what is known
-// about x.  The test entry points fill only ws.zeros / stats / part / part_pairs and call gn and conv3 with their own buffers.
+// about x.  vae_setup makes it; the entry points whose description has no buffers call gn and conv3 with the caller's tensors.
 struct VaeCtx {
   VaeWs ws;
   int n;
@@ -273,9 +312,19 @@ struct VaeCtx {
   int conv3(const half_t* in, half_t* out, const half_t* resid, int H, int W, const VaeConv& c, int* stat_slabs, int* stat_kernel = nullptr) const;
   int conv_down(const void* w, const float* b, int Ho, int Wo, int C);
   int resnet(const lfm_vae_resnet* r, int H, int W);
-  template <class W>
-  int mid_attention(const W* w, int T);
+  int mid_attention(const VaeAttn& w, int T);
 };
+
+// The set-up of every entry point with a workspace, after its own argument checks: refuse a misaligned workspace, then one too short for `need`; carve; zero
+// the zero page (once per call, the first thing enqueued); hand back the state for n images.  Nothing is enqueued before the last refusal.
+static int vae_setup(const VaeNeed& need, void* workspace, size_t bytes, int n, lfm_stream_t stream, bool chain_stats, VaeCtx& c) {
+  if ((uintptr_t)workspace & 255) return LFM_ERR_ALIGN;
+  if (vae_carve(need, nullptr, nullptr) > bytes) return LFM_ERR_WORKSPACE;
+  VaeWs ws;
+  vae_carve(need, workspace, &ws);
+  c = VaeCtx{ws, n, (hipStream_t)stream, ws.b[0], ws.b[1], ws.b[2], ws.b[3], 0, chain_stats};
+  return lfm_zero_async(ws.zeros, 256, c.st) ? LFM_ERR_LAUNCH : LFM_OK;
+}
 
 // y = silu?(GroupNorm(in) g + b).  ready_slabs > 0: the convolution that produced `in` already left its partial sums in ws.part (EpiConvStatsF16), in
 // that many slabs per image
@@ -354,30 +403,15 @@ int VaeCtx::conv3(const half_t* in, half_t* out, const half_t* resid, int H, int
 }
 
 // ---- test entry points: the decoder's GroupNorm (gn, its own statistics pass) and the conv3 -> gn hand-over, on the decoder's host code.
-// Workspace: [zeros 256 B][stats n x 32 x {mean, rstd}][part: the rest, in {mean, M2} pairs] (the decoder sizes part by lfm_vae_workspace_bytes;
-// gn takes as many statistics slabs as part has room for, as in the decoder).
-static int vae_test_ctx(void* workspace, size_t bytes, int n, lfm_stream_t stream, VaeCtx& c) {
-  if ((uintptr_t)workspace & 255) return LFM_ERR_ALIGN;
-  const size_t head = 256 + a256((size_t)n * 64 * 4);
-  if (bytes < head) return LFM_ERR_WORKSPACE;
-  c = VaeCtx{};
-  c.ws.zeros = (half_t*)workspace;
-  c.ws.stats = (float*)((char*)workspace + 256);
-  c.ws.part = (float*)((char*)workspace + head);
-  c.ws.part_pairs = (bytes - head) / 8;
-  c.n = n;
-  c.st = (hipStream_t)stream;
-  return LFM_OK;
-}
-
+// Workspace (vae_need_gn): stats for n images, the zero page, and part: the rest, in {mean, M2} pairs (the decoder sizes part by
+// lfm_vae_workspace_bytes; gn picks as many statistics slabs as part has room for, as in the decoder).
 extern "C" int lfm_vae_groupnorm_f16(const void* x, void* y, const float* gamma, const float* beta, void* workspace, size_t workspace_bytes, int n,
                                      int HW, int C, int silu, lfm_stream_t stream) {
   if (!x || !y || !gamma || !beta || !workspace) return LFM_ERR_ARG;
-  if (n <= 0 || HW <= 0 || C <= 0) return LFM_ERR_SHAPE;
+  if (n <= 0 || HW <= 0 || (C != 128 && C != 256 && C != 512)) return LFM_ERR_SHAPE;  // gn's own rule, ahead of the set-up's zero fill
   if (((uintptr_t)x | (uintptr_t)y) & 15) return LFM_ERR_ALIGN;
   VaeCtx c;
-  RC(vae_test_ctx(workspace, workspace_bytes, n, stream, c));
-  if (c.ws.part_pairs < (size_t)n * VGN_MAX_SLABS * (C / 4)) return LFM_ERR_WORKSPACE;
+  RC(vae_setup(vae_need_gn(n, workspace_bytes, (size_t)n * VGN_MAX_SLABS * (C / 4)), workspace, workspace_bytes, n, stream, false, c));
   return c.gn((const half_t*)x, (half_t*)y, gamma, beta, HW, C, silu != 0, 0);
 }
 
@@ -387,11 +421,9 @@ extern "C" int lfm_vae_conv3x3_gn_f16(const void* in, const void* w, const float
   if (!in || !w || !bias || !conv_out || !y || !gamma || !beta || !workspace) return LFM_ERR_ARG;
   if (n <= 0 || H <= 0 || W <= 0 || (ups && ((H | W) & 1))) return LFM_ERR_SHAPE;
   if (((uintptr_t)in | (uintptr_t)w | (uintptr_t)resid | (uintptr_t)conv_out | (uintptr_t)y) & 15) return LFM_ERR_ALIGN;
-  VaeCtx c;
-  RC(vae_test_ctx(workspace, workspace_bytes, n, stream, c));
   const size_t conv_pairs = (size_t)n * 2 * (H * W / 256) * (Cout / 4), stat_pairs = (size_t)n * VGN_MAX_SLABS * (Cout / 4);
-  if (c.ws.part_pairs < (conv_pairs > stat_pairs ? conv_pairs : stat_pairs)) return LFM_ERR_WORKSPACE;
-  if (lfm_zero_async(c.ws.zeros, 256, c.st)) return LFM_ERR_LAUNCH;
+  VaeCtx c;
+  RC(vae_setup(vae_need_gn(n, workspace_bytes, max_sz(conv_pairs, stat_pairs)), workspace, workspace_bytes, n, stream, false, c));
   int slabs = 0, kern = 0;
   RC(c.conv3((const half_t*)in, (half_t*)conv_out, (const half_t*)resid, H, W, VaeConv{w, bias, Cin, Cout, ups != 0}, &slabs, &kern));
   RC(c.gn((const half_t*)conv_out, (half_t*)y, gamma, beta, H * W, Cout, silu != 0, slabs));
@@ -419,78 +451,34 @@ int VaeCtx::resnet(const lfm_vae_resnet* r, int H, int W) {
 }
 
 // mid-block attention (diffusers Attention, 1 head of 512 channels over T tokens, residual): GroupNorm -> q, k, v -> softmax(q k^T / sqrt(C)) v
-// -> to_out + x, all on the GEMM kernel.  x is replaced by the result (buffers rotate).  W: lfm_vae_weights / lfm_vae_enc_weights name the fields alike.
-template <class W>
-int VaeCtx::mid_attention(const W* w, int T) {
+// -> to_out + x, all on the GEMM kernel.  x is replaced by the result (buffers rotate).
+int VaeCtx::mid_attention(const VaeAttn& w, int T) {
   const int M = n * T, C = 512;
-  RC(gn(x, t1, w->at_g, w->at_b, T, C, false, x_slabs));
+  RC(gn(x, t1, w.at_g, w.at_b, T, C, false, x_slabs));
   half_t* Qb = t2;                  // [M, C]
   half_t* Kb = t2 + (size_t)M * C;  // [M, C]
   half_t* Vt = t3;                  // [n, C, T]
   half_t* Pb = t3 + (size_t)M * C;  // [n, T, T]
   const ASrcRowMajor a{t1, C, M, 0};
-  RC(launch_gemm_tn(a, (const half_t*)w->q_w, C, M, C, C, EpiResidF16{Qb, C, w->q_b, nullptr}, st));
-  RC(launch_gemm_tn(a, (const half_t*)w->k_w, C, M, C, C, EpiResidF16{Kb, C, w->k_b, nullptr}, st));
-  RC(launch_gemm_tn(a, (const half_t*)w->v_w, C, M, C, C, EpiTransposeF16{Vt, w->v_b, T, C}, st));
+  RC(launch_gemm_tn(a, (const half_t*)w.q_w, C, M, C, C, EpiResidF16{Qb, C, w.q_b, nullptr}, st));
+  RC(launch_gemm_tn(a, (const half_t*)w.k_w, C, M, C, C, EpiResidF16{Kb, C, w.k_b, nullptr}, st));
+  RC(launch_gemm_tn(a, (const half_t*)w.v_w, C, M, C, C, EpiTransposeF16{Vt, w.v_b, T, C}, st));
   RC(launch_gemm_tn(ASrcRowMajor{Qb, C, T, 0}, Kb, C, T, T, C, EpiBatchF32{ws.S, T}, st, n, (long)T * C, (long)T * C, (long)T * T));
   hipLaunchKernelGGL(softmax_rows_kernel, dim3(cdiv((long)n * T, 4)), dim3(256), 0, st, ws.S, Pb, (long)n * T, T, 1.4426950408889634f / sqrtf((float)C));
   LFM_CHECK_LAUNCH();
   half_t* Ob = t1;  // GN output is dead now
   RC(launch_gemm_tn(ASrcRowMajor{Pb, T, T, 0}, Vt, T, T, C, T, EpiBatchF16{Ob, C}, st, n, (long)T * T, (long)C * T, (long)T * C));
-  RC(launch_gemm_tn(ASrcRowMajor{Ob, C, M, 0}, (const half_t*)w->o_w, C, M, C, C, EpiResidF16{t2, C, w->o_b, x}, st));
+  RC(launch_gemm_tn(ASrcRowMajor{Ob, C, M, 0}, (const half_t*)w.o_w, C, M, C, C, EpiResidF16{t2, C, w.o_b, x}, st));
   x_slabs = 0;
   rotate(t2);
   return LFM_OK;
 }
 
-// ---- test entry point: the decoder's mid-block attention on the caller's weights.  Workspace: [zeros 256 B][stats n x 32 x {mean, rstd}][part: the
-// decoder's share per image at R^2 = T, n x max(32 T, VGN_MAX_SLABS x 128) pairs, so the GroupNorm picks the slab count it picks in a decode]
-// [four rotating buffers, each n T (512 + max(512, T)) halves: Q | K, and V^T | P, are the largest tenants][S: n x T x T fp32].
-struct VaeAttnTestWeights {  // the fields mid_attention reads, named as in lfm_vae_weights / lfm_vae_enc_weights
-  const float *at_g, *at_b;
-  const void* q_w;
-  const float* q_b;
-  const void* k_w;
-  const float* k_b;
-  const void* v_w;
-  const float* v_b;
-  const void* o_w;
-  const float* o_b;
-};
-
-static size_t vae_attn_test_carve(int n, int T, void* ws, VaeCtx* c) {
-  const size_t M = (size_t)n * T, buf = M * (512 + (T > 512 ? (size_t)T : 512)) * 2;
-  const size_t part_pairs = (size_t)n * (32 * (size_t)T > (size_t)VGN_MAX_SLABS * 128 ? 32 * (size_t)T : (size_t)VGN_MAX_SLABS * 128);
-  size_t off = 0;
-  char* base = (char*)ws;
-  auto take = [&](size_t bytes) {
-    char* p = base ? base + off : nullptr;
-    off += a256(bytes);
-    return p;
-  };
-  half_t* zeros = (half_t*)take(256);
-  float* stats = (float*)take((size_t)n * 64 * 4);
-  float* part = (float*)take(part_pairs * 8);
-  half_t* b[4];
-  for (int i = 0; i < 4; ++i) b[i] = (half_t*)take(buf);
-  float* S = (float*)take(M * T * 4);
-  if (c) {
-    c->ws.zeros = zeros;
-    c->ws.stats = stats;
-    c->ws.part = part;
-    c->ws.part_pairs = part_pairs;
-    c->ws.S = S;
-    c->x = b[0];
-    c->t1 = b[1];
-    c->t2 = b[2];
-    c->t3 = b[3];
-  }
-  return off;
-}
-
+// ---- test entry point: the decoder's mid-block attention on the caller's weights.  Workspace: vae_need_attention, so the GroupNorm picks the slab
+// count it picks in a decode at R^2 = T.
 extern "C" size_t lfm_vae_mid_attention_workspace_bytes(int n, int T) {
   if (n <= 0 || T <= 0 || (T % 64)) return 0;
-  return vae_attn_test_carve(n, T, nullptr, nullptr);
+  return vae_carve(vae_need_attention(n, T), nullptr, nullptr);
 }
 
 extern "C" int lfm_vae_mid_attention_f16(const void* x, void* out, const float* gn_gamma, const float* gn_beta, const void* q_w, const float* q_b,
@@ -502,17 +490,11 @@ extern "C" int lfm_vae_mid_attention_f16(const void* x, void* out, const float* 
   if (((uintptr_t)x | (uintptr_t)out | (uintptr_t)q_w | (uintptr_t)k_w | (uintptr_t)v_w | (uintptr_t)o_w | (uintptr_t)gn_gamma | (uintptr_t)gn_beta |
        (uintptr_t)q_b | (uintptr_t)k_b | (uintptr_t)v_b | (uintptr_t)o_b) & 15)
     return LFM_ERR_ALIGN;
-  if ((uintptr_t)workspace & 255) return LFM_ERR_ALIGN;
-  if (workspace_bytes < vae_attn_test_carve(n, T, nullptr, nullptr)) return LFM_ERR_WORKSPACE;
-  VaeCtx c{};
-  vae_attn_test_carve(n, T, workspace, &c);
-  c.n = n;
-  c.st = (hipStream_t)stream;
-  c.x_slabs = 0;
+  VaeCtx c;
+  RC(vae_setup(vae_need_attention(n, T), workspace, workspace_bytes, n, stream, false, c));
   const size_t bytes = (size_t)n * T * 512 * 2;
   if (hipMemcpyAsync(c.x, x, bytes, hipMemcpyDeviceToDevice, c.st) != hipSuccess) return LFM_ERR_LAUNCH;
-  const VaeAttnTestWeights w{gn_gamma, gn_beta, q_w, q_b, k_w, k_b, v_w, v_b, o_w, o_b};
-  RC(c.mid_attention(&w, T));
+  RC(c.mid_attention(VaeAttn{gn_gamma, gn_beta, q_w, q_b, k_w, k_b, v_w, v_b, o_w, o_b}, T));
   if (hipMemcpyAsync(out, c.x, bytes, hipMemcpyDeviceToDevice, c.st) != hipSuccess) return LFM_ERR_LAUNCH;
   return LFM_OK;
 }
@@ -544,7 +526,7 @@ static int vae_decode_chunk(VaeCtx& c, const lfm_vae_weights* w, const float* z,
   RC(vae_conv_in(w->pq_w, w->pq_b, w->cin_w, w->cin_b, z, c.x, c.n, R, c.st));
   int H = R;
   RC(c.resnet(&w->mid[0], H, H));
-  RC(c.mid_attention(w, R * R));
+  RC(c.mid_attention(VaeAttn{w->at_g, w->at_b, w->q_w, w->q_b, w->k_w, w->k_b, w->v_w, w->v_b, w->o_w, w->o_b}, R * R));
   RC(c.resnet(&w->mid[1], H, H));
   for (int i = 0; i < 4; ++i) {
     for (int j = 0; j < 3; ++j) RC(c.resnet(&w->up[i][j], H, H));
@@ -556,25 +538,18 @@ static int vae_decode_chunk(VaeCtx& c, const lfm_vae_weights* w, const float* z,
     }
   }
   RC(c.gn(c.x, c.t1, w->no_g, w->no_b, H * H, 128, true, c.x_slabs));
-  const int M = c.n * H * H;
-  const EpiNCHWF32 eo{out, w->cout_b, H * H, 3};
-  int rc = 1;
-  if (conv_halo_allowed()) rc = launch_conv3x3_halo_out(c.t1, c.ws.zeros, (const half_t*)w->cout_w, c.n, H, H, 128, eo, c.st);
-  if (rc == 1) rc = launch_gemm_tn(ASrcConv<0>{c.t1, c.ws.zeros, H, H, 128, M}, (const half_t*)w->cout_w, 9L * 128, M, 4, 9 * 128, eo, c.st);
-  return rc;
+  return launch_conv3x3_out(c.t1, c.ws.zeros, (const half_t*)w->cout_w, c.n, H, H, 128, EpiNCHWF32{out, w->cout_b, H * H, 3}, c.st);
 }
 
 extern "C" int lfm_vae_decode(const lfm_vae_weights* w, void* workspace, size_t workspace_bytes, const float* z, float* out, int N, int R,
                               int chunk, lfm_stream_t stream) {
   if (!w || !workspace || !z || !out) return LFM_ERR_ARG;
   if (N <= 0 || R <= 0 || (R % 8) || chunk <= 0) return LFM_ERR_SHAPE;
-  const VaeWs ws = vae_carve(R, chunk, workspace);
-  if (ws.total > workspace_bytes) return LFM_ERR_WORKSPACE;
-  if ((uintptr_t)workspace & 255) return LFM_ERR_ALIGN;
-  hipStream_t st = (hipStream_t)stream;
-  if (lfm_zero_async(ws.zeros, 256, st)) return LFM_ERR_LAUNCH;
+  VaeCtx first;  // every pass starts from this state: the same buffers in the same roles, the room of `chunk` images
+  RC(vae_setup(vae_need_coder(R, chunk), workspace, workspace_bytes, chunk, stream, true, first));
   for (int n0 = 0; n0 < N; n0 += chunk) {
-    VaeCtx c{ws, (N - n0 < chunk) ? N - n0 : chunk, st, ws.b0, ws.b1, ws.b2, ws.b3, 0, true};
+    VaeCtx c = first;
+    if (N - n0 < chunk) c.n = N - n0;
     RC(vae_decode_chunk(c, w, z + (long)n0 * 4 * R * R, out + (long)n0 * 3 * 64 * R * R, R));
   }
   return LFM_OK;
@@ -610,78 +585,40 @@ static int vae_conv_moments(const half_t* in, const half_t* zeros, const void* w
 // host code.  Workspace of the two convolutions: 256 B of zeros (the padding rows of the gather).
 extern "C" size_t lfm_vae_downsample_workspace_bytes(int n, int Ho, int Wo, int C) {
   if (n <= 0 || Ho <= 0 || Wo <= 0 || C <= 0 || (C % 64) || 4L * n * Ho * Wo * C >= (1L << 31)) return 0;
-  return 256;
+  return vae_carve(VAE_NEED_ZEROS, nullptr, nullptr);
 }
 
 extern "C" int lfm_vae_downsample_f16(const void* x, const void* w, const float* bias, void* out, void* workspace, size_t workspace_bytes, int n, int Ho,
                                       int Wo, int C, lfm_stream_t stream) {
   if (!x || !w || !bias || !out || !workspace) return LFM_ERR_ARG;
-  const size_t need = lfm_vae_downsample_workspace_bytes(n, Ho, Wo, C);
-  if (!need) return LFM_ERR_SHAPE;
+  if (!lfm_vae_downsample_workspace_bytes(n, Ho, Wo, C)) return LFM_ERR_SHAPE;
   if (((uintptr_t)x | (uintptr_t)w | (uintptr_t)bias | (uintptr_t)out) & 15) return LFM_ERR_ALIGN;
-  if ((uintptr_t)workspace & 255) return LFM_ERR_ALIGN;
-  if (workspace_bytes < need) return LFM_ERR_WORKSPACE;
-  VaeCtx c{};
-  c.ws.zeros = (half_t*)workspace;
-  c.n = n;
-  c.st = (hipStream_t)stream;
+  VaeCtx c;
+  RC(vae_setup(VAE_NEED_ZEROS, workspace, workspace_bytes, n, stream, false, c));
   c.x = (half_t*)x;  // conv_down reads x and writes t1, then rotates: the result is in `out` and nothing is written to the caller's x
   c.t1 = (half_t*)out;
-  if (lfm_zero_async(c.ws.zeros, 256, c.st)) return LFM_ERR_LAUNCH;
   return c.conv_down(w, bias, Ho, Wo, C);
 }
 
 extern "C" size_t lfm_vae_conv_moments_workspace_bytes(int n, int H, int W) {
   if (n <= 0 || H <= 0 || W <= 0 || (long)n * H * W * 512 >= (1L << 31)) return 0;
-  return 256;
+  return vae_carve(VAE_NEED_ZEROS, nullptr, nullptr);
 }
 
 extern "C" int lfm_vae_conv_moments_f32(const void* in, const void* w8, const float* b8, float* moments, void* workspace, size_t workspace_bytes, int n,
                                         int H, int W, lfm_stream_t stream) {
   if (!in || !w8 || !b8 || !moments || !workspace) return LFM_ERR_ARG;
-  const size_t need = lfm_vae_conv_moments_workspace_bytes(n, H, W);
-  if (!need) return LFM_ERR_SHAPE;
+  if (!lfm_vae_conv_moments_workspace_bytes(n, H, W)) return LFM_ERR_SHAPE;
   if (((uintptr_t)in | (uintptr_t)w8 | (uintptr_t)b8 | (uintptr_t)moments) & 15) return LFM_ERR_ALIGN;
-  if ((uintptr_t)workspace & 255) return LFM_ERR_ALIGN;
-  if (workspace_bytes < need) return LFM_ERR_WORKSPACE;
-  if (lfm_zero_async(workspace, 256, (hipStream_t)stream)) return LFM_ERR_LAUNCH;
-  return vae_conv_moments((const half_t*)in, (const half_t*)workspace, w8, b8, moments, n, H, W, (hipStream_t)stream);
+  VaeCtx c;
+  RC(vae_setup(VAE_NEED_ZEROS, workspace, workspace_bytes, n, stream, false, c));
+  return vae_conv_moments((const half_t*)in, c.ws.zeros, w8, b8, moments, n, H, W, c.st);
 }
 
-// Workspace of the resnets: [zeros 256 B][stats n x 32 x {mean, rstd}][part: per image the larger of the convolution epilogues' slabs
-// (2 ceil(HW / 256) x Cmax / 4 pairs) and the statistics pass's (VGN_MAX_SLABS x 128)][four rotating buffers of n HW Cmax halves], Cmax = 512.
-static size_t vae_resnets_test_carve(int n, int HW, void* ws, VaeCtx* c) {
-  const size_t buf = (size_t)n * HW * 512 * 2;
-  const size_t conv_pairs = 2 * (size_t)cdiv(HW, 256) * 128, stat_pairs = (size_t)VGN_MAX_SLABS * 128;
-  const size_t part_pairs = (size_t)n * (conv_pairs > stat_pairs ? conv_pairs : stat_pairs);
-  size_t off = 0;
-  char* base = (char*)ws;
-  auto take = [&](size_t bytes) {
-    char* p = base ? base + off : nullptr;
-    off += a256(bytes);
-    return p;
-  };
-  half_t* zeros = (half_t*)take(256);
-  float* stats = (float*)take((size_t)n * 64 * 4);
-  float* part = (float*)take(part_pairs * 8);
-  half_t* b[4];
-  for (int i = 0; i < 4; ++i) b[i] = (half_t*)take(buf);
-  if (c) {
-    c->ws.zeros = zeros;
-    c->ws.stats = stats;
-    c->ws.part = part;
-    c->ws.part_pairs = part_pairs;
-    c->x = b[0];
-    c->t1 = b[1];
-    c->t2 = b[2];
-    c->t3 = b[3];
-  }
-  return off;
-}
-
+// Workspace of the resnets: vae_need_resnets.
 extern "C" size_t lfm_vae_resnets_workspace_bytes(int n, int H, int W) {
   if (n <= 0 || H <= 0 || W <= 0 || (long)n * H * W * 512 >= (1L << 31)) return 0;
-  return vae_resnets_test_carve(n, H * W, nullptr, nullptr);
+  return vae_carve(vae_need_resnets(n, H * W), nullptr, nullptr);
 }
 
 extern "C" int lfm_vae_resnets_f16(const lfm_vae_resnet* r, int n_res, const void* x, void* out, void* workspace, size_t workspace_bytes, int n, int H,
@@ -698,18 +635,10 @@ extern "C" int lfm_vae_resnets_f16(const lfm_vae_resnet* r, int n_res, const voi
     bits |= (uintptr_t)q.n1_g | (uintptr_t)q.n1_b | (uintptr_t)q.c1_w | (uintptr_t)q.c1_b | (uintptr_t)q.n2_g | (uintptr_t)q.n2_b | (uintptr_t)q.c2_w |
             (uintptr_t)q.c2_b | (uintptr_t)q.sc_w | (uintptr_t)q.sc_b;
   }
-  const size_t need = lfm_vae_resnets_workspace_bytes(n, H, W);
-  if (!need) return LFM_ERR_SHAPE;
+  if (!lfm_vae_resnets_workspace_bytes(n, H, W)) return LFM_ERR_SHAPE;
   if (bits & 15) return LFM_ERR_ALIGN;
-  if ((uintptr_t)workspace & 255) return LFM_ERR_ALIGN;
-  if (workspace_bytes < need) return LFM_ERR_WORKSPACE;
-  VaeCtx c{};
-  vae_resnets_test_carve(n, H * W, workspace, &c);
-  c.n = n;
-  c.st = (hipStream_t)stream;
-  c.x_slabs = 0;
-  c.chain_stats = chain_stats != 0;
-  if (lfm_zero_async(c.ws.zeros, 256, c.st)) return LFM_ERR_LAUNCH;
+  VaeCtx c;
+  RC(vae_setup(vae_need_resnets(n, H * W), workspace, workspace_bytes, n, stream, chain_stats != 0, c));
   if (hipMemcpyAsync(c.x, x, (size_t)n * H * W * r[0].cin * 2, hipMemcpyDeviceToDevice, c.st) != hipSuccess) return LFM_ERR_LAUNCH;
   for (int i = 0; i < n_res; ++i) RC(c.resnet(&r[i], H, W));
   if (hipMemcpyAsync(out, c.x, (size_t)n * H * W * r[n_res - 1].cout * 2, hipMemcpyDeviceToDevice, c.st) != hipSuccess) return LFM_ERR_LAUNCH;
@@ -729,7 +658,7 @@ static int vae_encode_chunk(VaeCtx& c, const lfm_vae_enc_weights* w, const float
     }
   }
   RC(c.resnet(&w->mid[0], H, H));
-  RC(c.mid_attention(w, H * H));
+  RC(c.mid_attention(VaeAttn{w->at_g, w->at_b, w->q_w, w->q_b, w->k_w, w->k_b, w->v_w, w->v_b, w->o_w, w->o_b}, H * H));
   RC(c.resnet(&w->mid[1], H, H));
   RC(c.gn(c.x, c.t1, w->no_g, w->no_b, H * H, 512, true, 0));
   return vae_conv_moments(c.t1, c.ws.zeros, w->cout_w, w->cout_b, moments, c.n, H, H, c.st);
@@ -739,13 +668,11 @@ extern "C" int lfm_vae_encode(const lfm_vae_enc_weights* w, void* workspace, siz
                               int chunk, lfm_stream_t stream) {
   if (!w || !workspace || !x || !moments) return LFM_ERR_ARG;
   if (N <= 0 || R <= 0 || (R % 8) || chunk <= 0) return LFM_ERR_SHAPE;
-  const VaeWs ws = vae_carve(R, chunk, workspace);
-  if (ws.total > workspace_bytes) return LFM_ERR_WORKSPACE;
-  if ((uintptr_t)workspace & 255) return LFM_ERR_ALIGN;
-  hipStream_t st = (hipStream_t)stream;
-  if (lfm_zero_async(ws.zeros, 256, st)) return LFM_ERR_LAUNCH;
+  VaeCtx first;  // as in lfm_vae_decode
+  RC(vae_setup(vae_need_coder(R, chunk), workspace, workspace_bytes, chunk, stream, false, first));
   for (int n0 = 0; n0 < N; n0 += chunk) {
-    VaeCtx c{ws, (N - n0 < chunk) ? N - n0 : chunk, st, ws.b0, ws.b1, ws.b2, ws.b3, 0, false};
+    VaeCtx c = first;
+    if (N - n0 < chunk) c.n = N - n0;
     RC(vae_encode_chunk(c, w, x + (long)n0 * 3 * 64 * R * R, moments + (long)n0 * 8 * R * R, R));
   }
   return LFM_OK;

@@ -237,3 +237,51 @@ def test_resnets_refusals(L):
             assert call(r=bad) == ARG, name
     assert call(x=ODD) == ALIGN and call(out=ODD) == ALIGN and call(ws=P + 16) == ALIGN
     assert call(nbytes=need - 1) == WORKSPACE
+
+
+# ------------------------------------------------------------------------------------------------ the carved workspaces (host arithmetic, no GPU)
+def a(v):
+    return (v + 255) // 256 * 256
+
+
+def coder_bytes(R, c):  # include/lfm_hip.h: lfm_vae_workspace_bytes
+    if R <= 0 or c <= 0 or R % 8:
+        return 0
+    return 4 * a(c * (8 * R) ** 2 * 512) + a(c * 256) + a(c * max((8 * R) ** 2 // 2, 8192) * 8) + 256 + a(c * R ** 4 * 4)
+
+
+def attention_bytes(n, T):  # lfm_vae_mid_attention_workspace_bytes
+    if n <= 0 or T <= 0 or T % 64:
+        return 0
+    return 256 + a(n * 256) + a(n * max(32 * T, 8192) * 8) + 4 * a(n * T * (512 + max(512, T)) * 2) + a(n * T * T * 4)
+
+
+def resnets_bytes(n, H, W):  # lfm_vae_resnets_workspace_bytes
+    if n <= 0 or H <= 0 or W <= 0 or n * H * W * 512 >= 2 ** 31:
+        return 0
+    return 256 + a(n * 256) + a(n * max(2 * -(-H * W // 256) * 128, 8192) * 8) + 4 * a(n * H * W * 512 * 2)
+
+
+def test_workspace_bytes_follow_the_header_formulas(L):
+    for R in (0, 4, 8, 16, 24, 32, 64):
+        for c in (0, 1, 2, 3, 8, 64):
+            assert L.lfm_vae_workspace_bytes(R, c) == coder_bytes(R, c), (R, c)
+    for n in (0, 1, 2, 3, 7):
+        for T in (0, 64, 100, 128, 576, 1024, 4096):
+            assert L.lfm_vae_mid_attention_workspace_bytes(n, T) == attention_bytes(n, T), (n, T)
+        for H, W in ((0, 4), (4, 4), (16, 16), (8, 24), (17, 5), (64, 64), (2048, 2048)):
+            assert L.lfm_vae_resnets_workspace_bytes(n, H, W) == resnets_bytes(n, H, W), (n, H, W)
+
+
+def test_decode_and_encode_refusals(L):
+    """Misaligned before short (a workspace that is both answers LFM_ERR_ALIGN), after the arguments and the shape."""
+    need = L.lfm_vae_workspace_bytes(8, 2)
+    assert need > 0
+    for f in (L.lfm_vae_decode, L.lfm_vae_encode):
+        assert f(P, P + 16, need, P, P, 3, 8, 2, None) == ALIGN
+        assert f(P, P, need - 1, P, P, 3, 8, 2, None) == WORKSPACE
+        assert f(P, P + 16, need - 1, P, P, 3, 8, 2, None) == ALIGN
+        for i in range(4):
+            assert f(*[None if j == i else P for j in range(2)], need, *[None if j == i else P for j in range(2, 4)], 3, 8, 2, None) == ARG, i
+        for bad in ((0, 8, 2), (3, 0, 2), (3, 12, 2), (3, 8, 0)):
+            assert f(P, P, need, P, P, *bad, None) == SHAPE, bad
