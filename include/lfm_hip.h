@@ -512,6 +512,22 @@ int lfm_layernorm_f16(const void* x, void* y, const float* gamma, const float* b
  * ldh elements apart, 2I columns used; y dense fp16 [M, I].  fp32 arithmetic, one rounding.  I % 8 == 0, ldh >= 2I (LFM_ERR_SHAPE); ldh % 8 == 0 and h, y
  * 16-byte aligned (LFM_ERR_ALIGN).  No workspace, graph-capturable. */
 int lfm_geglu_f16(const void* h, long ldh, void* y, long M, int I, lfm_stream_t stream);
+/* The two ops of the layout encoder (models/encoder.py:52-87 BERTEmbedder over models/x_transformer.py TransformerWrapper + Encoder) that the library did not
+ * have.  Additions to ABI 4.  Everything else of that encoder runs on entry points above: lfm_layernorm_f16, lfm_linear_f16 (the row-stacked to_q | to_k |
+ * to_v projection without bias into one [M, 3 * 512] buffer; to_out and net.2 with the residual) and lfm_cross_attention_f16 over the three column slices
+ * of that buffer (ldq = ldkv = 1536, Tq = Tk = L, 8 heads of 64) -- BERTEmbedder.forward passes no mask, so there is no mask argument.
+ *
+ * lfm_token_embed_f16: out[n*L + p][0..D) = fp16(tok_emb[ids[n*L + p]][:] + pos_emb[p][:]) (x_transformer.py:586-587).  tok_emb fp32 [vocab, D] and pos_emb
+ *   fp32 [pos_rows, D] dense; ids int64 [N*L] on the device; out dense fp16 [N*L, D].  The add is in fp32, one rounding to fp16.  D % 8 == 0 and L <= pos_rows
+ *   (LFM_ERR_SHAPE); the four pointers 16-byte aligned (LFM_ERR_ALIGN); both before any launch.  An id outside [0, vocab) (an IndexError in the reference)
+ *   poisons its row with NaN, as lfm_time_embed does for labels; the kernel never reads beyond a table.  No readback, no workspace: graph-capturable, and a
+ *   replay follows ids rewritten in place.
+ * lfm_linear_gelu_f16: C fp16 [M,N] = gelu(A W^T + bias) with the EXACT (erf) GELU of nn.GELU() -- x Phi(x) evaluated as 0.5 x erfc(-x / sqrt 2) in fp32 on the
+ *   accumulator, one rounding to fp16; not the tanh form of lfm_gemm_f16's GELU epilogue (timm's Mlp).  bias required (LFM_ERR_ARG).  Alignment, shapes and
+ *   kernel choice as lfm_linear_silu_f16. */
+int lfm_token_embed_f16(const float* tok_emb, int vocab, const float* pos_emb, int pos_rows, const void* ids_int64, void* out, int N, int L, int D,
+                        lfm_stream_t stream);
+int lfm_linear_gelu_f16(const void* A, long lda, const void* W, long ldw, void* C, long ldc, int M, int N, int K, const float* bias, lfm_stream_t stream);
 /* emb = time_embed(timestep_embedding(t, F)) (+ label_emb[y]) (nn.py:103-121, unet.py:633-641): fp32 [N,E] and fp16 silu(emb).
  * label_table has label_rows rows; a label outside [0, label_rows) (an IndexError in the reference) poisons its row with NaN. */
 int lfm_time_embed(const float* t, int t_len, const float* w0, const float* b0, const float* w2, const float* b2, const float* label_table,

@@ -110,6 +110,11 @@ __device__ __forceinline__ f32x2_t gelu_tanh_pk(f32x2_t x) {
 // tests/test_host_logic.py::test_no_packed_fp32_op_sel disassembles the built code objects and keeps every op_sel'd packed-fp32 form out of the library.
 // (Plain C, not inline asm: sixteen asm statements per pass pushed the one-wave-per-SIMD QKV kernel's accumulator view into scratch memory.)
 __device__ __forceinline__ float fma_v(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
+
+// The EXACT GELU g Phi(g) of F.gelu's default and nn.GELU() (GEGLU of the SpatialTransformer: token_ops.h; FeedForward of the layout encoder: ActGeluErf in
+// gemm_epilogues.h), written 0.5 g erfc(-g / sqrt 2): erfc keeps its relative accuracy where 1 + erf(g / sqrt 2) cancels (negative arguments).  Not
+// gelu_tanh_f above, which is the tanh form of timm's Mlp.
+__device__ __forceinline__ float gelu_erf_f(float g) { return 0.5f * g * erfcf(-0.70710678118654752f * g); }
 // a * acc + (b * u + v), four columns of one row.  Packed again, but only in the SAFE form: a and b are first pinned into registers of their own (the empty
 // asm), so that the compiler broadcasts each as the LOW register of a pair -- v_pk_fma_f32 .. op_sel_hi:[0,1,1], both halves read the low register -- and
 // never reaches into the high register of the (a, b) pair for the low half (op_sel:[1,..]).  In round 4's events the op_sel_hi-broadcast FMA of the same

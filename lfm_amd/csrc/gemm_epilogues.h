@@ -41,6 +41,9 @@ struct ActGeluTanh {  // two elements at a time on the packed-fp32 VALU (common.
 struct ActSilu {  // x * sigmoid(x) in fp32 on the accumulator (silu_f, common.h: v_exp_f32 + v_rcp_f32), element by element: EDM FeedForward (models/EDM.py:438)
   static __device__ __forceinline__ f32x4 apply(f32x4 v) { return (f32x4){silu_f(v.x), silu_f(v.y), silu_f(v.z), silu_f(v.w)}; }
 };
+struct ActGeluErf {  // the exact GELU of nn.GELU() in fp32 on the accumulator (gelu_erf_f, common.h: 0.5 g erfc(-g / sqrt 2)), element by element: x_transformer FeedForward (models/encoder.py)
+  static __device__ __forceinline__ f32x4 apply(f32x4 v) { return (f32x4){gelu_erf_f(v.x), gelu_erf_f(v.y), gelu_erf_f(v.z), gelu_erf_f(v.w)}; }
+};
 
 // ------------------------------------------------------------------ bias epilogues
 template <class Act>
@@ -66,6 +69,7 @@ struct EpiBiasF16 : EpiBiasActF16<ActIdentity> {  // C = acc + bias -> fp16; bia
 };
 struct EpiBiasGeluF16 : EpiBiasActF16<ActGeluTanh> {};  // C = gelu_tanh(acc + bias) -> fp16   (timm Mlp fc1, DiT.py:123-124)
 struct EpiBiasSiluF16 : EpiBiasActF16<ActSilu> {};      // C = silu(acc + bias) -> fp16   (EDM FeedForward.layer0, models/EDM.py:438)
+struct EpiBiasGeluErfF16 : EpiBiasActF16<ActGeluErf> {};  // C = gelu_erf(acc + bias) -> fp16   (x_transformer FeedForward net.0, models/encoder.py)
 
 struct EpiBiasF32 {  // C = acc + bias -> fp32   (adaLN modulation table)
   float* C;

@@ -165,6 +165,14 @@ extern "C" int lfm_linear_silu_f16(const void* A, long lda, const void* W, long 
   return launch_gemm_auto(ASrcRowMajor{(const half_t*)A, lda, M, 0}, (const half_t*)W, ldw, M, N, K, EpiBiasSiluF16{{(half_t*)C, ldc, bias}},
                           (hipStream_t)stream);
 }
+// C = gelu_erf(A W^T + bias): net.0 of the layout encoder's FeedForward (nn.Linear + nn.GELU(), the exact form); in fp32 on the accumulator, one rounding to fp16
+extern "C" int lfm_linear_gelu_f16(const void* A, long lda, const void* W, long ldw, void* C, long ldc, int M, int N, int K, const float* bias,
+                                   lfm_stream_t stream) {
+  if (!A || !W || !C || !bias) return LFM_ERR_ARG;
+  if ((lda % 8) || (ldw % 8) || (ldc % 4) || (((uintptr_t)A | (uintptr_t)W) & 15)) return LFM_ERR_ALIGN;
+  return launch_gemm_auto(ASrcRowMajor{(const half_t*)A, lda, M, 0}, (const half_t*)W, ldw, M, N, K, EpiBiasGeluErfF16{{(half_t*)C, ldc, bias}},
+                          (hipStream_t)stream);
+}
 
 // out[r][0 .. cols) = table[y[r]][0 .. cols): the rows of the stacked context table (one per TransformerBlock, column-wise) that this batch's labels name.
 // Plain 16-byte loads and stores, no host readback: safe under capture, and a replay follows labels rewritten in place.  A label outside [0, rows) is

@@ -7,7 +7,12 @@
 // apply); it is at most a few KiB and the second and third reads come from the cache of the CU that made the first, so no register image bounds C.
 //
 // GEGLU: y[m][i] = h[m][i] * gelu(h[m][I + i]) with the EXACT GELU g Phi(g) of F.gelu's default, written 0.5 g erfc(-g / sqrt 2): erfc keeps its relative
-// accuracy where 1 + erf(g / sqrt 2) cancels (negative gates).  The library's gelu_tanh_f is the tanh form of another model and is not this function.
+// accuracy where 1 + erf(g / sqrt 2) cancels (negative gates): gelu_erf_f of common.h, shared with the GEMM epilogue ActGeluErf.  The library's gelu_tanh_f is
+// the tanh form of another model and is not this function.
+//
+// Token + position embedding of the layout encoder (x_transformer.py:586-587, TransformerWrapper: token_emb(ids) + pos_emb(arange(L))): lfm_token_embed_f16,
+// one 8-column chunk per thread, fp32 tables, one fp32 add, one rounding to fp16.  The ids are read on the device (no readback: a captured replay follows ids
+// rewritten in place); an id outside the table poisons its row with NaN and reads nothing.
 #pragma once
 #include "common.h"
 
@@ -60,8 +65,6 @@ extern "C" int lfm_layernorm_f16(const void* x, void* y, const float* gamma, con
   return LFM_OK;
 }
 
-__device__ __forceinline__ float gelu_erf_f(float g) { return 0.5f * g * erfcf(-0.70710678118654752f * g); }
-
 __global__ __launch_bounds__(256) void geglu_kernel(const half_t* __restrict__ h, long ldh, half8_t* __restrict__ y, int I8, long total) {
   const long e = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (e >= total) return;
@@ -82,6 +85,45 @@ extern "C" int lfm_geglu_f16(const void* h, long ldh, void* y, long M, int I, lf
   const long total = M * (I / 8);
   if ((total + 255) / 256 >= (1L << 31)) return LFM_ERR_SHAPE;
   hipLaunchKernelGGL(geglu_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (const half_t*)h, ldh, (half8_t*)y, I / 8, total);
+  LFM_CHECK_LAUNCH();
+  return LFM_OK;
+}
+
+__global__ __launch_bounds__(256) void token_embed_kernel(const float* __restrict__ tok, int vocab, const float* __restrict__ pos, const long long* __restrict__ ids,
+                                                          half8_t* __restrict__ out, int L, int D8, long total) {
+  const long e = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= total) return;
+  const long m = e / D8;  // row n * L + p
+  const int c = (int)(e - m * D8);
+  const int p = (int)(m % L);
+  const long long id = ids[m];
+  half8_t o;
+  if (id < 0 || id >= vocab) {  // nn.Embedding raises in the reference; poison instead of reading out of bounds
+    const half_t nan = (half_t)__builtin_nanf("");
+#pragma unroll
+    for (int i = 0; i < 8; ++i) o[i] = nan;
+  } else {
+    const float* tr = tok + (id * D8 + c) * 8;
+    const float* pr = pos + ((long)p * D8 + c) * 8;
+    const f32x4 t0 = *(const f32x4*)tr, t1 = *(const f32x4*)(tr + 4), p0 = *(const f32x4*)pr, p1 = *(const f32x4*)(pr + 4);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      o[i] = (half_t)(t0[i] + p0[i]);
+      o[4 + i] = (half_t)(t1[i] + p1[i]);
+    }
+  }
+  out[e] = o;
+}
+
+extern "C" int lfm_token_embed_f16(const float* tok_emb, int vocab, const float* pos_emb, int pos_rows, const void* ids_int64, void* out, int N, int L, int D,
+                                   lfm_stream_t stream) {
+  if (!tok_emb || !pos_emb || !ids_int64 || !out) return LFM_ERR_ARG;
+  if (vocab <= 0 || pos_rows <= 0 || N <= 0 || L <= 0 || D <= 0 || D % 8 || L > pos_rows) return LFM_ERR_SHAPE;
+  if ((((uintptr_t)tok_emb | (uintptr_t)pos_emb | (uintptr_t)ids_int64 | (uintptr_t)out) & 15)) return LFM_ERR_ALIGN;
+  const long total = (long)N * L * (D / 8);
+  if ((total + 255) / 256 >= (1L << 31)) return LFM_ERR_SHAPE;
+  hipLaunchKernelGGL(token_embed_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, tok_emb, vocab, pos_emb,
+                     (const long long*)ids_int64, (half8_t*)out, L, D / 8, total);
   LFM_CHECK_LAUNCH();
   return LFM_OK;
 }

@@ -197,6 +197,10 @@ def lib():
     L.lfm_linear_resid_vec_f16.argtypes = [V, LG, V, LG, V, LG, I, I, I, V, V, V, LG, I, F, V]
     L.lfm_linear_silu_f16.restype = I
     L.lfm_linear_silu_f16.argtypes = [V, LG, V, LG, V, LG, I, I, I, V, V]
+    L.lfm_linear_gelu_f16.restype = I
+    L.lfm_linear_gelu_f16.argtypes = [V, LG, V, LG, V, LG, I, I, I, V, V]
+    L.lfm_token_embed_f16.restype = I
+    L.lfm_token_embed_f16.argtypes = [V, I, V, I, V, V, I, I, I, V]
     L.lfm_gather_rows_f32.restype = I
     L.lfm_gather_rows_f32.argtypes = [V, I, I, V, I, V, LG, V]
     L.lfm_song_embed.restype = I
@@ -251,10 +255,11 @@ def ptr(t):
     return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
 
 
-def check_labels(y, rows, what):
+def check_labels(y, rows, what, noun="label", table="the embedding table",
+                 hint=" (classifier-free guidance needs a model built with label_dropout > 0: its null class is row num_classes)"):
     """Labels must index the embedding table (the reference's nn.Embedding raises IndexError otherwise; a kernel cannot).  The check
     reads two scalars back from the device, so the verdict is remembered ON THE TENSOR OBJECT (attribute, keyed by its version counter and
-    the table size) -- a solver loop that passes the same label tensor to every evaluation pays once, while a fresh tensor that merely
+    the table size; `noun` / `table` / `hint` word the message for other index tensors: the layout encoder's tokens) -- a solver loop that passes the same label tensor to every evaluation pays once, while a fresh tensor that merely
     reuses a freed tensor's address is checked again.  Skipped during graph capture (no readback possible there)."""
     if y is None or y.numel() == 0:
         return
@@ -265,8 +270,7 @@ def check_labels(y, rows, what):
         return
     lo, hi = (int(v) for v in torch.stack([y.min(), y.max()]).tolist())  # one readback
     if lo < 0 or hi >= rows:
-        raise IndexError(f"{what}: label {hi if hi >= rows else lo} is outside the embedding table [0, {rows}) "
-                         "(classifier-free guidance needs a model built with label_dropout > 0: its null class is row num_classes)")
+        raise IndexError(f"{what}: {noun} {hi if hi >= rows else lo} is outside {table} [0, {rows}){hint}")
     try:
         y._lfm_labels_ok = key
     except Exception:  # noqa
@@ -554,6 +558,38 @@ def linear_silu(x, w, bias, out=None):
         out = torch.empty(M, N, dtype=torch.float16, device=x.device)
     check(lib().lfm_linear_silu_f16(ptr(x), x.stride(0), ptr(w), w.stride(0), ptr(out), out.stride(0), M, N, K, ptr(bias), stream_ptr(x.device)),
           "lfm_linear_silu_f16")
+    return out
+
+
+def linear_gelu(x, w, bias, out=None):
+    """lfm_linear_gelu_f16: fp16 gelu(x w^T + bias) with the exact (erf) GELU in fp32 on the accumulator; rows of x / w / out may be strided."""
+    require_gpu(x, "linear_gelu")
+    M, K = x.shape
+    N = w.shape[0]
+    if out is None:
+        out = torch.empty(M, N, dtype=torch.float16, device=x.device)
+    check(lib().lfm_linear_gelu_f16(ptr(x), x.stride(0), ptr(w), w.stride(0), ptr(out), out.stride(0), M, N, K, ptr(bias), stream_ptr(x.device)),
+          "lfm_linear_gelu_f16")
+    return out
+
+
+def token_embed(tok_emb, pos_emb, ids, out=None):
+    """lfm_token_embed_f16: fp16 (tok_emb[ids] + pos_emb[:L]) as rows [N*L, D]; tables dense fp32 [vocab, D] / [pos_rows, D], ids contiguous int64 [N, L] on
+    the device.  No readback (capturable); an id outside the table gives a NaN row."""
+    require_gpu(tok_emb, "token_embed")
+    vocab, D = tok_emb.shape
+    N, L = ids.shape
+    for name, t in (("tok_emb", tok_emb), ("pos_emb", pos_emb)):
+        if t.dtype != torch.float32 or t.dim() != 2 or t.shape[1] != D or not t.is_contiguous() or t.device != tok_emb.device:
+            raise LfmHipError(f"token_embed: {name} must be dense fp32 [rows, {D}] on {tok_emb.device}, got {t.dtype} {tuple(t.shape)} on {t.device}")
+    if ids.dtype != torch.int64 or not ids.is_contiguous() or ids.device != tok_emb.device:
+        raise LfmHipError(f"token_embed: ids must be contiguous int64 on {tok_emb.device}, got {ids.dtype} on {ids.device}")
+    if out is None:
+        out = torch.empty(N * L, D, dtype=torch.float16, device=tok_emb.device)
+    if out.dtype != torch.float16 or tuple(out.shape) != (N * L, D) or not out.is_contiguous():
+        raise LfmHipError(f"token_embed: out must be dense fp16 [{N * L}, {D}], got {out.dtype} {tuple(out.shape)} strides {out.stride()}")
+    check(lib().lfm_token_embed_f16(ptr(tok_emb), vocab, ptr(pos_emb), pos_emb.shape[0], ptr(ids), ptr(out), N, L, D, stream_ptr(tok_emb.device)),
+          "lfm_token_embed_f16")
     return out
 
 

@@ -55,4 +55,13 @@ def get_flow_model(config):
     )
 
 
-__all__ = ["create_network", "get_flow_model", "DiT", "DiT_models"]
+def __getattr__(name):
+    """``lfm_amd.models.BERTEmbedder`` (the layout encoder, models/encoder.py), imported on first use like the UNets: a DiT-only user loads nothing more."""
+    if name == "BERTEmbedder":
+        from .encoder import BERTEmbedder
+
+        return BERTEmbedder
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
+
+
+__all__ = ["create_network", "get_flow_model", "DiT", "DiT_models", "BERTEmbedder"]
