@@ -528,6 +528,20 @@ int lfm_geglu_f16(const void* h, long ldh, void* y, long M, int I, lfm_stream_t 
 int lfm_token_embed_f16(const float* tok_emb, int vocab, const float* pos_emb, int pos_rows, const void* ids_int64, void* out, int N, int L, int D,
                         lfm_stream_t stream);
 int lfm_linear_gelu_f16(const void* A, long lda, const void* W, long ldw, void* C, long ldc, int M, int N, int K, const float* bias, lfm_stream_t stream);
+/* The conditioning stage of mask-to-image synthesis (downstream_tasks/test_flow_latent_semantic_syn.py:131-135: F.one_hot -> SpatialRescaler, models/encoder.py:
+ * 90-112: n_stages x F.interpolate(scale_factor=0.5, mode="bilinear") -> the 1x1 channel_mapper) as one gather (csrc/label_rescale.h).  Addition to ABI 4.
+ *   out[n][o][i][j] = (sum over the 2^n x 2^n cell (i, j) of w[o][labels[n][y][x]]) / 4^n_stages (+ bias[o])
+ * which is that chain exactly: a bilinear x0.5 stage at align_corners=False is a 2x2 mean, and the means of a 0/1 map are exact in fp32.
+ * labels int64 [N,H,W] dense; w fp32 [Cout,num_cls] dense (channel_mapper.weight as stored); bias fp32 [Cout] or NULL; out fp32 NCHW
+ * [N,Cout,H >> n_stages,W >> n_stages] dense.  Any H, W >= 2^n_stages, odd and non-square included: rows and columns beyond the last whole cell are not read.
+ * Refused before any launch, in this order: labels, w or out NULL (LFM_ERR_ARG); N < 1, n_stages outside 1..4, Cout outside 1..8, num_cls < 1,
+ * num_cls * Cout * 4 > 65536 (the table lives in the LDS), H or W < 2^n_stages (LFM_ERR_SHAPE); labels not 8-byte, w / bias / out not 4-byte aligned
+ * (LFM_ERR_ALIGN).  Labels 16-byte aligned with W even are read two per load; the result does not depend on that, nor on N or an image's place in the batch:
+ * per cell the pixel columns are summed top to bottom, then combined by a binary tree, adjacent columns first.  A label outside [0, num_cls) (an error of
+ * F.one_hot in the reference) makes the Cout outputs of ITS cell NaN and is not used as an index.  No readback, no workspace, no atomics: graph-capturable,
+ * and a replay follows labels rewritten in place. */
+int lfm_label_rescale_f32(const void* labels_int64, const float* w, const float* bias, float* out, int N, int H, int W, int num_cls, int Cout, int n_stages,
+                          lfm_stream_t stream);
 /* emb = time_embed(timestep_embedding(t, F)) (+ label_emb[y]) (nn.py:103-121, unet.py:633-641): fp32 [N,E] and fp16 silu(emb).
  * label_table has label_rows rows; a label outside [0, label_rows) (an IndexError in the reference) poisons its row with NaN. */
 int lfm_time_embed(const float* t, int t_len, const float* w0, const float* b0, const float* w2, const float* b2, const float* label_table,

@@ -5,6 +5,11 @@ latent + 1 mask; 8 for semantic synthesis: 4 state + 4 rescaled label map).
 Drop-in for /root/reference/downstream_tasks/test_flow_latent_inpainting.py:58-91 and test_flow_latent_semantic_syn.py:33-67
 (``sample_from_model``, ``WrapperCondFlow``); the velocity field is the origin-ADM ``UNetModel`` on the HIP path
 (``models.get_flow_model`` with ``num_in_channels`` 9 / 8, ``num_out_channels`` 4).
+
+Drivers: ``python -m lfm_amd.downstream_tasks.test_flow_latent_inpainting`` and ``python -m lfm_amd.downstream_tasks.flow_latent_semantic_syn``.  The
+mask-to-image driver is a module of its own beside the sampler file ``test_flow_latent_semantic_syn.py`` (``SpatialRescaler``, ``synthesize_batch``), which
+keeps its text: ``flow_latent_semantic_syn`` holds the same two names extended (``SpatialRescaler.encode_labels``, ``synthesize_batch(..., cond_path=)``)
+and is the module to import them from.
 """
 import torch
 from torch import nn

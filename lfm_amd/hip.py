@@ -203,6 +203,8 @@ def lib():
     L.lfm_token_embed_f16.argtypes = [V, I, V, I, V, V, I, I, I, V]
     L.lfm_gather_rows_f32.restype = I
     L.lfm_gather_rows_f32.argtypes = [V, I, I, V, I, V, LG, V]
+    L.lfm_label_rescale_f32.restype = I
+    L.lfm_label_rescale_f32.argtypes = [V, V, V, V, I, I, I, I, I, I, V]
     L.lfm_song_embed.restype = I
     L.lfm_song_embed.argtypes = [V, I, V, V, V, V, V, V, F, V, I, V, V, V, I, I, I, V]
     L.lfm_fourier_embed.restype = I
@@ -603,6 +605,37 @@ def gather_rows(table, y, out=None):
     if out is None:
         out = torch.empty(y.numel(), cols, device=table.device)
     check(lib().lfm_gather_rows_f32(ptr(table), rows, cols, ptr(y), y.numel(), ptr(out), out.stride(0), stream_ptr(table.device)), "lfm_gather_rows_f32")
+    return out
+
+
+LABEL_RESCALE_MAX_STAGES, LABEL_RESCALE_MAX_COUT, LABEL_RESCALE_TABLE_BYTES = 4, 8, 65536  # include/lfm_hip.h: lfm_label_rescale_f32
+
+
+def label_rescale_serves(num_cls, cout, n_stages):
+    """The limits of lfm_label_rescale_f32 that do not depend on the label map."""
+    return 1 <= n_stages <= LABEL_RESCALE_MAX_STAGES and 1 <= cout <= LABEL_RESCALE_MAX_COUT and num_cls >= 1 and num_cls * cout * 4 <= LABEL_RESCALE_TABLE_BYTES
+
+
+def label_rescale(labels, w, bias, n_stages, out=None):
+    """lfm_label_rescale_f32: out[n, o, i, j] = mean over the 2^n x 2^n cell of w[o, labels[n, y, x]] (+ bias[o]); labels contiguous int64 [N, H, W] on the
+    device, w dense fp32 [Cout, num_cls], bias fp32 [Cout] or None, out fp32 [N, Cout, H >> n, W >> n].  No readback (capturable); a label outside
+    [0, num_cls) gives a NaN cell."""
+    require_gpu(labels, "label_rescale")
+    if labels.dtype != torch.int64 or labels.dim() != 3 or not labels.is_contiguous():
+        raise LfmHipError(f"label_rescale: labels must be contiguous int64 [N, H, W], got {labels.dtype} {tuple(labels.shape)} strides {labels.stride()}")
+    N, H, W = labels.shape
+    if w.dtype != torch.float32 or w.dim() != 2 or not w.is_contiguous() or w.device != labels.device:
+        raise LfmHipError(f"label_rescale: w must be dense fp32 [Cout, num_cls] on {labels.device}, got {w.dtype} {tuple(w.shape)} on {w.device}")
+    cout, num_cls = w.shape
+    if bias is not None and (bias.dtype != torch.float32 or tuple(bias.shape) != (cout,) or not bias.is_contiguous() or bias.device != labels.device):
+        raise LfmHipError(f"label_rescale: bias must be dense fp32 [{cout}] on {labels.device}, got {bias.dtype} {tuple(bias.shape)} on {bias.device}")
+    shape = (N, cout, H >> n_stages, W >> n_stages)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=labels.device)
+    if out.dtype != torch.float32 or tuple(out.shape) != shape or not out.is_contiguous() or out.device != labels.device:
+        raise LfmHipError(f"label_rescale: out must be dense fp32 {shape} on {labels.device}, got {out.dtype} {tuple(out.shape)} strides {out.stride()}")
+    check(lib().lfm_label_rescale_f32(ptr(labels), ptr(w), ptr(bias), ptr(out), N, H, W, num_cls, cout, int(n_stages), stream_ptr(labels.device)),
+          "lfm_label_rescale_f32")
     return out
 
 
