@@ -327,6 +327,10 @@ int lfm_vae_encode(const lfm_vae_enc_weights* w, void* workspace, size_t workspa
  * lfm_vae_groupnorm_f16: y = silu?(GroupNorm(x) * gamma + beta), x, y fp16 NHWC [n, HW, C], C in {128, 256, 512}; statistics by their own pass. */
 int lfm_vae_groupnorm_f16(const void* x, void* y, const float* gamma, const float* beta, void* workspace, size_t workspace_bytes, int n, int HW, int C,
                           int silu, lfm_stream_t stream);
+/* The statistics slabs per image lfm_vae_groupnorm_f16's own pass takes for this shape with a workspace of workspace_bytes (the decoder's slab policy:
+ * 64 at most, or up to 512 of at least 64 pixels when n < 16 and the room allows it); LFM_ERR_SHAPE / LFM_ERR_WORKSPACE exactly where that entry point
+ * refuses the shape / the workspace size.  No launch; usable without a GPU.  Addition to ABI 4. */
+int lfm_vae_groupnorm_plan(int n, int HW, int C, size_t workspace_bytes);
 /* conv_out = conv3x3(in (nearest-2x upsampled when ups)) + bias (+ resid), then y = silu?(GroupNorm(conv_out) * gamma + beta), as a decoder resnet
  * hands a convolution to its GroupNorm: w fp16 [Cout][9][Cin], H, W the output size.  Needs also n x 2 (H W / 256) x Cout / 4 pairs of room.
  * *stat_slabs = the statistics slabs per image the convolution left (0: the GroupNorm ran its own pass); *stat_kernel = 1 (halo-tiled convolution),
@@ -447,6 +451,11 @@ int lfm_gather_rows_f32(const float* table, int rows, int cols, const void* y_in
 size_t lfm_groupnorm_scratch_bytes(int N, int C);
 int lfm_groupnorm_f16(const void* x, void* y, const float* gamma, const float* beta, const float* film, long film_stride, void* scratch, int N,
                       int HW, int C, int groups, float eps, int silu, lfm_stream_t stream);
+/* Which kernels lfm_groupnorm_f16 runs for this shape under the calling thread's flags (csrc/groupnorm_dispatch.h: gn_choose): stats | apply << 4 with
+ * stats 1 = the fused small-map kernel, 2 = row-wise slabs, 3 / 4 = per-group slabs read 4 / 1 channels at a time; apply 1 = inside the fused kernel,
+ * 2 = a thread per channel octet, 3 = a thread per 16-byte chunk; LFM_ERR_SHAPE for a shape that is refused.  For lfm_groupnorm2_f16: the plan at
+ * C = Ca + Cb.  No launch; usable without a GPU.  Addition to ABI 4. */
+int lfm_groupnorm_plan(int N, int HW, int C, int groups);
 /* The same on the channel concat [xa (Ca channels) | xb (Cb channels)] read in place (groups may straddle the seam); y is dense [N*HW, Ca + Cb];
  * scratch: lfm_groupnorm_scratch_bytes(N, Ca + Cb).  Ca % 8 == Cb % 8 == 0.  Bit-identical to lfm_concat_channels_f16 + lfm_groupnorm_f16. */
 int lfm_groupnorm2_f16(const void* xa, int Ca, const void* xb, int Cb, void* y, const float* gamma, const float* beta, const float* film,

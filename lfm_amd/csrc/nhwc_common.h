@@ -1,9 +1,10 @@
 // NHWC-fp16 pieces that the VAE (vae.hip) and the UNet building blocks (ops.hip) share: the implicit-GEMM A source of a 3x3 convolution, the
-// "acc + bias (+ residual)" epilogues, the row-wise GroupNorm statistics kernel with the {mean, M2} slot arithmetic, and the gate in front of
-// the halo-tiled convolution kernels.
+// "acc + bias (+ residual)" epilogues (one of which leaves GroupNorm statistics: the slot arithmetic, the row-wise statistics kernel and the rest
+// of what the two GroupNorms share are groupnorm_common.h, included here), and the gate in front of the halo-tiled convolution kernels.
 #pragma once
 #include "gemm_dispatch.h"
 #include "conv_halo_kernel.h"
+#include "groupnorm_common.h"  // gn_slot (EpiConvStatsF16), gn_merge, gn_mean_rstd, GnIn, gn_walk, gn_stats_rows_kernel, GN_MAX_SLABS
 
 // ------------------------------------------------------------------ implicit-GEMM A source, NHWC fp16, 3x3
 // M = N*H*W output pixels, K = 9*Cin with k = tap*Cin + ci; the gather (shifted pixel rows, zero padding) is the per-lane source address.
@@ -138,23 +139,6 @@ struct EpiNCHWF32 {  // Cout <= 4 output conv (the VAE decoder's `.sample` image
   }
 };
 
-// ------------------------------------------------------------------ GroupNorm statistics: {mean, M2} slots
-// Deterministic two-stage statistics (the reference is deterministic; float atomics are not): every producer folds a slab of pixels into partial
-// {mean, M2} slots, a second kernel merges the slots of a group in a fixed order.  Both stages are shifted, so that offset data (|mean| >> std)
-// keeps its variance instead of losing it to the fp32 cancellation of sum(x^2) / n - mean^2.
-// The slot of sums taken around the shift k: s = sum (x - k), q = sum (x - k)^2 over 1 / rc values.
-__device__ __forceinline__ void gn_slot(float* o, float k, float s, float q, float rc) {
-  o[0] = k + s * rc;
-  o[1] = fmaxf(q - s * s * rc, 0.f);
-}
-// One step of the merge, shifted by K (the group's first slot mean): slot {mean m, M2} of c values adds
-// sum (x - K) += c (m - K),  sum (x - K)^2 += M2 + c (m - K)^2 -- linear, so lanes and trees add as before.
-__device__ __forceinline__ void gn_merge(float& sum, float& sq, const float* slot, float c, float K) {
-  const float d = slot[0] - K;
-  sum += c * d;
-  sq += slot[1] + c * d * d;
-}
-
 // EpiResidF16 that also leaves the GroupNorm statistics of what it stores (round 3): the next layer of every VAE resnet is a GroupNorm over exactly
 // this tensor, and its statistics pass (gn_stats_rows_kernel) re-read it from HBM just to add it up.  In the row-major hand-over of the 256-row kernels
 // a lane owns the same eight output columns for all of its rows, so it keeps shifted sums of the ROUNDED fp16 values per half-octet (a group is >= 4
@@ -214,74 +198,6 @@ struct EpiConvStatsF16 {
     finish_slab(img, ((m0 - img * HW) >> 8) * 2 + g, n0 + wn * 64, lane);
   }
 };
-
-// GroupNorm input = the channel concat [a | b] of two NHWC tensors read in place (th.cat([h, hs.pop()], dim=1) feeding a ResBlock's first
-// GroupNorm, unet.py:649 + :171: the concatenated tensor is never materialised); b == nullptr: a alone (Ca == C).  Ca % 8 == 0.
-struct GnIn {
-  const half_t* a;
-  const half_t* b;
-  int Ca, Cb;
-  __device__ __forceinline__ const half_t* at(long pix, int c) const { return c < Ca ? a + pix * Ca + c : b + pix * Cb + (c - Ca); }
-  // a thread that owns channel c of every pixel of image n: first pixel's address and the row stride of the tensor that holds c
-  __device__ __forceinline__ const half_t* column(long pix0, int c, long& stride) const {
-    const bool fa = c < Ca;
-    stride = fa ? Ca : Cb;
-    return fa ? a + pix0 * Ca + c : b + pix0 * Cb + (c - Ca);
-  }
-};
-
-// Row-wise statistics (channels per group % 4 == 0, C / 8 <= 256): grid (slabs, images); a block reads a slab of pixels with FULL rows (coalesced);
-// thread = channel octet x pixel row; the sums are of x - k, k = the slab's first value of the half-octet (every thread of the octet reads the same
-// k); per half-octet partial sums are folded through LDS (fixed order) and leave as slot part[n][slab][C / 4 half-octets].
-inline __global__ __launch_bounds__(256) void gn_stats_rows_kernel(GnIn in, float* __restrict__ part, int HW, int C, int pix_per_block) {
-  __shared__ float red[4][256];
-  const int n = blockIdx.y, c8n = C / 8, tid = threadIdx.x;
-  const int rows = 256 / c8n;
-  const int oct = tid % c8n, prow = tid / c8n;
-  const int p0 = blockIdx.x * pix_per_block;
-  const int p1 = min(p0 + pix_per_block, HW);
-  float s[2] = {0.f, 0.f}, q[2] = {0.f, 0.f};  // per half-octet (4 channels): a group is >= 4 channels wide
-  long XS;  // row stride of the tensor that holds this thread's octet
-  const half_t* base = in.column((long)n * HW, oct * 8, XS);
-  const float k[2] = {(float)base[(long)p0 * XS], (float)base[(long)p0 * XS + 4]};  // the shifts: pixel p0 of this slab, per half-octet
-  if (prow < rows) {
-    auto add = [&](const half8_t& v) {
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const float f = (float)v[j] - k[j >> 2];
-        s[j >> 2] += f;
-        q[j >> 2] += f * f;
-      }
-    };
-    int p = p0 + prow;
-    for (; p + 3 * rows < p1; p += 4 * rows) {  // four independent loads in flight (one per iteration ran at 1.5 TB/s), summed in pixel order
-      const half8_t v0 = *(const half8_t*)(base + (long)p * XS), v1 = *(const half8_t*)(base + (long)(p + rows) * XS);
-      const half8_t v2 = *(const half8_t*)(base + (long)(p + 2 * rows) * XS), v3 = *(const half8_t*)(base + (long)(p + 3 * rows) * XS);
-      add(v0);
-      add(v1);
-      add(v2);
-      add(v3);
-    }
-    for (; p < p1; p += rows) add(*(const half8_t*)(base + (long)p * XS));
-  }
-  red[0][tid] = s[0];
-  red[1][tid] = s[1];
-  red[2][tid] = q[0];
-  red[3][tid] = q[1];
-  __syncthreads();
-  if (tid < c8n) {  // fold the pixel-rows of this channel octet, then one {mean, M2} slot per half-octet
-    for (int r = 1; r < rows; ++r) {
-      s[0] += red[0][tid + r * c8n];
-      s[1] += red[1][tid + r * c8n];
-      q[0] += red[2][tid + r * c8n];
-      q[1] += red[3][tid + r * c8n];
-    }
-    const float rc = 1.f / (float)((p1 - p0) * 4);
-    float* o = part + (((long)n * gridDim.x + blockIdx.x) * (C / 4) + tid * 2) * 2;
-    gn_slot(o, k[0], s[0], q[0], rc);
-    gn_slot(o + 2, k[1], s[1], q[1], rc);
-  }
-}
 
 // ------------------------------------------------------------------ halo kernel or implicit GEMM
 // May the halo-tiled kernels (conv_halo_kernel.h) be tried for this output / residual: the automatic kernel choice, 16-byte stores, and

@@ -5,7 +5,7 @@
 // k = tap*Cin + ci; the A-tile gather (shifted pixel rows, zero padding, optional nearest-2x upsample) is done
 // by the per-lane LDS-DMA source address.  GroupNorm statistics / apply+SiLU are bandwidth-bound side kernels.
 #include "../../include/lfm_hip.h"
-#include "nhwc_common.h"  // ASrcConv<MODE>, EpiResidF16, EpiConvStatsF16, EpiNCHWF32, gn_stats_rows_kernel, conv_halo_allowed
+#include "nhwc_common.h"  // ASrcConv<MODE>, EpiResidF16, EpiConvStatsF16, EpiNCHWF32, conv_halo_allowed; groupnorm_common.h
 
 // ------------------------------------------------------------------ epilogues (EpiResidF16, EpiConvStatsF16, EpiNCHWF32: nhwc_common.h)
 struct EpiTransposeF16 {  // per image: Ct[img][n][m % T] = acc + bias[n]   (V^T for the mid attention)
@@ -108,10 +108,11 @@ __global__ __launch_bounds__(256) void vae_conv_in_kernel(const float* __restric
 
 // ------------------------------------------------------------------ GroupNorm(32 groups, eps 1e-6) on NHWC fp16
 // Two-stage, deterministic statistics: the producing convolution's epilogue (EpiConvStatsF16) or a pass of its own (gn_stats_rows_kernel) folds
-// slabs of pixels into per-half-octet partial {mean, M2} slots part[n][slab][C/4] (nhwc_common.h: both shifted, so a group whose mean is hundreds
+// slabs of pixels into per-half-octet partial {mean, M2} slots part[n][slab][C/4] (groupnorm_common.h: both shifted, so a group whose mean is hundreds
 // of standard deviations keeps its variance); a small second kernel merges the slabs and the half-octets of a group in a fixed order into
-// stats[n][g] = {mean, rstd}; apply fuses SiLU.
-#define VGN_MAX_SLABS 64
+// stats[n][g] = {mean, rstd}; apply fuses SiLU.  The apply is ((x - mean) rstd) gamma + beta, the decoder's own rounding (constant groups come out
+// as exactly beta), which is why these two kernels are not the UNets' (groupnorm_kernels.h: x a + b); the slot arithmetic, the closing step, the
+// statistics kernel and the host constants are shared.
 // one WAVE per (image, group): lane l folds slabs l, l + 64, ... in order, then a fixed-tree wave sum (deterministic).  (One thread per
 // (image, group) walking all slabs serially took 75 us once the convolution epilogues started to deliver 512 slabs per image.)
 // Slot {mean m, M2} of slab b holds c = 4 min(ppb, HW - b ppb) values; the merge is shifted by the group's first slot mean K (gn_merge).
@@ -129,11 +130,7 @@ __global__ __launch_bounds__(256) void gn_finish_kernel(const float* __restrict_
   }
   sum = wave_sum(sum);
   sq = wave_sum(sq);
-  if (lane == 0) {
-    const float cnt = (float)HW * (float)(C / 32), dl = sum / cnt;
-    stats[(long)i * 2] = K + dl;
-    stats[(long)i * 2 + 1] = rsqrtf(fmaxf(sq / cnt - dl * dl, 0.f) + 1e-6f);
-  }
+  if (lane == 0) gn_mean_rstd(K, sum, sq, (float)HW * (float)(C / 32), 1e-6f, stats[(long)i * 2], stats[(long)i * 2 + 1]);
 }
 
 // apply: y = silu?((x - mean) rstd gamma + beta).  Round 4: a thread OWNS one channel octet (256 % (C / 8) == 0) and walks the pixels of its block's
@@ -169,7 +166,7 @@ __global__ __launch_bounds__(256) void gn_apply_kernel(const half_t* __restrict_
     return o;
   };
   int p = p0 + prow;
-  for (; p + 3 * pstride < p1; p += 4 * pstride) {  // four chunks in flight per thread
+  for (; p + 3 * pstride < p1; p += 4 * pstride) {  // four chunks in flight per thread (gn_walk's loop in its own text: see there)
     half8_t v[4];
 #pragma unroll
     for (int u = 0; u < 4; ++u) v[u] = *(const half8_t*)(x + base + (long)(p + u * pstride) * C);
@@ -221,19 +218,19 @@ static inline size_t max_sz(size_t a, size_t b) { return a > b ? a : b; }
 
 // lfm_vae_decode / lfm_vae_encode, `chunk` images per pass.  The largest activation is the upsample convolution's 256 channels at 8R x 8R.  part: per image
 // the larger of the convolution epilogues' 128-row slabs (2 HW / 256 x C / 4 half-octets, at most (8R)^2 x 256 / 512) and the statistics pass's
-// VGN_MAX_SLABS x 128.  A last, shorter pass keeps the room of `chunk` images (gn may then pick more slabs per image).
+// GN_MAX_SLABS x 128.  A last, shorter pass keeps the room of `chunk` images (gn may then pick more slabs per image).
 static VaeNeed vae_need_coder(int R, int chunk) {
   const size_t px = (size_t)(8 * R) * (8 * R), T = (size_t)R * R, c = (size_t)chunk;
-  return {c * px * 256 * 2, c, c * max_sz(px * 256 / 512, (size_t)VGN_MAX_SLABS * 128), c * T * T * 4};
+  return {c * px * 256 * 2, c, c * max_sz(px * 256 / 512, (size_t)GN_MAX_SLABS * 128), c * T * T * 4};
 }
 // The mid-block attention alone: the buffers hold Q | K and V^T | P (n T (512 + max(512, T)) halves), part is the decoder's share per image at R^2 = T.
 static VaeNeed vae_need_attention(int n, int T) {
   const size_t M = (size_t)n * T;
-  return {M * (512 + max_sz(T, 512)) * 2, (size_t)n, n * max_sz(32 * (size_t)T, (size_t)VGN_MAX_SLABS * 128), M * T * 4};
+  return {M * (512 + max_sz(T, 512)) * 2, (size_t)n, n * max_sz(32 * (size_t)T, (size_t)GN_MAX_SLABS * 128), M * T * 4};
 }
 // A run of resnets up to 512 channels wide: part as in the decoder, with the epilogue slabs of a ragged map rounded up.
 static VaeNeed vae_need_resnets(int n, int HW) {
-  return {(size_t)n * HW * 512 * 2, (size_t)n, n * max_sz(2 * (size_t)cdiv(HW, 256) * 128, (size_t)VGN_MAX_SLABS * 128), 0};
+  return {(size_t)n * HW * 512 * 2, (size_t)n, n * max_sz(2 * (size_t)cdiv(HW, 256) * 128, (size_t)GN_MAX_SLABS * 128), 0};
 }
 // The two GroupNorm entry points: part is what the caller's bytes leave after stats and the zero page, in whole 256-byte pieces (32 pairs: every
 // count gn compares it with or divides it by is a multiple of 32).  Below `least_pairs` the description asks for that much, which no longer fits
@@ -326,35 +323,42 @@ static int vae_setup(const VaeNeed& need, void* workspace, size_t bytes, int n, 
   return lfm_zero_async(ws.zeros, 256, c.st) ? LFM_ERR_LAUNCH : LFM_OK;
 }
 
+// The decoder's slab policy: {slabs per image, pixels per slab} of the statistics a GroupNorm of n images merges.  ready_slabs > 0: the convolution that
+// produced the tensor left that many (the epilogues: 128 pixels each).  Else the GroupNorm's own pass: GN_MAX_SLABS when the images fill the chip; a FEW
+// images (--measure_time decodes ONE) get up to 512 -- 64 blocks walked a 256x256x128 map in 64 dependent 16-byte loads per thread, 68 us per GroupNorm and
+// 38 % of the batch-1 decode (profiles/r06_latency_mode.txt) -- as far as ws.part has room (part_pairs = its capacity in pairs, 0 = unknown: the old cap).
+struct VaeGnSlabs {
+  int slabs, ppb;
+};
+static inline VaeGnSlabs vae_gn_slabs(int n, int HW, int C, size_t part_pairs, int ready_slabs) {
+  if (ready_slabs) return {ready_slabs, HW / ready_slabs};
+  int cap = GN_MAX_SLABS;
+  if (part_pairs && n * GN_MAX_SLABS < 1024) {
+    const long room = (long)(part_pairs / ((size_t)n * (C / 4)));
+    const long want = 1024 / n;
+    cap = (int)(want < room ? want : room);
+    if (cap > 512) cap = 512;
+    if (cap < GN_MAX_SLABS) cap = GN_MAX_SLABS;
+  }
+  int ppb = 1024;
+  if (cap > GN_MAX_SLABS) ppb = cdiv(HW, cap) > 64 ? cdiv(HW, cap) : 64;  // >= 64 pixels per block: at least a few loads per thread
+  if (cdiv(HW, ppb) > cap) ppb = cdiv(HW, cap);
+  return {cdiv(HW, ppb), ppb};
+}
+
 // y = silu?(GroupNorm(in) g + b).  ready_slabs > 0: the convolution that produced `in` already left its partial sums in ws.part (EpiConvStatsF16), in
 // that many slabs per image
 int VaeCtx::gn(const half_t* in, half_t* y, const float* g, const float* b, int HW, int C, bool silu, int ready_slabs) const {
   if (C % 128 || 256 % (C / 8) || C > 512) return LFM_ERR_SHAPE;  // groups of >= 4 channels, octet-per-thread mapping
-  int slabs = ready_slabs, ppb = ready_slabs ? HW / ready_slabs : 0;  // pixels per slab (the convolution epilogues: 128)
+  const VaeGnSlabs s = vae_gn_slabs(n, HW, C, ws.part_pairs, ready_slabs);
   if (!ready_slabs) {
-    // slabs per image: VGN_MAX_SLABS when the images fill the chip; a FEW images (--measure_time decodes ONE) get up to 512 -- 64 blocks walked a 256x256x128 map in
-    // 64 dependent 16-byte loads per thread, 68 us per GroupNorm and 38 % of the batch-1 decode (profiles/r06_latency_mode.txt) -- as far as ws.part has room
-    // (ws.part_pairs = its capacity in pairs, 0 = unknown: the old cap)
-    int cap = VGN_MAX_SLABS;
-    if (ws.part_pairs && n * VGN_MAX_SLABS < 1024) {
-      const long room = (long)(ws.part_pairs / ((size_t)n * (C / 4)));
-      const long want = 1024 / n;
-      cap = (int)(want < room ? want : room);
-      if (cap > 512) cap = 512;
-      if (cap < VGN_MAX_SLABS) cap = VGN_MAX_SLABS;
-    }
-    ppb = 1024;
-    if (cap > VGN_MAX_SLABS) ppb = cdiv(HW, cap) > 64 ? cdiv(HW, cap) : 64;  // >= 64 pixels per block: at least a few loads per thread
-    if (cdiv(HW, ppb) > cap) ppb = cdiv(HW, cap);
-    slabs = cdiv(HW, ppb);
-    hipLaunchKernelGGL(gn_stats_rows_kernel, dim3(slabs, n), dim3(256), 0, st, GnIn{in, nullptr, C, 0}, ws.part, HW, C, ppb);
+    hipLaunchKernelGGL(gn_stats_rows_kernel, dim3(s.slabs, n), dim3(256), 0, st, GnIn{in, nullptr, C, 0}, ws.part, HW, C, s.ppb);
     LFM_CHECK_LAUNCH();
   }
-  hipLaunchKernelGGL(gn_finish_kernel, dim3(cdiv(n * 32, 4)), dim3(256), 0, st, ws.part, ws.stats, slabs, ppb, HW, C, n * 32);
+  hipLaunchKernelGGL(gn_finish_kernel, dim3(cdiv(n * 32, 4)), dim3(256), 0, st, ws.part, ws.stats, s.slabs, s.ppb, HW, C, n * 32);
   LFM_CHECK_LAUNCH();
-  const int app = HW >= 4096 ? 256 : (HW >= 256 ? 64 : HW);  // pixels per block: 16 .. 4 chunks per thread at 128 .. 512 channels
-  if (silu) hipLaunchKernelGGL(gn_apply_kernel<true>, dim3(cdiv(HW, app), n), dim3(256), 0, st, in, y, ws.stats, g, b, HW, C, app);
-  else hipLaunchKernelGGL(gn_apply_kernel<false>, dim3(cdiv(HW, app), n), dim3(256), 0, st, in, y, ws.stats, g, b, HW, C, app);
+  const int app = gn_pixels_per_block(HW);
+  GN_LAUNCH_SILU(gn_apply_kernel, silu, dim3(cdiv(HW, app), n), st, in, y, ws.stats, g, b, HW, C, app);
   LFM_CHECK_LAUNCH();
   return LFM_OK;
 }
@@ -405,14 +409,24 @@ int VaeCtx::conv3(const half_t* in, half_t* out, const half_t* resid, int H, int
 // ---- test entry points: the decoder's GroupNorm (gn, its own statistics pass) and the conv3 -> gn hand-over, on the decoder's host code.
 // Workspace (vae_need_gn): stats for n images, the zero page, and part: the rest, in {mean, M2} pairs (the decoder sizes part by
 // lfm_vae_workspace_bytes; gn picks as many statistics slabs as part has room for, as in the decoder).
+static inline bool vae_groupnorm_shape_ok(int n, int HW, int C) { return n > 0 && HW > 0 && (C == 128 || C == 256 || C == 512); }  // gn's own rule
+static inline VaeNeed vae_need_groupnorm(int n, int C, size_t bytes) { return vae_need_gn(n, bytes, (size_t)n * GN_MAX_SLABS * (C / 4)); }
+
 extern "C" int lfm_vae_groupnorm_f16(const void* x, void* y, const float* gamma, const float* beta, void* workspace, size_t workspace_bytes, int n,
                                      int HW, int C, int silu, lfm_stream_t stream) {
   if (!x || !y || !gamma || !beta || !workspace) return LFM_ERR_ARG;
-  if (n <= 0 || HW <= 0 || (C != 128 && C != 256 && C != 512)) return LFM_ERR_SHAPE;  // gn's own rule, ahead of the set-up's zero fill
+  if (!vae_groupnorm_shape_ok(n, HW, C)) return LFM_ERR_SHAPE;  // ahead of the set-up's zero fill
   if (((uintptr_t)x | (uintptr_t)y) & 15) return LFM_ERR_ALIGN;
   VaeCtx c;
-  RC(vae_setup(vae_need_gn(n, workspace_bytes, (size_t)n * VGN_MAX_SLABS * (C / 4)), workspace, workspace_bytes, n, stream, false, c));
+  RC(vae_setup(vae_need_groupnorm(n, C, workspace_bytes), workspace, workspace_bytes, n, stream, false, c));
   return c.gn((const half_t*)x, (half_t*)y, gamma, beta, HW, C, silu != 0, 0);
+}
+// The slabs per image of that call's statistics pass, with its refusals of a shape and of a short workspace; no launch.
+extern "C" int lfm_vae_groupnorm_plan(int n, int HW, int C, size_t workspace_bytes) {
+  if (!vae_groupnorm_shape_ok(n, HW, C)) return LFM_ERR_SHAPE;
+  const VaeNeed need = vae_need_groupnorm(n, C, workspace_bytes);
+  if (vae_carve(need, nullptr, nullptr) > workspace_bytes) return LFM_ERR_WORKSPACE;
+  return vae_gn_slabs(n, HW, C, need.part_pairs, 0).slabs;
 }
 
 extern "C" int lfm_vae_conv3x3_gn_f16(const void* in, const void* w, const float* bias, const void* resid, void* conv_out, void* y, const float* gamma,
@@ -421,7 +435,7 @@ extern "C" int lfm_vae_conv3x3_gn_f16(const void* in, const void* w, const float
   if (!in || !w || !bias || !conv_out || !y || !gamma || !beta || !workspace) return LFM_ERR_ARG;
   if (n <= 0 || H <= 0 || W <= 0 || (ups && ((H | W) & 1))) return LFM_ERR_SHAPE;
   if (((uintptr_t)in | (uintptr_t)w | (uintptr_t)resid | (uintptr_t)conv_out | (uintptr_t)y) & 15) return LFM_ERR_ALIGN;
-  const size_t conv_pairs = (size_t)n * 2 * (H * W / 256) * (Cout / 4), stat_pairs = (size_t)n * VGN_MAX_SLABS * (Cout / 4);
+  const size_t conv_pairs = (size_t)n * 2 * (H * W / 256) * (Cout / 4), stat_pairs = (size_t)n * GN_MAX_SLABS * (Cout / 4);
   VaeCtx c;
   RC(vae_setup(vae_need_gn(n, workspace_bytes, max_sz(conv_pairs, stat_pairs)), workspace, workspace_bytes, n, stream, false, c));
   int slabs = 0, kern = 0;

@@ -161,6 +161,11 @@ def lib():
     L.lfm_groupnorm_f16.argtypes = [V, V, V, V, V, LG, V, I, I, I, I, F, I, V]
     L.lfm_groupnorm2_f16.restype = I
     L.lfm_groupnorm2_f16.argtypes = [V, I, V, I, V, V, V, V, LG, V, I, I, I, F, I, V]
+    if hasattr(L, "lfm_groupnorm_plan"):  # additions to ABI 4: an LFM_HIP_LIBRARY built before them (the parent of an A/B) still loads
+        L.lfm_groupnorm_plan.restype = I
+        L.lfm_groupnorm_plan.argtypes = [I, I, I, I]
+        L.lfm_vae_groupnorm_plan.restype = I
+        L.lfm_vae_groupnorm_plan.argtypes = [I, I, I, C.c_size_t]
     L.lfm_linear2_f16.restype = I
     L.lfm_linear2_f16.argtypes = [V, I, V, I, V, LG, V, LG, I, I, V, V, V]
     L.lfm_avgpool2_f16.restype = I
@@ -458,6 +463,23 @@ def conv3x3_plan(N, H, W, Cin, Cout, mode=0, workspace_bytes=0):
     """The path (1 halo-tiled kernel, 2 split-K + finish kernel, 3 one implicit GEMM; include/lfm_hip.h: lfm_conv3x3_plan) lfm_conv3x3_f16_ws takes for this
     shape with 16-byte-aligned operands and that much workspace under the calling thread's flags, or LFM_ERR_SHAPE (-1) (no launch, no GPU needed)."""
     return lib().lfm_conv3x3_plan(int(N), int(H), int(W), int(Cin), int(Cout), int(mode), int(workspace_bytes))
+
+
+GN_STATS_FUSED, GN_STATS_ROWS, GN_STATS_GROUPS4, GN_STATS_GROUPS1 = 1, 2, 3, 4  # lfm_groupnorm_plan: the statistics path
+GN_APPLY_FUSED, GN_APPLY_OCTET, GN_APPLY_CHUNK = 1, 2, 3  # and the apply path
+
+
+def groupnorm_plan(N, HW, C, groups):
+    """(statistics path GN_STATS_*, apply path GN_APPLY_*) of lfm_groupnorm_f16 for this shape under the calling thread's flags (include/lfm_hip.h:
+    lfm_groupnorm_plan, csrc/groupnorm_dispatch.h; lfm_groupnorm2_f16: C = Ca + Cb), or LFM_ERR_SHAPE (-1) (no launch, no GPU needed)."""
+    plan = lib().lfm_groupnorm_plan(int(N), int(HW), int(C), int(groups))
+    return plan if plan < 0 else (plan & 15, plan >> 4)
+
+
+def vae_groupnorm_plan(n, HW, C, workspace_bytes):
+    """The statistics slabs per image of lfm_vae_groupnorm_f16 for this shape and workspace size (include/lfm_hip.h: lfm_vae_groupnorm_plan), or
+    LFM_ERR_SHAPE (-1) / LFM_ERR_WORKSPACE (-3) as that entry point refuses (no launch, no GPU needed)."""
+    return lib().lfm_vae_groupnorm_plan(int(n), int(HW), int(C), int(workspace_bytes))
 
 
 def unet_attention_plan(N, T, heads, ch):

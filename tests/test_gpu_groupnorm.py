@@ -87,17 +87,23 @@ def with_flags(flags, fn):
 
 
 # ------------------------------------------------------------------ lfm_groupnorm_f16 (UNets)
-# (N, HW, C, groups, film, flags, path): fused = HW <= 1024 and cpg % 8 == 0; rows = cpg % 4 == 0 with HW > 1024 or flag UNET_GN_ROWS; groups = the rest
+# (N, HW, C, groups, film, flags, (statistics, apply) kernels the case is about -- asserted against lfm_groupnorm_plan before the launch; the rule itself
+# is stated once, in the header of csrc/groupnorm_dispatch.h --, label)
+FUSED = (hip.GN_STATS_FUSED, hip.GN_APPLY_FUSED)
+ROWS, GROUPS4, GROUPS1 = hip.GN_STATS_ROWS, hip.GN_STATS_GROUPS4, hip.GN_STATS_GROUPS1
+OCTET, CHUNK = hip.GN_APPLY_OCTET, hip.GN_APPLY_CHUNK
 UNET_CASES = [
-    (8, 1024, 256, 32, True, 0, "fused, ADM 32x32 level (boundary HW = 1024)"),
-    (3, 100, 512, 32, False, 0, "fused, ragged 10x10"),
-    (2, 64, 2048, 32, True, 0, "fused, 64-wide groups"),
-    (2, 4096, 128, 32, True, 0, "rows, ADM 64x64 level"),
-    (3, 1025, 256, 32, False, 0, "rows, ragged (boundary HW = 1025)"),
-    (4, 256, 512, 32, True, hip.DBG_UNET_GN_ROWS << 4, "rows via flag 16384"),
-    (2, 300, 96, 32, False, 0, "groups layout, cpg 3"),
-    (2, 4100, 96, 32, True, 0, "groups layout, ragged slabs"),
-    (1, 2048, 4096, 32, False, 0, "groups layout, cpg 128 (C / 8 > 256)"),
+    (8, 1024, 256, 32, True, 0, FUSED, "fused, ADM 32x32 level (boundary HW = 1024)"),
+    (3, 100, 512, 32, False, 0, FUSED, "fused, ragged 10x10"),
+    (2, 64, 2048, 32, True, 0, FUSED, "fused, 64-wide groups"),
+    (2, 4096, 128, 32, True, 0, (ROWS, OCTET), "rows, ADM 64x64 level"),
+    (3, 1025, 256, 32, False, 0, (ROWS, OCTET), "rows, ragged (boundary HW = 1025)"),
+    (4, 256, 512, 32, True, hip.DBG_UNET_GN_ROWS << 4, (ROWS, OCTET), "rows via flag 16384"),
+    (2, 300, 96, 32, False, 0, (GROUPS1, CHUNK), "groups layout, cpg 3"),
+    (2, 4100, 96, 32, True, 0, (GROUPS1, CHUNK), "groups layout, ragged slabs"),
+    (1, 2048, 4096, 32, False, 0, (GROUPS4, CHUNK), "groups layout, cpg 128 (C / 8 > 256)"),
+    (2, 300, 384, 32, False, 0, (ROWS, CHUNK), "rows, cpg 12, chunk apply (48 octets do not divide the block)"),
+    (2, 300, 64, 32, False, 0, (GROUPS1, OCTET), "groups layout, cpg 2, octet apply"),
 ]
 
 
@@ -106,7 +112,8 @@ UNET_CASES = [
 def test_groupnorm_f16_vs_fp64(case, fam):
     from lfm_amd import hip
 
-    N, HW, C_, groups, film_on, flags, what = case
+    N, HW, C_, groups, film_on, flags, kernels, what = case
+    assert with_flags(flags, lambda: hip.groupnorm_plan(N, HW, C_, groups)) == kernels  # the kernels this case is about really run
     dev = torch.device("cuda:0")
     L = hip.lib()
     x = family(fam, N, HW, C_, groups, seed=HW + C_, dev=dev)
@@ -129,10 +136,10 @@ def test_groupnorm_f16_vs_fp64(case, fam):
     # in the output -- 2e-3 at |mean| = 60, eps = 1e-5 -- so it is not silu(beta) to the fp16 rounding as the decoder's centred apply is, below.)
 
 
-TWO_SOURCE_CASES = [
-    (4, 256, 512, 256, True, "fused, groups straddle the seam"),
-    (2, 2048, 256, 128, False, "rows"),
-    (2, 512, 128, 64, True, "groups layout, groups straddle the seam"),
+TWO_SOURCE_CASES = [  # (N, HW, Ca, Cb, film, (statistics, apply) of the plan at C = Ca + Cb, label)
+    (4, 256, 512, 256, True, FUSED, "fused, groups straddle the seam"),
+    (2, 2048, 256, 128, False, (ROWS, CHUNK), "rows"),
+    (2, 512, 128, 64, True, (GROUPS1, CHUNK), "groups layout, groups straddle the seam"),
 ]
 
 
@@ -142,8 +149,9 @@ def test_groupnorm2_f16_offset_on_one_source(case, fam):
     """lfm_groupnorm2_f16 on [xa | xb] with the family on xa only (a group that straddles the seam mixes both)."""
     from lfm_amd import hip
 
-    N, HW, Ca, Cb, film_on, what = case
+    N, HW, Ca, Cb, film_on, kernels, what = case
     C_ = Ca + Cb
+    assert hip.groupnorm_plan(N, HW, C_, G) == kernels
     dev = torch.device("cuda:0")
     L = hip.lib()
     xa = family(fam, N, HW, C_, G, seed=HW + Ca, dev=dev)[..., :Ca].contiguous()  # the family's groups as the concat sees them, cut at the seam
@@ -171,15 +179,17 @@ def vae_gn_workspace(n, HW, C_, dev):
     return torch.empty(256 + (n * 256 + 255) // 256 * 256 + pairs * 8, dtype=torch.uint8, device=dev)
 
 
-# (n, HW, C): n < 16 -> up to 512 statistics slabs per image, n >= 16 -> 64; HW 64 (R = 8 mid level) .. 65536 (full resolution at R = 32)
+# (n, HW, C, statistics slabs per image -- asserted against lfm_vae_groupnorm_plan before the launch --, label): n < 16 -> up to 512 slabs of at least 64 pixels
+# per image as far as the workspace has room, n >= 16 -> at most 64 of 1024; HW 64 (R = 8 mid level) .. 65536 (full resolution at R = 32)
 VAE_GN_CASES = [
-    (1, 65536, 128, "batch-1 full resolution, 512 slabs"),
-    (3, 1000, 256, "ragged slabs"),
-    (15, 4096, 512, "n = 15, last below the 64-slab branch"),
-    (16, 4096, 256, "n = 16, first on the 64-slab branch"),
-    (64, 1024, 512, "headline mid level (R = 32)"),
-    (64, 64, 512, "R = 8 mid level"),
-    (16, 16384, 128, "n = 16 at 128x128"),
+    (1, 65536, 128, 512, "batch-1 full resolution, 512 slabs"),
+    (3, 1000, 256, 16, "ragged slabs"),
+    (15, 4096, 512, 4, "n = 15, room for 64 slabs only: the 64-slab launch"),
+    (16, 4096, 256, 4, "n = 16, first on the 64-slab branch"),
+    (64, 1024, 512, 1, "headline mid level (R = 32)"),
+    (64, 64, 512, 1, "R = 8 mid level"),
+    (16, 16384, 128, 16, "n = 16 at 128x128"),
+    (15, 4608, 128, 68, "n = 15, last below the 64-slab branch: 1024 // 15 = 68 ragged slabs"),
 ]
 
 
@@ -188,12 +198,13 @@ VAE_GN_CASES = [
 def test_vae_groupnorm_vs_fp64(case, fam):
     from lfm_amd import hip
 
-    n, HW, C_, what = case
+    n, HW, C_, slabs, what = case
     dev = torch.device("cuda:0")
     L = hip.lib()
     x = family(fam, n, HW, C_, G, seed=n + HW + C_, dev=dev)
     gamma, beta, _ = affine(C_, C_ + n, dev)
     ws = vae_gn_workspace(n, HW, C_, dev)
+    assert hip.vae_groupnorm_plan(n, HW, C_, ws.numel()) == slabs  # the slab policy this case is about really runs
     silu = C_ != 512  # the mid-attention GroupNorm has no SiLU
 
     def run():

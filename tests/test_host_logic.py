@@ -602,6 +602,71 @@ def test_attention_plan_is_the_kernel_that_runs():
     assert hip.attention_plan(0, 16, 64, 256) == -1 and hip.attention_plan(4, 0, 64, 256) == -1  # as lfm_dit_attention_hd refuses them
 
 
+# (N, HW, C, groups) -> lfm_groupnorm_plan as (statistics, apply) under (the defaults, flag UNET_GN_ROWS); -1 = LFM_ERR_SHAPE.  Written from the rules, not from
+# the C++, with cpg = C / groups.  Statistics: FUSED 1 = cpg % 8 == 0, cpg <= 2048, HW <= 1024 and the flag not set; else ROWS 2 = cpg % 4 == 0 and C / 8 <= 256; else
+# GROUPS4 3 = cpg % 4 == 0; else GROUPS1 4.  Apply: FUSED 1 with the fused statistics; else OCTET 2 = C / 8 <= 256 and 256 % (C / 8) == 0; else CHUNK 3, refused
+# from HW (C / 8) = 2^31.  GROUPS4 + OCTET cannot occur: GROUPS4 is what a cpg % 4 == 0 shape gets only when C / 8 > 256 kept it from ROWS, and OCTET needs C / 8 <= 256.
+_F, _R, _G4, _G1 = (1, 1), 2, 3, 4
+_O, _CH = 2, 3
+_GROUPNORM_PLAN = [
+    ((2, 1024, 256, 32), (_F, (_R, _O))),                  # cpg 8 at the HW boundary; the flag: the three-kernel path of a fused shape
+    ((2, 1025, 256, 32), ((_R, _O), (_R, _O))),
+    ((2, 1024, 128, 32), ((_R, _O), (_R, _O))),            # cpg 4
+    ((2, 1025, 128, 32), ((_R, _O), (_R, _O))),
+    ((2, 1024, 384, 32), ((_R, _CH), (_R, _CH))),          # cpg 12: 48 octets do not divide the block
+    ((2, 300, 384, 32), ((_R, _CH), (_R, _CH))),
+    ((2, 2000, 768, 32), ((_R, _CH), (_R, _CH))),          # cpg 24 above HW 1024: 96 octets
+    ((2, 1024, 96, 32), ((_G1, _CH), (_G1, _CH))),         # cpg 3
+    ((2, 1025, 96, 32), ((_G1, _CH), (_G1, _CH))),
+    ((2, 1024, 64, 32), ((_G1, _O), (_G1, _O))),           # cpg 2: 8 octets
+    ((2, 300, 64, 32), ((_G1, _O), (_G1, _O))),
+    ((2, 64, 2048, 1), (_F, (_R, _O))),                    # groups = 1: cpg = 2048 is the widest fused group; C / 8 = 256 is the widest ROWS / OCTET
+    ((2, 64, 4096, 1), ((_G4, _CH), (_G4, _CH))),          # cpg 4096 > 2048
+    ((2, 1024, 2304, 32), (_F, (_G4, _CH))),               # cpg 72, C / 8 = 288 > 256: the flag on a shape the row kernels do not take
+    ((2, 1025, 2304, 32), ((_G4, _CH), (_G4, _CH))),
+    ((2, 64, 4096, 32), (_F, (_G4, _CH))),
+    ((1, 178956970, 96, 32), ((_G1, _CH), (_G1, _CH))),    # HW x 12 = 2^31 - 8: the chunk kernel's last index
+    ((1, 178956971, 96, 32), (-1, -1)),                    # HW x 12 = 2^31 + 4
+    ((1, 300000000, 64, 32), ((_G1, _O), (_G1, _O))),      # the octet kernel has no such limit
+    ((0, 64, 256, 32), (-1, -1)), ((2, 0, 256, 32), (-1, -1)), ((2, 64, 0, 32), (-1, -1)), ((2, 64, 256, 0), (-1, -1)),
+    ((-1, 64, 256, 32), (-1, -1)), ((2, -64, 256, 32), (-1, -1)), ((2, 64, -256, 32), (-1, -1)), ((2, 64, 256, -32), (-1, -1)),
+    ((2, 64, 264, 33), (-1, -1)),                          # groups > 32 (33 divides 264, 264 % 8 == 0)
+    ((2, 64, 256, 3), (-1, -1)),                           # C % groups
+    ((2, 64, 36, 4), (-1, -1)),                            # C % 8
+]
+
+
+def test_groupnorm_plan_is_the_kernels_that_run():
+    """lfm_groupnorm_plan (no launch) = the one chooser lfm_groupnorm_f16 and lfm_groupnorm2_f16 launch through (csrc/groupnorm_dispatch.h: gn_choose): the statistics
+    and the apply kernel per shape under the defaults and under flag UNET_GN_ROWS, and every refusal.  lfm_vae_groupnorm_plan = the slabs per image of the
+    decoder's statistics pass (csrc/vae.hip: vae_gn_slabs) for the workspace tests/test_gpu_groupnorm.py gives it."""
+    from lfm_amd import hip
+
+    shapes = [s for s, _ in _GROUPNORM_PLAN]
+    plans = lambda: [hip.groupnorm_plan(*s) for s in shapes]
+    try:
+        assert list(zip(shapes, plans())) == list(zip(shapes, [w[0] for _, w in _GROUPNORM_PLAN]))
+        hip.gemm_select(hip.DBG_UNET_GN_ROWS << 4)
+        assert list(zip(shapes, plans())) == list(zip(shapes, [w[1] for _, w in _GROUPNORM_PLAN]))
+    finally:
+        hip.gemm_select(0)
+    assert hip.lib().lfm_groupnorm_plan(2, 1024, 256, 32) == 1 | 1 << 4 and hip.lib().lfm_groupnorm_plan(2, 300, 384, 32) == 2 | 3 << 4  # stats | apply << 4
+
+    # the decoder: stats for n images, the zero page, then per image the larger of the full-resolution epilogue slabs and 64 slabs x 128 half-octets, 8 bytes a pair
+    ws = lambda n, HW: 256 + (n * 256 + 255) // 256 * 256 + n * max(HW * 256 // 512, 64 * 128) * 8
+    vae = lambda n, HW, C_: hip.vae_groupnorm_plan(n, HW, C_, ws(n, HW))
+    assert vae(1, 65536, 128) == 512    # one image: room for 32768 / 32 = 1024 slabs, 1024 / n wanted, 512 the cap; 128 pixels each
+    assert vae(16, 4096, 256) == 4      # n x 64 = 1024: the 64-slab policy, 1024 pixels per slab
+    assert vae(15, 4096, 512) == 4      # n = 15 with room for 8192 / 128 = 64 slabs only: the same launch
+    assert vae(15, 4608, 128) == 68     # n = 15 with room for 8192 / 32 = 256: 1024 // 15 = 68 slabs of ceil(4608 / 68) = 68 pixels
+    assert vae(3, 1000, 256) == 16      # room for 128, but no slab below 64 pixels
+    assert vae(64, 1024, 512) == 1 and vae(64, 64, 512) == 1 and vae(16, 16384, 128) == 16
+    assert hip.vae_groupnorm_plan(15, 4096, 512, ws(15, 4096) + 15 * 4 * 128 * 8) == 64  # four more slabs of room per image: 68 allowed, 64 of 64 pixels taken
+    short = 256 + 16 * 256 + 16 * 64 * 32 * 8  # tests/test_gpu_groupnorm.py: test_vae_groupnorm_refuses_a_short_workspace
+    assert hip.vae_groupnorm_plan(16, 64, 128, short) == 1 and hip.vae_groupnorm_plan(16, 64, 128, short - 8) == -3
+    assert vae(0, 64, 128) == -1 and vae(2, 0, 128) == -1 and vae(2, 64, 384) == -1 and vae(2, 64, 64) == -1
+
+
 # pairs of flags of DIFFERENT consumers on the same bits (csrc/debug_flags.h says "shares" next to both): today's overlaps, acknowledged one by one.
 # A new pair fails test_debug_flags_have_one_definition until it is added here on purpose.
 _SHARED_FLAG_BITS = {
