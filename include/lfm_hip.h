@@ -551,6 +551,21 @@ int lfm_linear_gelu_f16(const void* A, long lda, const void* W, long ldw, void* 
  * and a replay follows labels rewritten in place. */
 int lfm_label_rescale_f32(const void* labels_int64, const float* w, const float* bias, float* out, int N, int H, int W, int num_cls, int Cout, int n_stages,
                           lfm_stream_t stream);
+/* Baseline JPEG encoding of the samples on the device (csrc/jpeg_encode.h; DESIGN.md "JPEG encode").  Additions to ABI 4.
+ *   img_nhwc uint8 [N,H,W,3] dense RGB, 1 <= H, W <= 4096, 1 <= N <= 65535; quality 1..100 (libjpeg's scaling of the Annex-K tables, 8-bit entries)
+ *   out      uint8 [N][cap]: for image i the entropy-coded data and the EOI marker, i.e. everything that follows the header in the file
+ *            PIL.Image.save(path, quality=quality) writes for it (4:2:0, baseline, Annex-K Huffman tables, no restart markers) -- byte for byte; the header is
+ *            the host's (lfm_amd/io_formats.py: jpeg_header), the same 623 bytes for every image of a size and quality
+ *   lengths  int32 [N]: the TRUE number of those bytes, also when it exceeds cap.  Then out[i] holds the first cap of them, and nothing is written at or
+ *            beyond out[i] + cap, nor outside [workspace, workspace + lfm_jpeg_encode_workspace_bytes(N, H, W, cap)).
+ * Refused before any launch, in this order: img_nhwc, workspace, out or lengths NULL, quality outside 1..100 (LFM_ERR_ARG); N, H, W outside the ranges above,
+ * cap < 1 (LFM_ERR_SHAPE; lfm_jpeg_encode_workspace_bytes returns 0 for them); workspace not 16-byte or lengths not 4-byte aligned (LFM_ERR_ALIGN);
+ * workspace_bytes too small (LFM_ERR_WORKSPACE).  img_nhwc needs no alignment (16-byte aligned with W % 16 == 0 it is read 16 bytes per lane).
+ * Six kernels on `stream`, no host synchronisation, no readback, no one-time set-up, integer arithmetic only and no atomics on global memory: deterministic,
+ * independent of N and of an image's place in the batch, graph-capturable, and a replay follows pixels rewritten in place. */
+size_t lfm_jpeg_encode_workspace_bytes(int N, int H, int W, int cap);
+int lfm_jpeg_encode_rgb8(const uint8_t* img_nhwc, int N, int H, int W, int quality, int cap, void* workspace, size_t workspace_bytes, uint8_t* out,
+                         int32_t* lengths, lfm_stream_t stream);
 /* emb = time_embed(timestep_embedding(t, F)) (+ label_emb[y]) (nn.py:103-121, unet.py:633-641): fp32 [N,E] and fp16 silu(emb).
  * label_table has label_rows rows; a label outside [0, label_rows) (an IndexError in the reference) poisons its row with NaN. */
 int lfm_time_embed(const float* t, int t_len, const float* w0, const float* b0, const float* w2, const float* b2, const float* label_table,

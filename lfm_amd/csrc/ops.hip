@@ -448,6 +448,10 @@ extern "C" int lfm_concat_channels_f16(const void* a, const void* b, void* out, 
 // ------------------------------------------------------------------ label-map conditioning of mask-to-image synthesis (encoder.py:90-112): lfm_label_rescale_f32
 #include "label_rescale.h"
 
+// ------------------------------------------------------------------ the sample writers' JPEGs, byte-identical to PIL.Image.save: lfm_jpeg_encode_rgb8,
+// lfm_jpeg_encode_workspace_bytes
+#include "jpeg_encode.h"
+
 // ------------------------------------------------------------------ timestep embedding MLP (nn.py:103-121 + unet.py:633-641)
 // emb[r] = W2 silu(W0 [cos(t f) | sin(t f)] + b0) + b2 (+ label_emb[y[r]]);  also emits fp16 silu(emb) for the ResBlock emb_layers
 __global__ __launch_bounds__(256) void time_embed1_kernel(const float* __restrict__ t, int t_len, const float* __restrict__ w0,

@@ -114,6 +114,9 @@ def build_parser():
     p.add_argument("--num_cls", type=int, default=None, help="classes of the label maps (default: the reference's table -- coco 182, ade20k 151, celeba 19)")
     p.add_argument("--cond_path", type=str, default="fused", choices=["fused", "onehot"], help="conditioning stage: one gather kernel, or the one-hot chain")
     p.add_argument("--save_dir", type=str, default=None, help="default: the reference's ./mask2image_generated_samples/{dataset}")
+    # absent from the namespace unless given (read with getattr, "host" when absent): a default run's arguments stay the reference's plus the five above
+    p.add_argument("--jpeg_encoder", type=str, default=argparse.SUPPRESS, choices=["host", "device"], help="host (default) = PIL.Image.save on the CPU; device = "
+                   "the HIP JPEG encoder, only the compressed bytes cross to the host (the same bytes in the same files)")
     return p
 
 
@@ -173,7 +176,7 @@ def load_segmentation(path, size, num_cls):
 def main(argv=None):
     import os
 
-    from ..io_formats import save_indexed_jpegs, to_uint8_rounding
+    from ..io_formats import begin_jpegs_device, finish_jpegs_device, save_indexed_jpegs, to_uint8_rounding, to_uint8_rounding_device, write_indexed_files
 
     args = build_parser().parse_args(argv)
     if not args.random_weights and args.segmentation is None:
@@ -190,11 +193,23 @@ def main(argv=None):
     save_dir = args.save_dir or "./mask2image_generated_samples/{}".format(args.dataset)
     os.makedirs(save_dir, exist_ok=True)
     torch.manual_seed(42)  # reference :71
+    waiting = None  # --jpeg_encoder device: the previous batch's encoder job; its files are written while this batch's kernels run
     for i, start in enumerate(range(0, seg.shape[0], args.batch_size)):
         batch = seg[start:start + args.batch_size].to(device)
         img, _ = synthesize_batch(model_cond, vae, cond_stage_model, batch, num_cls, args, cond_path=args.cond_path)
-        save_indexed_jpegs(to_uint8_rounding(img), save_dir, start)  # torchvision.utils.save_image's conversion; its `normalized=True` (:146) is no keyword of it
+        if getattr(args, "jpeg_encoder", "host") == "device":  # the same conversion where the image lives, then the encoder behind it on the same stream
+            job, done = begin_jpegs_device(to_uint8_rounding_device(img)), torch.cuda.Event()
+            done.record()
+            if waiting is not None:
+                waiting[1].synchronize()
+                write_indexed_files(finish_jpegs_device(waiting[0]), save_dir, waiting[2])
+            waiting = (job, done, start)
+        else:
+            save_indexed_jpegs(to_uint8_rounding(img), save_dir, start)  # torchvision.utils.save_image's conversion; its `normalized=True` (:146) is no keyword of it
         print("generating batch ", i)
+    if waiting is not None:
+        waiting[1].synchronize()
+        write_indexed_files(finish_jpegs_device(waiting[0]), save_dir, waiting[2])
 
 
 if __name__ == "__main__":

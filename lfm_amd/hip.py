@@ -210,6 +210,11 @@ def lib():
     L.lfm_gather_rows_f32.argtypes = [V, I, I, V, I, V, LG, V]
     L.lfm_label_rescale_f32.restype = I
     L.lfm_label_rescale_f32.argtypes = [V, V, V, V, I, I, I, I, I, I, V]
+    if hasattr(L, "lfm_jpeg_encode_rgb8"):  # additions to ABI 4 (an LFM_HIP_LIBRARY built before them still loads; jpeg_encode then fails loudly)
+        L.lfm_jpeg_encode_workspace_bytes.restype = C.c_size_t
+        L.lfm_jpeg_encode_workspace_bytes.argtypes = [I, I, I, I]
+        L.lfm_jpeg_encode_rgb8.restype = I
+        L.lfm_jpeg_encode_rgb8.argtypes = [V, I, I, I, I, I, V, C.c_size_t, V, V, V]
     L.lfm_song_embed.restype = I
     L.lfm_song_embed.argtypes = [V, I, V, V, V, V, V, V, F, V, I, V, V, V, I, I, I, V]
     L.lfm_fourier_embed.restype = I
@@ -659,6 +664,52 @@ def label_rescale(labels, w, bias, n_stages, out=None):
     check(lib().lfm_label_rescale_f32(ptr(labels), ptr(w), ptr(bias), ptr(out), N, H, W, num_cls, cout, int(n_stages), stream_ptr(labels.device)),
           "lfm_label_rescale_f32")
     return out
+
+
+JPEG_MAX_DIM = 4096  # csrc/jpeg_encode.h
+# (device index, stream) -> uint8 workspace, grown on demand: calls on one stream are ordered, calls on two streams (the drivers' lanes) must not share one.
+# A call under graph capture never reads or feeds this cache: its workspace comes from the graph's own pool and belongs to the graph.
+_jpeg_ws = {}
+
+
+def jpeg_default_capacity(H, W):
+    """Bytes per image hip.jpeg_encode reserves unless told otherwise: one per pixel of the image rounded up to whole MCUs, several times what a photograph-like
+    sample takes at quality 75 (noise at quality 100 takes more: its true length still comes back, and io_formats falls back to Pillow)."""
+    return (-(-H // 16) * 16) * (-(-W // 16) * 16)
+
+
+def jpeg_encode(img_u8, quality=75, capacity=None):
+    """lfm_jpeg_encode_rgb8: contiguous uint8 [N, H, W, 3] RGB on the device -> (out uint8 [N, capacity], lengths int32 [N]).  out[i, :lengths[i]] is what follows
+    the header (io_formats.jpeg_header) in the file PIL.Image.save writes for image i; lengths[i] is the true length also when it exceeds `capacity` (then out[i]
+    holds the first `capacity` bytes).  No readback, current stream.  Capturable: under capture the outputs AND the workspace are allocated from the graph's
+    private pool (they live as long as the graph does, and no eager call ever sees that memory); outside a capture the workspace is cached per stream."""
+    require_gpu(img_u8, "jpeg_encode")
+    if img_u8.dtype != torch.uint8 or img_u8.dim() != 4 or img_u8.shape[-1] != 3 or not img_u8.is_contiguous():
+        raise LfmHipError(f"jpeg_encode: images must be contiguous uint8 [N, H, W, 3], got {img_u8.dtype} {tuple(img_u8.shape)} strides {img_u8.stride()}")
+    N, H, W, _ = img_u8.shape
+    cap = jpeg_default_capacity(H, W) if capacity is None else int(capacity)
+    L = lib()
+    if not hasattr(L, "lfm_jpeg_encode_rgb8"):
+        raise LfmHipError("this liblfm_hip.so has no lfm_jpeg_encode_rgb8: rebuild it (python -m lfm_amd._build --force)")
+    need = L.lfm_jpeg_encode_workspace_bytes(N, H, W, cap)
+    if need == 0:
+        raise LfmHipError(f"jpeg_encode: unsupported shape N={N} H={H} W={W} capacity={cap} (1 <= H, W <= {JPEG_MAX_DIM}, N >= 1, capacity >= 1)")
+    dev = img_u8.device
+    stream = torch.cuda.current_stream(dev)
+    if torch.cuda.is_current_stream_capturing():
+        ws = torch.empty(need, dtype=torch.uint8, device=dev)
+    else:
+        key = (dev.index, stream.cuda_stream)
+        ws = _jpeg_ws.get(key)
+        if ws is None or ws.numel() < need:
+            ws = _jpeg_ws[key] = torch.empty(need, dtype=torch.uint8, device=dev)
+    out = torch.empty((N, cap), dtype=torch.uint8, device=dev)
+    lengths = torch.empty((N,), dtype=torch.int32, device=dev)
+    check(L.lfm_jpeg_encode_rgb8(ptr(img_u8), N, H, W, int(quality), cap, ptr(ws), ws.numel(), ptr(out), ptr(lengths), C.c_void_p(stream.cuda_stream)),
+          "lfm_jpeg_encode_rgb8")
+    if torch.cuda.is_current_stream_capturing():
+        out._lfm_jpeg_ws = ws  # the graph's workspace lives as long as the graph's output does
+    return out, lengths
 
 
 def fir_down2(x, N, Ho, Wo, C, pad=1, bias=None, resid=None, scale=1.0, out=None):
