@@ -566,6 +566,41 @@ int lfm_label_rescale_f32(const void* labels_int64, const float* w, const float*
 size_t lfm_jpeg_encode_workspace_bytes(int N, int H, int W, int cap);
 int lfm_jpeg_encode_rgb8(const uint8_t* img_nhwc, int N, int H, int W, int quality, int cap, void* workspace, size_t workspace_bytes, uint8_t* out,
                          int32_t* lengths, lfm_stream_t stream);
+/* The elementwise stages of an inpainting batch (downstream_tasks/test_flow_latent_inpainting.py: CustomizedInpaintingEvalDataset.__getitem__ :36-55, the loop
+ * :147-150 and :157-160, torchvision.utils.save_image's quantisation) from the bytes the files hold (csrc/inpaint.h).  Additions to ABI 4.
+ * Images are uint8 NHWC [N,H,W,3] dense, masks uint8 [N,H,W] dense, the PNG's bytes as stored: 255 = keep, 0 = hole, anything between blends.  H % 8 == 0 and
+ * W % 8 == 0.  Every fp32 operation below is rounded on its own (no FMA contraction; byte / 255 is the correctly rounded quotient), in the order written, which is the reference's: prepare
+ * and composite give the bits torch gives on the CPU.  The LFM_FAST_MATH=1 A/B build is not covered by that statement.
+ *
+ * lfm_inpaint_prepare_u8: per pixel  i = (float)b / 255.0f  per channel,  m = 1.0f - (float)p / 255.0f  (1 = hole),  masked = (1.0f - m) * i;
+ *   masked_nchw [N,3,H,W] = masked * 2.0f - 1.0f  (the VAE encoder's input);  image_nchw [N,3,H,W] = i * 2.0f - 1.0f  where that pointer is not NULL;
+ *   mask_latent[n * mask_latent_image_stride + (y / 8) * (W / 8) + x / 8] = m * 2.0f - 1.0f  for y % 8 == 0 and x % 8 == 0: F.interpolate(mask, size=(H/8, W/8))
+ *   (nearest) is that pick.  The caller passes channel 4 of the [N,5,H/8,W/8] conditioning tensor with stride 5 * (H/8) * (W/8); nothing else of it is written.
+ * lfm_inpaint_cond_f32: out[n * out_image_stride + c * hw + k] = (mean + expf(0.5f * clamp(logvar, -30, 20)) * eps) * scale  for c < 4, k < hw, with moments
+ *   fp32 [N,8,hw] (mean | logvar, lfm_vae_encode's output) and eps fp32 [N,4,hw]: DiagonalGaussianDistribution.sample() scaled.  eps == NULL gives mean * scale
+ *   (.mode(): one multiplication, exact) and the logvar half is not read.  Elements beyond the first 4 * hw of an image's stride (the mask channel) are not
+ *   touched.  expf is the accurate library routine (OCML, documented at 1 ulp; no approximate v_exp_f32), the clamp keeps a NaN as torch.clamp does; four
+ *   roundings and that ulp per element (tests/inpaint_cases.py derives the bound from them).
+ * lfm_inpaint_composite_u8: per pixel and channel, from the bytes and the decoded sample fake_nchw fp32 [N,3,H,W]:
+ *   f01 = (f + 1.0f) / 2.0f;  mm = ((m * 2.0f - 1.0f) + 1.0f) / 2.0f;  i01 = ((i * 2.0f - 1.0f) + 1.0f) / 2.0f;  o = f01 * mm + (1.0f - mm) * i01;
+ *   out_nhwc uint8 [N,H,W,3] = (uint8_t)clamp(o * 255.0f + 0.5f, 0, 255).  The round trip through [-1,1] is part of the definition (i01 != i for 63 of the 256
+ *   bytes).  A pixel with mask byte 255 comes out as its image byte, one with mask byte 0 as the quantised sample.  A NaN in o gives byte 0, +inf 255, -inf 0;
+ *   a non-finite f reaches o also where the mask keeps the image (inf * 0), so such a pixel is 0 whatever the image holds.  Not compared with torch, whose
+ *   float-to-uint8 conversion of a NaN is not defined.
+ *
+ * Alignment.  Served at any base alignment the element types allow: byte pointers anywhere, float pointers 4-byte aligned (LFM_ERR_ALIGN otherwise).  prepare
+ * and composite run 16 pixels per lane with 16-byte accesses when W % 16 == 0 and every pointer is 16-byte aligned, 8 pixels per lane with 8-byte loads of the
+ * bytes and 16-byte accesses of the floats when the byte pointers are 8-byte and the float pointers 16-byte aligned, one element per access otherwise; cond
+ * runs four elements per access when hw % 4 == 0, out_image_stride % 4 == 0 and its pointers are 16-byte aligned.  Every variant gives the same bits.
+ * mask_latent is written 4 bytes at a time.
+ * Refused before any launch, in this order: a required pointer NULL (LFM_ERR_ARG; image_nchw and eps may be NULL); N, H, W or hw < 1, H % 8, W % 8, a stride
+ * smaller than what is written per image (LFM_ERR_SHAPE); a misaligned float pointer (LFM_ERR_ALIGN).  One launch each on `stream`, no readback, no
+ * workspace, no allocation, no atomics: graph-capturable, and a replay follows inputs rewritten in place. */
+int lfm_inpaint_prepare_u8(const uint8_t* img_nhwc, const uint8_t* mask, float* masked_nchw, float* image_nchw, float* mask_latent,
+                           long mask_latent_image_stride, int N, int H, int W, lfm_stream_t stream);
+int lfm_inpaint_cond_f32(const float* moments, const float* eps, float scale, float* out, long out_image_stride, int N, int hw, lfm_stream_t stream);
+int lfm_inpaint_composite_u8(const float* fake_nchw, const uint8_t* img_nhwc, const uint8_t* mask, uint8_t* out_nhwc, int N, int H, int W,
+                             lfm_stream_t stream);
 /* emb = time_embed(timestep_embedding(t, F)) (+ label_emb[y]) (nn.py:103-121, unet.py:633-641): fp32 [N,E] and fp16 silu(emb).
  * label_table has label_rows rows; a label outside [0, label_rows) (an IndexError in the reference) poisons its row with NaN. */
 int lfm_time_embed(const float* t, int t_len, const float* w0, const float* b0, const float* w2, const float* b2, const float* label_table,

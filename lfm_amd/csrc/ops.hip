@@ -452,6 +452,10 @@ extern "C" int lfm_concat_channels_f16(const void* a, const void* b, void* out, 
 // lfm_jpeg_encode_workspace_bytes
 #include "jpeg_encode.h"
 
+// ------------------------------------------------------------------ inpainting's elementwise stages from the image and mask bytes (test_flow_latent_inpainting.py
+// :36-55, :147-150, :157-160): lfm_inpaint_prepare_u8, lfm_inpaint_cond_f32, lfm_inpaint_composite_u8
+#include "inpaint.h"
+
 // ------------------------------------------------------------------ timestep embedding MLP (nn.py:103-121 + unet.py:633-641)
 // emb[r] = W2 silu(W0 [cos(t f) | sin(t f)] + b0) + b2 (+ label_emb[y[r]]);  also emits fp16 silu(emb) for the ResBlock emb_layers
 __global__ __launch_bounds__(256) void time_embed1_kernel(const float* __restrict__ t, int t_len, const float* __restrict__ w0,

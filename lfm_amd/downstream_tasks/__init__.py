@@ -6,10 +6,14 @@ Drop-in for /root/reference/downstream_tasks/test_flow_latent_inpainting.py:58-9
 (``sample_from_model``, ``WrapperCondFlow``); the velocity field is the origin-ADM ``UNetModel`` on the HIP path
 (``models.get_flow_model`` with ``num_in_channels`` 9 / 8, ``num_out_channels`` 4).
 
-Drivers: ``python -m lfm_amd.downstream_tasks.test_flow_latent_inpainting`` and ``python -m lfm_amd.downstream_tasks.flow_latent_semantic_syn``.  The
-mask-to-image driver is a module of its own beside the sampler file ``test_flow_latent_semantic_syn.py`` (``SpatialRescaler``, ``synthesize_batch``), which
-keeps its text: ``flow_latent_semantic_syn`` holds the same two names extended (``SpatialRescaler.encode_labels``, ``synthesize_batch(..., cond_path=)``)
-and is the module to import them from.
+Drivers: ``python -m lfm_amd.downstream_tasks.flow_latent_inpainting`` and ``python -m lfm_amd.downstream_tasks.flow_latent_semantic_syn``.  Each is a
+module of its own beside its sampler file, which keeps its text.  ``test_flow_latent_semantic_syn.py`` holds ``SpatialRescaler`` and ``synthesize_batch``;
+``flow_latent_semantic_syn`` holds the same two names extended (``SpatialRescaler.encode_labels``, ``synthesize_batch(..., cond_path=)``) and is the module
+to import them from.  ``test_flow_latent_inpainting.py`` holds ``inpaint_batch`` on float tensors built as the reference's dataset class builds them (its
+own ``main`` runs a synthetic batch only); ``flow_latent_inpainting`` holds ``inpaint_batch_u8`` on the bytes of the image and mask files (uint8 NHWC images,
+the mask PNG's bytes; ``prep_path="fused"``: three kernels, csrc/inpaint.h, do the arithmetic around VAE encode, solve and decode bit for bit as the
+reference's fp32 ops do; ``"torch"``: those ops on the device and ``inpaint_batch``), the loaders for ``--images`` / ``--masks`` (directories in the
+reference's naming or ``.npy``) and the driver that writes one JPEG per pair.
 """
 import torch
 from torch import nn

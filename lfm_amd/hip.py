@@ -215,6 +215,13 @@ def lib():
         L.lfm_jpeg_encode_workspace_bytes.argtypes = [I, I, I, I]
         L.lfm_jpeg_encode_rgb8.restype = I
         L.lfm_jpeg_encode_rgb8.argtypes = [V, I, I, I, I, I, V, C.c_size_t, V, V, V]
+    if hasattr(L, "lfm_inpaint_prepare_u8"):  # additions to ABI 4 (an LFM_HIP_LIBRARY built before them still loads; the inpaint_* wrappers then fail loudly)
+        L.lfm_inpaint_prepare_u8.restype = I
+        L.lfm_inpaint_prepare_u8.argtypes = [V, V, V, V, V, LG, I, I, I, V]
+        L.lfm_inpaint_cond_f32.restype = I
+        L.lfm_inpaint_cond_f32.argtypes = [V, V, F, V, LG, I, I, V]
+        L.lfm_inpaint_composite_u8.restype = I
+        L.lfm_inpaint_composite_u8.argtypes = [V, V, V, V, I, I, I, V]
     L.lfm_song_embed.restype = I
     L.lfm_song_embed.argtypes = [V, I, V, V, V, V, V, V, F, V, I, V, V, V, I, I, I, V]
     L.lfm_fourier_embed.restype = I
@@ -710,6 +717,79 @@ def jpeg_encode(img_u8, quality=75, capacity=None):
     if torch.cuda.is_current_stream_capturing():
         out._lfm_jpeg_ws = ws  # the graph's workspace lives as long as the graph's output does
     return out, lengths
+
+
+def _inpaint_lib():
+    L = lib()
+    if not hasattr(L, "lfm_inpaint_prepare_u8"):
+        raise LfmHipError("this liblfm_hip.so has no lfm_inpaint_prepare_u8: rebuild it (python -m lfm_amd._build --force)")
+    return L
+
+
+def _inpaint_bytes(what, img_u8, mask_u8):
+    """The shape checks of the inpainting kernels' byte inputs -> (N, H, W)."""
+    require_gpu(img_u8, what)
+    if img_u8.dtype != torch.uint8 or img_u8.dim() != 4 or img_u8.shape[-1] != 3 or not img_u8.is_contiguous():
+        raise LfmHipError(f"{what}: images must be contiguous uint8 [N, H, W, 3], got {img_u8.dtype} {tuple(img_u8.shape)} strides {img_u8.stride()}")
+    N, H, W, _ = img_u8.shape
+    if mask_u8.dtype != torch.uint8 or tuple(mask_u8.shape) != (N, H, W) or not mask_u8.is_contiguous() or mask_u8.device != img_u8.device:
+        raise LfmHipError(f"{what}: masks must be contiguous uint8 [{N}, {H}, {W}] on {img_u8.device}, got {mask_u8.dtype} {tuple(mask_u8.shape)} on "
+                          f"{mask_u8.device}")
+    if H % 8 or W % 8 or N < 1:
+        raise LfmHipError(f"{what}: H and W must be multiples of 8 and N >= 1, got N={N} H={H} W={W}")
+    return N, H, W
+
+
+def _inpaint_f32(what, name, t, shape, device):
+    if t.dtype != torch.float32 or tuple(t.shape) != shape or not t.is_contiguous() or t.device != device:
+        raise LfmHipError(f"{what}: {name} must be dense fp32 {shape} on {device}, got {t.dtype} {tuple(t.shape)} strides {t.stride()} on {t.device}")
+    return t
+
+
+def inpaint_prepare(img_u8, mask_u8, cond, want_image=False):
+    """lfm_inpaint_prepare_u8: uint8 NHWC images [N,H,W,3] and the mask PNG's bytes [N,H,W] (255 = keep) -> (masked image fp32 [N,3,H,W] in [-1,1], the VAE
+    encoder's input; the image itself likewise, or None), and channel 4 of `cond` (dense fp32 [N,5,H/8,W/8]) = the mask in {-1..+1} (+1 = hole) picked at
+    [::8, ::8].  The reference's dataset arithmetic, bit for bit.  Channels 0..3 of `cond` are not written.  No readback (capturable)."""
+    L = _inpaint_lib()
+    N, H, W = _inpaint_bytes("inpaint_prepare", img_u8, mask_u8)
+    h, w = H // 8, W // 8
+    _inpaint_f32("inpaint_prepare", "cond", cond, (N, 5, h, w), img_u8.device)
+    masked = torch.empty(N, 3, H, W, dtype=torch.float32, device=img_u8.device)
+    image = torch.empty_like(masked) if want_image else None
+    check(L.lfm_inpaint_prepare_u8(ptr(img_u8), ptr(mask_u8), ptr(masked), ptr(image), C.c_void_p(cond.data_ptr() + 4 * h * w * 4), 5 * h * w, N, H, W,
+                                   stream_ptr(img_u8.device)), "lfm_inpaint_prepare_u8")
+    return masked, image
+
+
+def inpaint_cond(moments, eps, scale, cond):
+    """lfm_inpaint_cond_f32: cond[:, :4] = (mean + exp(0.5 * clamp(logvar, -30, 20)) * eps) * scale from the VAE encoder's moments fp32 [N,8,h,w]
+    (mean | logvar) and eps fp32 [N,4,h,w]; eps None: mean * scale (the posterior's mode).  cond dense fp32 [N,5,h,w]; its channel 4 is not written.  No
+    readback (capturable).  Returns cond."""
+    L = _inpaint_lib()
+    require_gpu(moments, "inpaint_cond")
+    if moments.dim() != 4 or moments.shape[1] != 8:
+        raise LfmHipError(f"inpaint_cond: moments must be fp32 [N, 8, h, w], got {tuple(moments.shape)}")
+    N, _, h, w = moments.shape
+    _inpaint_f32("inpaint_cond", "moments", moments, (N, 8, h, w), moments.device)
+    if eps is not None:
+        _inpaint_f32("inpaint_cond", "eps", eps, (N, 4, h, w), moments.device)
+    _inpaint_f32("inpaint_cond", "cond", cond, (N, 5, h, w), moments.device)
+    check(L.lfm_inpaint_cond_f32(ptr(moments), ptr(eps), float(scale), ptr(cond), 5 * h * w, N, h * w, stream_ptr(moments.device)), "lfm_inpaint_cond_f32")
+    return cond
+
+
+def inpaint_composite(fake, img_u8, mask_u8, out=None):
+    """lfm_inpaint_composite_u8: decoded sample fp32 [N,3,H,W] in [-1,1] + the image and mask bytes -> uint8 NHWC [N,H,W,3]: the reference's composite
+    fake01 * mask01 + (1 - mask01) * image01 (:157-160) as torchvision.utils.save_image quantises it, bit for bit.  No readback (capturable)."""
+    L = _inpaint_lib()
+    N, H, W = _inpaint_bytes("inpaint_composite", img_u8, mask_u8)
+    _inpaint_f32("inpaint_composite", "fake", fake, (N, 3, H, W), img_u8.device)
+    if out is None:
+        out = torch.empty(N, H, W, 3, dtype=torch.uint8, device=img_u8.device)
+    if out.dtype != torch.uint8 or tuple(out.shape) != (N, H, W, 3) or not out.is_contiguous() or out.device != img_u8.device:
+        raise LfmHipError(f"inpaint_composite: out must be contiguous uint8 [{N}, {H}, {W}, 3] on {img_u8.device}, got {out.dtype} {tuple(out.shape)}")
+    check(L.lfm_inpaint_composite_u8(ptr(fake), ptr(img_u8), ptr(mask_u8), ptr(out), N, H, W, stream_ptr(img_u8.device)), "lfm_inpaint_composite_u8")
+    return out
 
 
 def fir_down2(x, N, Ho, Wo, C, pad=1, bias=None, resid=None, scale=1.0, out=None):
