@@ -411,7 +411,9 @@ int lfm_conv3x3_scaled_f16_ws(const void* in, const void* w, const float* bias, 
  * calling thread's flags: 1 = the halo-tiled direct kernel, 2 = split-K slices + the finish kernel, 3 = one implicit GEMM; LFM_ERR_SHAPE for a shape that
  * is refused.  No launch; usable without a GPU. */
 int lfm_conv3x3_plan(int N, int H, int W, int Cin, int Cout, int mode, size_t workspace_bytes);
-/* first conv (unet.py:475): fp32 NCHW [N,Cin<=16,H,W] -> fp16 NHWC [N,H,W,Cout]; w fp32 [Cout,Cin,3,3] */
+/* first conv (unet.py:475): fp32 NCHW [N,Cin<=16,H,W] -> fp16 NHWC [N,H,W,Cout]; w fp32 [Cout,Cin,3,3].  Cout % 8 == 0.  out_nhwc and bias 16-byte
+ * aligned, else LFM_ERR_ALIGN before any launch: the scalar kernel stores eight channels and loads four bias values at a time.  The one exception:
+ * Cout of 64, 128, 192 or 256 on the MFMA kernel (the default there while its operand planes fit the LDS) needs out_nhwc 8-byte aligned only. */
 int lfm_conv3x3_in_f32(const float* x_nchw, const float* w, const float* bias, void* out_nhwc, int N, int H, int W, int Cin, int Cout,
                        lfm_stream_t stream);
 /* last conv (unet.py:594): fp16 NHWC -> fp32 NCHW [N,nch<=4,H,W]; w4 fp16 [4][9][Cin] (rows >= nch zero), bias4 fp32 [4] */

@@ -202,14 +202,19 @@ extern "C" int lfm_gather_rows_f32(const float* table, int rows, int cols, const
 // ------------------------------------------------------------------ first conv: fp32 NCHW (Cin <= 16) -> fp16 NHWC
 // Weights are transposed into LDS as [k = (c,ky,kx)][Cout] so the 8 output channels of a thread are two float4 reads per tap;
 // a block walks CI_PIX pixels (threads = Cout/8 channel-octets x pixel rows), input taps are L1-served broadcast loads.
+// blockIdx.y: the slice [blockIdx.y Cs, + Cs) of the output channels (Cs % 8 == 0) -- one slice, unless the weights of all of them exceed the LDS
+// (Cin 16 with Cout 320: 180 KiB).
 #define CI_PIX 256
 __global__ __launch_bounds__(256) void conv_in_kernel(const float* __restrict__ x, const float* __restrict__ w, const float* __restrict__ b,
-                                                      half_t* __restrict__ out, int N, int H, int W, int Cin, int Cout) {
-  extern __shared__ __attribute__((aligned(16))) float wl[];  // [Cin*9][Cout]
-  const int KK = Cin * 9, c8n = Cout / 8;
-  for (int e = threadIdx.x; e < KK * Cout; e += 256) {
+                                                      half_t* __restrict__ out, int N, int H, int W, int Cin, int Cout, int Cs) {
+  extern __shared__ __attribute__((aligned(16))) float wl[];  // [Cin*9][Cl]
+  const int KK = Cin * 9, cs0 = blockIdx.y * Cs, Cl = Cout - cs0 < Cs ? Cout - cs0 : Cs, c8n = Cl / 8;
+  w += (long)cs0 * KK;
+  b += cs0;
+  out += cs0;
+  for (int e = threadIdx.x; e < KK * Cl; e += 256) {
     const int co = e / KK, k = e - co * KK;  // w is [Cout][Cin][3][3] = [Cout][KK]
-    wl[k * Cout + co] = w[e];
+    wl[k * Cl + co] = w[e];
   }
   __syncthreads();
   const int oct = threadIdx.x % c8n, prow = threadIdx.x / c8n, rows = 256 / c8n;
@@ -226,7 +231,7 @@ __global__ __launch_bounds__(256) void conv_in_kernel(const float* __restrict__ 
         const int iy = yy + t / 3 - 1, ix = xx + t % 3 - 1;
         if ((unsigned)iy >= (unsigned)H || (unsigned)ix >= (unsigned)W) continue;
         const float v = x[(((long)n * Cin + c) * H + iy) * W + ix];
-        const float* wr = wl + (c * 9 + t) * Cout + co;
+        const float* wr = wl + (c * 9 + t) * Cl + co;
         a0 += v * *(const f32x4*)wr;
         a1 += v * *(const f32x4*)(wr + 4);
       }
@@ -323,7 +328,7 @@ static int launch_conv_in_mfma(const float* x, const float* w, const float* b, h
 extern "C" int lfm_conv3x3_in_f32(const float* x_nchw, const float* w, const float* bias, void* out_nhwc, int N, int H, int W, int Cin,
                                   int Cout, lfm_stream_t stream) {
   if (!x_nchw || !w || !bias || !out_nhwc) return LFM_ERR_ARG;
-  if (N <= 0 || Cin <= 0 || Cin > 16 || Cout % 8 || Cout / 8 > 256) return LFM_ERR_SHAPE;
+  if (N <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cin > 16 || Cout <= 0 || Cout % 8 || Cout / 8 > 256) return LFM_ERR_SHAPE;
   if ((Cout == 64 || Cout == 128 || Cout == 192 || Cout == 256) && !((uintptr_t)out_nhwc & 7) && !((uintptr_t)bias & 15) &&
       !(lfm_gemm_debug_flags() & LFM_DBG_UNET_CONV_IN_SCALAR)) {  // flag: the scalar kernel (A/B)
     int rc;
@@ -333,11 +338,13 @@ extern "C" int lfm_conv3x3_in_f32(const float* x_nchw, const float* w, const flo
     else rc = launch_conv_in_mfma<4>(x_nchw, w, bias, (half_t*)out_nhwc, N, H, W, Cin, Cout, (hipStream_t)stream);
     if (rc != 1) return rc;
   }
-  const size_t lds = (size_t)Cin * 9 * Cout * 4;
-  if (lds > 160 * 1024) return LFM_ERR_SHAPE;
+  if (((uintptr_t)out_nhwc | (uintptr_t)bias) & 15) return LFM_ERR_ALIGN;  // the scalar kernel: 16-byte stores of eight channels, 16-byte bias loads
+  // output channels per slice: all of them, or the fewest equal slices of whole octets whose weights fit the LDS (Cin <= 16: 8 channels are 4.5 KiB at most)
+  const int fit = (int)(160 * 1024 / ((size_t)Cin * 9 * 4)) & ~7, slices = cdiv(Cout, fit), Cs = cdiv(cdiv(Cout, slices), 8) * 8;
+  const size_t lds = (size_t)Cin * 9 * Cs * 4;
   if (!lfm_kernel_lds<&conv_in_kernel>(160 * 1024)) return LFM_ERR_LAUNCH;
-  hipLaunchKernelGGL(conv_in_kernel, dim3(cdiv((long)N * H * W, CI_PIX)), dim3(256), lds, (hipStream_t)stream, x_nchw, w, bias,
-                     (half_t*)out_nhwc, N, H, W, Cin, Cout);
+  hipLaunchKernelGGL(conv_in_kernel, dim3(cdiv((long)N * H * W, CI_PIX), slices), dim3(256), lds, (hipStream_t)stream, x_nchw, w, bias,
+                     (half_t*)out_nhwc, N, H, W, Cin, Cout, Cs);
   LFM_CHECK_LAUNCH();
   return LFM_OK;
 }
