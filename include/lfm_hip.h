@@ -603,6 +603,34 @@ int lfm_inpaint_prepare_u8(const uint8_t* img_nhwc, const uint8_t* mask, float* 
 int lfm_inpaint_cond_f32(const float* moments, const float* eps, float scale, float* out, long out_image_stride, int N, int hw, lfm_stream_t stream);
 int lfm_inpaint_composite_u8(const float* fake_nchw, const uint8_t* img_nhwc, const uint8_t* mask, uint8_t* out_nhwc, int N, int H, int W,
                              lfm_stream_t stream);
+/* SSIM per image of two image batches, and the per-image sum of a mask's bytes: the score of the reference's inpainting evaluator
+ * (datasets_prep/inpaint_preprocess/losses/ssim.py: SSIM._ssim :47-67 with size_average=False; losses/base_loss.py: SSIMScore; evaluator.py: the mask area
+ * per image) in one tile kernel and one reduce kernel (csrc/ssim.h).  Additions to ABI 4.
+ *   lfm_ssim_u8:  a, b uint8 NHWC [N,H,W,3] dense, each byte b taken as (float)b / 255.0f, the correctly rounded quotient (C = 3); mask uint8 [N,H,W] dense
+ *                 or NULL.  With a mask, mask_sum[n] = the exact integer sum of image n's mask bytes; mask_sum is NULL if and only if mask is.
+ *   lfm_ssim_f32: a, b fp32 NCHW [N,C,H,W] dense, 1 <= C <= 4, used as they are.
+ * window: `window_size` floats in DEVICE memory, the 1-D Gaussian the caller builds as the reference's _gaussian does (sigma 1.5, normalised in fp32);
+ * window_size odd, 3..11.  With x, y one channel of the two images, 0 outside the image (zero padding, window_size / 2 wide), and G(q)[r][c] =
+ * sum_j w[j] * (sum_k w[k] * q[r + j - p][c + k - p]), p = window_size / 2 (horizontal pass, then vertical, FMAs in ascending tap order):
+ *   mu1 = G(x), mu2 = G(y), s11 = G(x*x) - mu1*mu1, s22 = G(y*y) - mu2*mu2, s12 = G(x*y) - mu1*mu2
+ *   map = ((2*mu1*mu2 + C1) * (2*s12 + C2)) / ((mu1*mu1 + mu2*mu2 + C1) * (s11 + s22 + C2)),  C1 = 1e-4f, C2 = 9e-4f
+ *   out[n] = (float)(sum of map over c, r, c in fp64 of fp32 tile sums / (C*H*W))
+ * Every product, sum and the division of the map are rounded on their own in fp32 (no FMA contraction), so identical images score exactly 1.0f.  The
+ * reference's 2-D window is the fp32 outer product of w; the separable form differs from it by rounding only (tests/ssim_cases.py derives the bound
+ * against the reference in fp64).  Sums are taken in a fixed order without float atomics: out[n] is bit-reproducible and does not depend on N or on the
+ * image's place in the batch; a NaN in one image reaches that image's result only.  1 <= H, W <= 4096; N * ceil(H/32) * ceil(W/32) < 2^31.
+ * workspace: lfm_ssim_workspace_bytes(N, H, W) bytes (8 per image and 32 x 32 tile, rounded up to 16; 0 for a refused shape), 16-byte aligned, no
+ * initialisation needed.  Byte pointers need no alignment: with W % 4 == 0 and a, b, mask 4-byte aligned the bytes are read a word at a time, otherwise
+ * byte by byte, with the same bits.
+ * Refused before any launch, in this order: a required pointer NULL, or exactly one of mask and mask_sum NULL (LFM_ERR_ARG); N, H, W, C or window_size out of
+ * range, or workspace_bytes too small (LFM_ERR_SHAPE); window, out, a float image pointer not 4-byte aligned, mask_sum not 8-byte aligned, or the workspace
+ * not 16-byte aligned (LFM_ERR_ALIGN).  Two launches on `stream`, no host synchronisation, no readback, no allocation; writes only out, mask_sum and the
+ * first lfm_ssim_workspace_bytes bytes of the workspace: graph-capturable, and a replay follows inputs rewritten in place. */
+size_t lfm_ssim_workspace_bytes(int N, int H, int W);
+int lfm_ssim_u8(const uint8_t* a_nhwc, const uint8_t* b_nhwc, const uint8_t* mask, int N, int H, int W, const float* window, int window_size,
+                void* workspace, size_t workspace_bytes, float* out, long long* mask_sum, lfm_stream_t stream);
+int lfm_ssim_f32(const float* a_nchw, const float* b_nchw, int N, int C, int H, int W, const float* window, int window_size, void* workspace,
+                 size_t workspace_bytes, float* out, lfm_stream_t stream);
 /* emb = time_embed(timestep_embedding(t, F)) (+ label_emb[y]) (nn.py:103-121, unet.py:633-641): fp32 [N,E] and fp16 silu(emb).
  * label_table has label_rows rows; a label outside [0, label_rows) (an IndexError in the reference) poisons its row with NaN. */
 int lfm_time_embed(const float* t, int t_len, const float* w0, const float* b0, const float* w2, const float* b2, const float* label_table,

@@ -463,6 +463,10 @@ extern "C" int lfm_concat_channels_f16(const void* a, const void* b, void* out, 
 // :36-55, :147-150, :157-160): lfm_inpaint_prepare_u8, lfm_inpaint_cond_f32, lfm_inpaint_composite_u8
 #include "inpaint.h"
 
+// ------------------------------------------------------------------ the inpainting evaluator's SSIM per image and the masks' byte sums (losses/ssim.py :36-67):
+// lfm_ssim_u8, lfm_ssim_f32, lfm_ssim_workspace_bytes
+#include "ssim.h"
+
 // ------------------------------------------------------------------ timestep embedding MLP (nn.py:103-121 + unet.py:633-641)
 // emb[r] = W2 silu(W0 [cos(t f) | sin(t f)] + b0) + b2 (+ label_emb[y[r]]);  also emits fp16 silu(emb) for the ResBlock emb_layers
 __global__ __launch_bounds__(256) void time_embed1_kernel(const float* __restrict__ t, int t_len, const float* __restrict__ w0,

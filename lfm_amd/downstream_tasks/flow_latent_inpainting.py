@@ -85,6 +85,14 @@ def build_parser():
     return p
 
 
+def driver_parser():
+    """``build_parser()`` (the sampling surface, which keeps its set of arguments) plus the driver's evaluation flag --ssim."""
+    p = build_parser()
+    p.add_argument("--ssim", action="store_true", help="score each batch's composites against the ground truth on the device before they are encoded "
+                   "(lfm_ssim_u8) and print SSIM in total and per decile of mask area at the end: the pre-JPEG score; the files are the same with or without")
+    return p
+
+
 def _load_npy(path, size, flag, tail):
     import numpy as np
 
@@ -136,7 +144,7 @@ def synthetic_pairs(n, size, seed=0):
 def main(argv=None):
     from ..io_formats import begin_jpegs_device, finish_jpegs_device, save_indexed_jpegs, write_indexed_files
 
-    args = build_parser().parse_args(argv)
+    args = driver_parser().parse_args(argv)
     if (args.images is None) != (args.masks is None):
         raise SystemExit("--images and --masks go together")
     if args.images is None and not args.random_weights:
@@ -153,10 +161,17 @@ def main(argv=None):
     save_dir = args.save_dir or "./inpainting_generated_samples/{}".format(args.dataset)
     os.makedirs(save_dir, exist_ok=True)
     torch.manual_seed(42)  # reference :95
+    score = None
+    if args.ssim:  # the composites are scored where they are: N floats and N mask sums per batch stay on the device until the table is printed
+        from .. import inpaint_eval
+
+        score = inpaint_eval.SSIMScore()
     waiting = None  # --jpeg_encoder device: the previous batch's encoder job; its files are written while this batch's kernels run
     for i, start in enumerate(range(0, imgs.shape[0], args.batch_size)):  # index = i * batch_size + j (:163; the last batch may be ragged)
         image_u8, mask_u8 = imgs[start:start + args.batch_size].to(device), masks[start:start + args.batch_size].to(device)  # the bytes: 4 per pixel
         out, _ = inpaint_batch_u8(model_cond, vae, image_u8, mask_u8, args, sample_posterior=args.posterior == "sample", prep_path=args.prep_path)
+        if score is not None:
+            score(out, image_u8, mask_u8)
         if args.jpeg_encoder == "device":  # the encoder behind the composite on the same stream
             job, done = begin_jpegs_device(out), torch.cuda.Event()
             done.record()
@@ -170,6 +185,9 @@ def main(argv=None):
     if waiting is not None:
         waiting[1].synchronize()
         write_indexed_files(finish_jpegs_device(waiting[0]), save_dir, waiting[2])
+    if score is not None:
+        groups, names = inpaint_eval.area_bins(score.mask_sums, args.image_size, args.image_size)
+        print(inpaint_eval.format_table(inpaint_eval.results_by_name(score, groups, names), title="SSIM of the composites before JPEG coding"))
 
 
 if __name__ == "__main__":

@@ -222,6 +222,13 @@ def lib():
         L.lfm_inpaint_cond_f32.argtypes = [V, V, F, V, LG, I, I, V]
         L.lfm_inpaint_composite_u8.restype = I
         L.lfm_inpaint_composite_u8.argtypes = [V, V, V, V, I, I, I, V]
+    if hasattr(L, "lfm_ssim_u8"):  # additions to ABI 4, likewise (ssim_u8 / ssim_f32 fail loudly without them)
+        L.lfm_ssim_workspace_bytes.restype = C.c_size_t
+        L.lfm_ssim_workspace_bytes.argtypes = [I, I, I]
+        L.lfm_ssim_u8.restype = I
+        L.lfm_ssim_u8.argtypes = [V, V, V, I, I, I, V, I, V, C.c_size_t, V, V, V]
+        L.lfm_ssim_f32.restype = I
+        L.lfm_ssim_f32.argtypes = [V, V, I, I, I, I, V, I, V, C.c_size_t, V, V]
     L.lfm_song_embed.restype = I
     L.lfm_song_embed.argtypes = [V, I, V, V, V, V, V, V, F, V, I, V, V, V, I, I, I, V]
     L.lfm_fourier_embed.restype = I
@@ -789,6 +796,74 @@ def inpaint_composite(fake, img_u8, mask_u8, out=None):
     if out.dtype != torch.uint8 or tuple(out.shape) != (N, H, W, 3) or not out.is_contiguous() or out.device != img_u8.device:
         raise LfmHipError(f"inpaint_composite: out must be contiguous uint8 [{N}, {H}, {W}, 3] on {img_u8.device}, got {out.dtype} {tuple(out.shape)}")
     check(L.lfm_inpaint_composite_u8(ptr(fake), ptr(img_u8), ptr(mask_u8), ptr(out), N, H, W, stream_ptr(img_u8.device)), "lfm_inpaint_composite_u8")
+    return out
+
+
+SSIM_MAX_DIM = 4096  # csrc/ssim.h
+_ssim_windows = {}  # (device, window_size) -> the 1-D window on that device
+
+
+def ssim_gaussian(window_size, sigma=1.5):
+    """The reference's ``SSIM._gaussian`` (losses/ssim.py:36-40), operation for operation: a Python-float exp per tap, ``torch.Tensor`` (fp32), divided by
+    its fp32 sum.  fp32 [window_size] on the host."""
+    import numpy as np
+
+    g = torch.Tensor([np.exp(-((x - (window_size // 2)) ** 2) / float(2 * sigma**2)) for x in range(window_size)])
+    return g / g.sum()
+
+
+def _ssim_setup(what, device, N, H, W, window_size):
+    """-> (library, window on `device`, workspace, its size) for one call; the workspace is a fresh block of the caching allocator on the current stream."""
+    L = lib()
+    if not hasattr(L, "lfm_ssim_u8"):
+        raise LfmHipError("this liblfm_hip.so has no lfm_ssim_u8: rebuild it (python -m lfm_amd._build --force)")
+    ws = int(window_size)
+    if ws < 3 or ws > 11 or ws % 2 == 0:
+        raise LfmHipError(f"{what}: window_size must be odd and 3..11, got {window_size}")
+    need = L.lfm_ssim_workspace_bytes(N, H, W)
+    if need == 0:
+        raise LfmHipError(f"{what}: unsupported shape N={N} H={H} W={W} (N >= 1, 1 <= H, W <= {SSIM_MAX_DIM})")
+    key = (device, ws)
+    window = _ssim_windows.get(key)
+    if window is None:  # (a first call under graph capture would put the copy into the graph: warm up outside, as for every capture)
+        window = _ssim_windows[key] = ssim_gaussian(ws).to(device)
+    return L, window, torch.empty(need, dtype=torch.uint8, device=device), need
+
+
+def ssim_u8(a, b, mask=None, window_size=11):
+    """lfm_ssim_u8: two contiguous uint8 NHWC batches [N,H,W,3] on the device (each byte / 255) -> (SSIM per image fp32 [N], as the reference's
+    ``SSIM(window_size, size_average=False)`` gives it; the int64 sum of each image's mask bytes [N], or None without a mask uint8 [N,H,W]).  One tile kernel
+    and one reduce kernel on the current stream, no readback (capturable); bit-reproducible, independent of N and of the image's place in the batch."""
+    require_gpu(a, "ssim_u8")
+    for name, t in (("a", a), ("b", b)):
+        if t.dtype != torch.uint8 or t.dim() != 4 or t.shape[-1] != 3 or not t.is_contiguous() or t.shape != a.shape or t.device != a.device:
+            raise LfmHipError(f"ssim_u8: {name} must be contiguous uint8 [N, H, W, 3] on {a.device}, both alike, got {t.dtype} {tuple(t.shape)} strides "
+                              f"{t.stride()} on {t.device}")
+    N, H, W, _ = a.shape
+    if mask is not None and (mask.dtype != torch.uint8 or tuple(mask.shape) != (N, H, W) or not mask.is_contiguous() or mask.device != a.device):
+        raise LfmHipError(f"ssim_u8: mask must be contiguous uint8 [{N}, {H}, {W}] on {a.device}, got {mask.dtype} {tuple(mask.shape)} on {mask.device}")
+    L, window, ws, need = _ssim_setup("ssim_u8", a.device, N, H, W, window_size)
+    out = torch.empty(N, dtype=torch.float32, device=a.device)
+    mask_sum = torch.empty(N, dtype=torch.int64, device=a.device) if mask is not None else None
+    check(L.lfm_ssim_u8(ptr(a), ptr(b), ptr(mask), N, H, W, ptr(window), int(window_size), ptr(ws), need, ptr(out), ptr(mask_sum), stream_ptr(a.device)),
+          "lfm_ssim_u8")
+    return out, mask_sum
+
+
+def ssim_f32(a, b, window_size=11):
+    """lfm_ssim_f32: two contiguous fp32 NCHW batches [N,C,H,W] on the device, 1 <= C <= 4 -> SSIM per image fp32 [N] (``SSIM(window_size,
+    size_average=False)``).  As ssim_u8 otherwise."""
+    require_gpu(a, "ssim_f32")
+    for name, t in (("a", a), ("b", b)):
+        if t.dtype != torch.float32 or t.dim() != 4 or not t.is_contiguous() or t.shape != a.shape or t.device != a.device:
+            raise LfmHipError(f"ssim_f32: {name} must be contiguous fp32 [N, C, H, W] on {a.device}, both alike, got {t.dtype} {tuple(t.shape)} strides "
+                              f"{t.stride()} on {t.device}")
+    N, Cn, H, W = a.shape
+    if Cn < 1 or Cn > 4:
+        raise LfmHipError(f"ssim_f32: 1 <= C <= 4, got C={Cn}")
+    L, window, ws, need = _ssim_setup("ssim_f32", a.device, N, H, W, window_size)
+    out = torch.empty(N, dtype=torch.float32, device=a.device)
+    check(L.lfm_ssim_f32(ptr(a), ptr(b), N, Cn, H, W, ptr(window), int(window_size), ptr(ws), need, ptr(out), stream_ptr(a.device)), "lfm_ssim_f32")
     return out
 
 
