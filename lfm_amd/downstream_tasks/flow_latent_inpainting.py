@@ -142,7 +142,7 @@ def synthetic_pairs(n, size, seed=0):
 
 
 def main(argv=None):
-    from ..io_formats import begin_jpegs_device, finish_jpegs_device, save_indexed_jpegs, write_indexed_files
+    from ..batch_pipeline import JpegSink, run_in_flight
 
     args = driver_parser().parse_args(argv)
     if (args.images is None) != (args.masks is None):
@@ -166,25 +166,20 @@ def main(argv=None):
         from .. import inpaint_eval
 
         score = inpaint_eval.SSIMScore()
-    waiting = None  # --jpeg_encoder device: the previous batch's encoder job; its files are written while this batch's kernels run
-    for i, start in enumerate(range(0, imgs.shape[0], args.batch_size)):  # index = i * batch_size + j (:163; the last batch may be ragged)
-        image_u8, mask_u8 = imgs[start:start + args.batch_size].to(device), masks[start:start + args.batch_size].to(device)  # the bytes: 4 per pixel
+    sink = JpegSink(args.jpeg_encoder, save_dir)
+
+    def produce(i, model_cond, vae):  # index = i * batch_size + j (:163; the last batch may be ragged)
+        rows = slice(i * args.batch_size, (i + 1) * args.batch_size)
+        image_u8, mask_u8 = imgs[rows].to(device), masks[rows].to(device)  # the bytes: 4 per pixel
         out, _ = inpaint_batch_u8(model_cond, vae, image_u8, mask_u8, args, sample_posterior=args.posterior == "sample", prep_path=args.prep_path)
         if score is not None:
             score(out, image_u8, mask_u8)
-        if args.jpeg_encoder == "device":  # the encoder behind the composite on the same stream
-            job, done = begin_jpegs_device(out), torch.cuda.Event()
-            done.record()
-            if waiting is not None:
-                waiting[1].synchronize()
-                write_indexed_files(finish_jpegs_device(waiting[0]), save_dir, waiting[2])
-            waiting = (job, done, start)
-        else:
-            save_indexed_jpegs(out.cpu(), save_dir, start)
         print("generating batch ", i)
-    if waiting is not None:
-        waiting[1].synchronize()
-        write_indexed_files(finish_jpegs_device(waiting[0]), save_dir, waiting[2])
+        return sink.begin(out)  # device: the encoder behind the composite on the same stream
+
+    # device: a batch's files are written while the next batch's kernels run (one batch behind); host: right behind the batch
+    run_in_flight([(model_cond, vae, torch.cuda.current_stream(device))], -(-imgs.shape[0] // args.batch_size), produce,
+                  lambda i, job: sink.finish(job, i * args.batch_size), depth=1 if args.jpeg_encoder == "device" else 0)
     if score is not None:
         groups, names = inpaint_eval.area_bins(score.mask_sums, args.image_size, args.image_size)
         print(inpaint_eval.format_table(inpaint_eval.results_by_name(score, groups, names), title="SSIM of the composites before JPEG coding"))

@@ -176,7 +176,8 @@ def load_segmentation(path, size, num_cls):
 def main(argv=None):
     import os
 
-    from ..io_formats import begin_jpegs_device, finish_jpegs_device, save_indexed_jpegs, to_uint8_rounding, to_uint8_rounding_device, write_indexed_files
+    from ..batch_pipeline import JpegSink, run_in_flight
+    from ..io_formats import to_uint8_rounding, to_uint8_rounding_device
 
     args = build_parser().parse_args(argv)
     if not args.random_weights and args.segmentation is None:
@@ -193,23 +194,20 @@ def main(argv=None):
     save_dir = args.save_dir or "./mask2image_generated_samples/{}".format(args.dataset)
     os.makedirs(save_dir, exist_ok=True)
     torch.manual_seed(42)  # reference :71
-    waiting = None  # --jpeg_encoder device: the previous batch's encoder job; its files are written while this batch's kernels run
-    for i, start in enumerate(range(0, seg.shape[0], args.batch_size)):
-        batch = seg[start:start + args.batch_size].to(device)
+    on_device = getattr(args, "jpeg_encoder", "host") == "device"
+    sink = JpegSink("device" if on_device else "host", save_dir)
+    # torchvision.utils.save_image's conversion (its `normalized=True` (:146) is no keyword of it): on the host, or where the image lives with the encoder behind it
+    to_u8 = to_uint8_rounding_device if on_device else to_uint8_rounding
+
+    def produce(i, model_cond, vae):
+        batch = seg[i * args.batch_size:(i + 1) * args.batch_size].to(device)
         img, _ = synthesize_batch(model_cond, vae, cond_stage_model, batch, num_cls, args, cond_path=args.cond_path)
-        if getattr(args, "jpeg_encoder", "host") == "device":  # the same conversion where the image lives, then the encoder behind it on the same stream
-            job, done = begin_jpegs_device(to_uint8_rounding_device(img)), torch.cuda.Event()
-            done.record()
-            if waiting is not None:
-                waiting[1].synchronize()
-                write_indexed_files(finish_jpegs_device(waiting[0]), save_dir, waiting[2])
-            waiting = (job, done, start)
-        else:
-            save_indexed_jpegs(to_uint8_rounding(img), save_dir, start)  # torchvision.utils.save_image's conversion; its `normalized=True` (:146) is no keyword of it
         print("generating batch ", i)
-    if waiting is not None:
-        waiting[1].synchronize()
-        write_indexed_files(finish_jpegs_device(waiting[0]), save_dir, waiting[2])
+        return sink.begin(to_u8(img))
+
+    # device: a batch's files are written while the next batch's kernels run (one batch behind); host: right behind the batch
+    run_in_flight([(model_cond, vae, torch.cuda.current_stream(device))], -(-seg.shape[0] // args.batch_size), produce,
+                  lambda i, job: sink.finish(job, i * args.batch_size), depth=1 if on_device else 0)
 
 
 if __name__ == "__main__":

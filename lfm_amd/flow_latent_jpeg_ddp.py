@@ -14,9 +14,10 @@ import torch
 import torch.distributed as dist
 
 from . import test_flow_latent_ddp as base
+from .batch_pipeline import default_save_dir, join_lanes, lanes_for, run_in_flight
 from .flow_latent_jpeg import build_parser, takes_device_path, without_encoder_flag
 from .sampler.random_util import get_generator
-from .test_flow_latent import build_models, make_lanes, run_sampling
+from .test_flow_latent import build_models, run_sampling
 
 __all__ = ["run", "main"]
 
@@ -25,37 +26,24 @@ def run(args, model, vae, generator, rank, world, device, to_uint8, save_encoded
     """The sampling loop of test_flow_latent_ddp.run for one rank with the JPEGs encoded where the batch was made.  ``save_encoded(files, start)`` receives
     the finished files of this rank's batch whose first global index is ``start`` (file ``j`` is ``j * world + rank + start``).  Returns what was done:
     ``written`` lists (start, count) of THIS rank's batches."""
-    from collections import deque
-
     from .io_formats import begin_jpegs_device, finish_jpegs_device
 
     total, _, iters = base.shard_plan(args.n_sample, args.batch_size, world)
     if rank == 0:
         log(f"Total number of images that will be sampled: {total}")
-    n_lanes = int(getattr(args, "in_flight", 0) or 0) or 2
-    lanes = make_lanes(model, vae, device, n_lanes) if n_lanes > 1 else [(model, vae, torch.cuda.current_stream(device))]
-    written, pending = [], deque()
+    lanes = lanes_for(args, model, vae, device)
+    written = []
 
-    def drain():  # the batch submitted `lanes` iterations ago: its lengths, its compressed bytes, one write per image; no rank waits for another
-        job, done, i = pending.popleft()
-        done.synchronize()
+    def produce(i, mdl, va):  # the encoder rides the lane's stream
+        return begin_jpegs_device(to_uint8(run_sampling(mdl, va, args, args.batch_size, generator, device)))
+
+    def consume(i, job):  # the batch submitted `lanes` iterations ago: its lengths, its compressed bytes, one write per image; no rank waits for another
         start = i * args.batch_size * world
         save_encoded(finish_jpegs_device(job), start)
         written.append((start, int(job["images"].shape[0])))
 
-    for i in range(iters):
-        mdl, va, st = lanes[i % len(lanes)]
-        with torch.cuda.stream(st):
-            job = begin_jpegs_device(to_uint8(run_sampling(mdl, va, args, args.batch_size, generator, device)))  # the encoder rides the lane's stream
-            done = torch.cuda.Event()
-            done.record(st)
-        pending.append((job, done, i))
-        if len(pending) > len(lanes):
-            drain()
-    while pending:
-        drain()
-    for _, _, st in lanes:
-        torch.cuda.current_stream(device).wait_stream(st)
+    run_in_flight(lanes, iters, produce, consume)
+    join_lanes(lanes, device)
     return {"total": total, "iters": iters, "written": written, "gather_seconds": 0.0, "lanes": len(lanes)}
 
 
@@ -78,7 +66,7 @@ def main(argv=None):
     torch.manual_seed(args.seed)
     torch.cuda.manual_seed_all(args.seed)
     generator = get_generator(args.generator, args.n_sample, args.seed)
-    save_dir = args.save_dir or "./generated_samples/{}/exp{}_ep{}_m{}".format(args.dataset, args.exp, args.epoch_id, args.method)
+    save_dir = default_save_dir(args)
     res = run(args, model, vae, generator, rank, world, device, images_to_uint8,
               lambda files, start: write_indexed_files(files, save_dir, start, world_size=world, rank=rank))
     dist.barrier()

@@ -1,6 +1,6 @@
 """Sampling driver of the layout-to-image path with its conditioning stage: ``lfm_amd.test_flow_latent`` plus the token pipeline the reference leaves to its
-callers.  ``lfm_amd/test_flow_latent.py`` itself is a fixed yardstick of this repository (the file every pull request is measured with keeps its text), so the
-token flags live here, on a driver that takes every flag and serves every mode of that one and runs ITS ``run_sampling``, solvers, lanes and image writers.
+callers.  The plain driver keeps the reference's argument surface, so the token flags live here, on a driver that takes every flag of that one and runs ITS
+mode dispatch (``run_modes``), ``run_sampling``, solvers, lanes and image writers.
 
     python -m lfm_amd.flow_latent_layout --use_origin_adm --layout --layout_tokens tokens.npy [--cond_stage_ckpt FILE | --random_weights] <the driver's flags>
 
@@ -13,10 +13,6 @@ Five flags are added (absent from the reference):
 The tokens go through ``BERTEmbedder`` (lfm_amd/models/encoder.py) once per batch, before the solve.  The context reaches the model through a per-batch handle
 (``Conditioned``) that adds ``context=`` to every evaluation, so the plain driver's ``run_sampling`` -- labels, guidance doubling, either solver family, the
 null-half drop, the VAE decode -- runs as it is, not a copy of it."""
-import math
-import os
-import time
-
 import torch
 
 from . import test_flow_latent as tfl
@@ -126,100 +122,13 @@ def run_sampling(model, first_stage_model, cond, args, num_samples, generator, d
 
 
 def main(argv=None):
-    """The modes of ``lfm_amd.test_flow_latent.main`` (:246-344), each evaluation through ``Conditioned``."""
-    from .autoencoder import images_to_uint8
+    """The modes of ``lfm_amd.test_flow_latent.run_modes``, each evaluation through ``Conditioned``: the conditioner keeps one embedder handle per lane stream."""
     from .sampler.random_util import get_generator
 
     args = build_parser().parse_args(argv)
-    args.world_size = args.num_proc_node * args.num_process_per_node
-    torch.set_grad_enabled(False)
-    device = torch.device("cuda:{}".format(args.local_rank))
-    torch.cuda.set_device(device)
+    device = tfl.set_up(args)
     model, vae, cond = build_models(args, device)
-    generator = get_generator(args.generator, args.n_sample, args.seed)
-    latent = (4, args.image_size // 8, args.image_size // 8)
-
-    if args.compute_nfe:
-        total, trials = 0.0, 300
-        for _ in range(trials):
-            x0 = generator.randn(1, *latent).to(device)
-            x0, kw = tfl.make_model_kwargs(args, x0, generator, device)
-            _, nfe = tfl.sample_from_model(Conditioned(model, cond.context(1)), x0, kw, args)
-            total += float(nfe) / trials
-        print(f"Average NFE over {trials} trials: {int(total)}")
-        return
-    if args.measure_time:
-        x = generator.randn(1, *latent).to(device)
-        warm = Conditioned(model, cond.context(1))
-        for _ in range(10):
-            warm(torch.tensor(1.0, device=device), x)
-        times = []
-        for _ in range(300):
-            s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            s.record()
-            run_sampling(model, vae, cond, args, 1, generator, device)  # the encoder is part of a sample's time
-            e.record()
-            torch.cuda.synchronize()
-            times.append(s.elapsed_time(e))
-        tt = torch.tensor(times)
-        print("Inference time: {:.2f}+/-{:.2f}ms".format(float(tt.mean()), float(tt.std(unbiased=False))))
-        return
-    save_dir = args.save_dir or "./generated_samples/{}/exp{}_ep{}_m{}".format(args.dataset, args.exp, args.epoch_id, args.method)
-    if args.compute_fid:
-        n = args.batch_size
-        batches = int(math.ceil(args.n_sample / n))
-        t0 = time.time()
-        if getattr(args, "fid_feature_extractor", ""):
-            from .fid import FeatureStatistics, fid_against_reference_stats, load_feature_extractor
-
-            extract = load_feature_extractor(args.fid_feature_extractor, device)
-            stats = None
-            for _ in range(batches):
-                feats = extract(images_to_uint8(run_sampling(model, vae, cond, args, n, generator, device), rounding=True))
-                stats = stats or FeatureStatistics(feats.shape[1], feats.device)
-                stats.update(feats)
-            fid = fid_against_reference_stats(stats.all_reduce(), args.real_img_dir)
-            print("FID = {}".format(fid))
-            with open(args.output_log or os.devnull, "a") as f:
-                f.write("Epoch = {}, FID = {}\n".format(args.epoch_id, fid))
-            return
-        # batches in flight on the plain driver's lanes; the conditioner keeps one embedder handle per lane stream
-        from collections import deque
-
-        lanes = tfl.make_lanes(model, vae, device, int(getattr(args, "in_flight", 0) or 0) or 2)
-        pending = deque()
-
-        def drain(p):
-            p[0].synchronize()
-            tfl.save_images_uint8(p[1], save_dir, p[2] * n)
-
-        for i in range(batches):
-            mdl, va, st = lanes[i % len(lanes)]
-            with torch.cuda.stream(st):
-                u8 = images_to_uint8(run_sampling(mdl, va, cond, args, n, generator, device), rounding=True)
-                done = torch.cuda.Event()
-                done.record(st)
-            pending.append((done, u8, i))
-            if len(pending) > len(lanes):
-                drain(pending.popleft())
-        while pending:
-            drain(pending.popleft())
-        print(f"wrote {batches * n} images to {save_dir} in {time.time() - t0:.1f}s")
-        return
-    img = run_sampling(model, vae, cond, args, args.batch_size, generator, device)
-    from .io_formats import make_grid_nhwc, save_jpeg
-
-    if not args.use_karras_samplers:  # named as the plain driver names its sheet
-        save_path = "./samples_{}_{}_{}_{}".format(args.dataset, args.method, args.atol, args.rtol)
-    else:
-        save_path = "./samples_{}_{}_{}".format(args.dataset, args.method, args.num_steps)
-    if args.num_classes is not None and args.num_classes > 1:
-        save_path += "_cfg{}".format(args.cfg_scale)
-    save_path = (os.path.join(args.save_dir, os.path.basename(save_path)) if args.save_dir else save_path) + ".jpg"
-    if os.path.dirname(save_path):
-        os.makedirs(os.path.dirname(save_path), exist_ok=True)
-    save_jpeg(make_grid_nhwc(images_to_uint8(img, rounding=True).cpu(), nrow=8, padding=0), save_path)
-    print("Samples are save at '{}".format(save_path))
+    tfl.run_modes(args, model, vae, get_generator(args.generator, args.n_sample, args.seed), device, bind=lambda m, n: Conditioned(m, cond.context(n)))
 
 
 if __name__ == "__main__":

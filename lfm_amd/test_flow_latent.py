@@ -17,13 +17,14 @@ import time
 import torch
 from torch import nn
 
+from .batch_pipeline import JpegSink, default_save_dir, lanes_for, make_lanes, run_in_flight, sheet_path  # noqa: F401  (make_lanes: named here by its users)
 from .models import create_network
 from .sampler.karras_sample import karras_sample
 from .sampler.random_util import get_generator
 from .solvers import (ADAPTIVE_SOLVER, FIXER_SOLVER, fused_fixed_grid_available, odeint, sample_torchdiffeq_euler_fused)
 
 __all__ = ["ADAPTIVE_SOLVER", "FIXER_SOLVER", "NFECount", "sample_from_model", "sample_from_model_with_fixed_step_solver",
-           "run_sampling", "build_parser", "main"]
+           "run_sampling", "make_lanes", "build_parser", "run_modes", "main"]
 
 
 class NFECount(nn.Module):
@@ -120,21 +121,6 @@ def run_sampling(model, first_stage_model, args, num_samples, generator, device,
     if first_stage_model is None:
         return fake_sample
     return first_stage_model.decode(fake_sample / args.scale_factor).sample
-
-
-def make_lanes(model, vae, device, n_lanes):
-    """[(model, vae, stream)] x n_lanes for batches in flight on one GPU: lane 0 is the model itself, the others are concurrency twins (same packed weights, own
-    workspace / solver buffers / captured graphs).  Every lane stream first waits for the stream the weights were loaded and packed on.  Batches of a sampling job
-    are independent (reference test_flow_latent_ddp.py:128-146) and a lane's result is bit-identical to the one-lane result (tests/test_gpu_cosched.py)."""
-    from .solvers import concurrency_twin
-
-    cur = torch.cuda.current_stream(device)
-    lanes = []
-    for k in range(max(1, n_lanes)):
-        st = torch.cuda.Stream(device)
-        st.wait_stream(cur)
-        lanes.append((model if k == 0 else concurrency_twin(model), vae if k == 0 or vae is None else concurrency_twin(vae), st))
-    return lanes
 
 
 def load_checkpoint(model, path, device, trust_checkpoint=False):
@@ -243,54 +229,55 @@ def save_images_uint8(img_u8, save_dir, start_index, stride=1, offset=0):
     save_indexed_jpegs(img_u8.cpu(), save_dir, start_index, world_size=stride, rank=offset)
 
 
-def main(argv=None):
+def run_modes(args, model, vae, generator, device, bind=None, jpeg_encoder="host"):
+    """The four modes (--compute_nfe / --measure_time / --compute_fid / the default sample sheet) on built models.  ``bind(model, num_samples)`` returns what is
+    evaluated for a batch of that size (the layout driver binds the batch's context; default: the model itself); `jpeg_encoder` is who encodes --compute_fid's
+    per-image JPEGs (batch_pipeline.JpegSink)."""
     from .autoencoder import images_to_uint8
 
-    args = build_parser().parse_args(argv)
-    args.world_size = args.num_proc_node * args.num_process_per_node
-    torch.set_grad_enabled(False)
-    device = torch.device("cuda:{}".format(args.local_rank))
-    torch.cuda.set_device(device)
-    model, vae = build_models(args, device)
-    generator = get_generator(args.generator, args.n_sample, args.seed)
-
+    bind = bind or (lambda m, num_samples: m)
+    latent = (4, args.image_size // 8, args.image_size // 8)
     if args.compute_nfe:
         total, trials = 0.0, 300
         for _ in range(trials):
-            x0 = generator.randn(1, 4, args.image_size // 8, args.image_size // 8).to(device)
+            x0 = generator.randn(1, *latent).to(device)
             x0, kw = make_model_kwargs(args, x0, generator, device)
-            _, nfe = sample_from_model(model, x0, kw, args)
+            _, nfe = sample_from_model(bind(model, 1), x0, kw, args)
             total += float(nfe) / trials
         print(f"Average NFE over {trials} trials: {int(total)}")
         return
     if args.measure_time:
-        x = generator.randn(1, 4, args.image_size // 8, args.image_size // 8).to(device)
+        x = generator.randn(1, *latent).to(device)
+        warm = bind(model, 1)
         for _ in range(10):
-            model(torch.tensor(1.0, device=device), x)
+            warm(torch.tensor(1.0, device=device), x)
         times = []
         for _ in range(300):
             s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             s.record()
-            run_sampling(model, vae, args, 1, generator, device)
+            run_sampling(bind(model, 1), vae, args, 1, generator, device)  # what bind does (the layout encoder) is part of a sample's time
             e.record()
             torch.cuda.synchronize()
             times.append(s.elapsed_time(e))
         tt = torch.tensor(times)
         print("Inference time: {:.2f}+/-{:.2f}ms".format(float(tt.mean()), float(tt.std(unbiased=False))))
         return
-    save_dir = args.save_dir or "./generated_samples/{}/exp{}_ep{}_m{}".format(args.dataset, args.exp, args.epoch_id, args.method)
     if args.compute_fid:
         n = args.batch_size
-        total_samples = int(math.ceil(args.n_sample / n) * n)
+        batches = int(math.ceil(args.n_sample / n))
         t0 = time.time()
+
+        def sample_u8(mdl, va):  # the single-process script writes through torchvision.utils.save_image: ROUNDING uint8 conversion (:264-269)
+            return images_to_uint8(run_sampling(bind(mdl, n), va, args, n, generator, device), rounding=True)
+
         if getattr(args, "fid_feature_extractor", ""):
             # on-device statistics (lfm_amd/fid.py): the images never leave the GPU; mu / sigma / Frechet distance as fid_score.py:230-283
             from .fid import FeatureStatistics, fid_against_reference_stats, load_feature_extractor
 
             extract = load_feature_extractor(args.fid_feature_extractor, device)
             stats = None
-            for i in range(total_samples // n):
-                feats = extract(images_to_uint8(run_sampling(model, vae, args, n, generator, device), rounding=True))
+            for _ in range(batches):
+                feats = extract(sample_u8(model, vae))
                 stats = stats or FeatureStatistics(feats.shape[1], feats.device)
                 stats.update(feats)
             fid = fid_against_reference_stats(stats.all_reduce(), args.real_img_dir)
@@ -298,50 +285,39 @@ def main(argv=None):
             with open(args.output_log or os.devnull, "a") as f:
                 f.write("Epoch = {}, FID = {}\n".format(args.epoch_id, fid))
             return
-        # batches in flight: consecutive batches alternate between HIP streams (solvers.concurrency_twin: the same weights, own scratch and captured graphs),
-        # and the host converts / writes batch i - lanes while batches i - lanes + 1 .. i run (every lane stays busy under the JPEG encoding) -- the reference's
-        # loop (:264-269) serialises solve, decode and JPEG writes
-        from collections import deque
-
-        lanes = make_lanes(model, vae, device, int(getattr(args, "in_flight", 0) or 0) or 2)
-        pending = deque()
-
-        def drain(p):
-            p[0].synchronize()
-            # the single-process script writes through torchvision.utils.save_image: ROUNDING uint8 conversion (:264-269)
-            save_images_uint8(p[1], save_dir, p[2] * n)
-
-        for i in range(total_samples // n):
-            mdl, va, st = lanes[i % len(lanes)]
-            with torch.cuda.stream(st):
-                u8 = images_to_uint8(run_sampling(mdl, va, args, n, generator, device), rounding=True)
-                done = torch.cuda.Event()
-                done.record(st)
-            pending.append((done, u8, i))
-            if len(pending) > len(lanes):
-                drain(pending.popleft())
-        while pending:
-            drain(pending.popleft())
-        print(f"wrote {total_samples} images to {save_dir} in {time.time() - t0:.1f}s; FID needs pytorch_fid + Inception weights "
-              "(not available offline): run the reference's pytorch_fid on that directory (lfm_amd.io_formats has the statistics "
-              "reader and the Frechet distance)")
+        # batches in flight: consecutive batches alternate between the lanes' HIP streams, and the host converts / writes batch i - lanes while batches
+        # i - lanes + 1 .. i run (every lane stays busy under the JPEG writing) -- the reference's loop (:264-269) serialises solve, decode and JPEG writes
+        sink = JpegSink(jpeg_encoder, default_save_dir(args))
+        run_in_flight(lanes_for(args, model, vae, device), batches, lambda i, mdl, va: sink.begin(sample_u8(mdl, va)), lambda i, job: sink.finish(job, i * n))
+        print(f"wrote {batches * n} images to {sink.save_dir} in {time.time() - t0:.1f}s{' (JPEGs encoded on the device)' if jpeg_encoder == 'device' else ''}; "
+              "FID needs pytorch_fid + Inception weights (not available offline): run the reference's pytorch_fid on that directory (lfm_amd.io_formats has the "
+              "statistics reader and the Frechet distance)")
         return
-    img = run_sampling(model, vae, args, args.batch_size, generator, device)
+    img = run_sampling(bind(model, args.batch_size), vae, args, args.batch_size, generator, device)
     # default mode: ONE sample sheet, nrow=8, padding=0, named as the reference names it (test_flow_latent.py:288-298)
     from .io_formats import make_grid_nhwc, save_jpeg
 
-    if not args.use_karras_samplers:
-        save_path = "./samples_{}_{}_{}_{}".format(args.dataset, args.method, args.atol, args.rtol)
-    else:
-        save_path = "./samples_{}_{}_{}".format(args.dataset, args.method, args.num_steps)
-    if args.num_classes is not None and args.num_classes > 1:
-        save_path += "_cfg{}".format(args.cfg_scale)
-    save_path = os.path.join(args.save_dir, os.path.basename(save_path)) if args.save_dir else save_path
-    save_path += ".jpg"
+    save_path = sheet_path(args)
     if os.path.dirname(save_path):
         os.makedirs(os.path.dirname(save_path), exist_ok=True)
     save_jpeg(make_grid_nhwc(images_to_uint8(img, rounding=True).cpu(), nrow=8, padding=0), save_path)
     print("Samples are save at '{}".format(save_path))
+
+
+def set_up(args):
+    """What every single-process main does between parsing and building the models; returns the device."""
+    args.world_size = args.num_proc_node * args.num_process_per_node
+    torch.set_grad_enabled(False)
+    device = torch.device("cuda:{}".format(args.local_rank))
+    torch.cuda.set_device(device)
+    return device
+
+
+def main(argv=None):
+    args = build_parser().parse_args(argv)
+    device = set_up(args)
+    model, vae = build_models(args, device)
+    run_modes(args, model, vae, get_generator(args.generator, args.n_sample, args.seed), device)
 
 
 if __name__ == "__main__":

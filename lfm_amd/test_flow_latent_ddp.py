@@ -12,6 +12,7 @@ import os
 import torch
 import torch.distributed as dist
 
+from .batch_pipeline import default_save_dir, join_lanes, lanes_for
 from .sampler.random_util import get_generator
 from .test_flow_latent import build_models, build_parser, run_sampling, save_images_uint8
 
@@ -145,16 +146,12 @@ def run(args, model, vae, generator, rank, world, device, to_uint8, save=None, l
     # Batches in flight per GPU: the batches of a sampling job are independent (reference :128-146), so consecutive batches go to alternating HIP streams
     # ("lanes": the same weights, own scratch and captured solver graphs -- solvers.concurrency_twin) and overlap on the chip; results are bit-identical to one
     # lane (tests/test_gpu_cosched.py).  Noise is still drawn in batch order from the one generator, file indices and the gather order do not change.
-    n_lanes = int(getattr(args, "in_flight", 0) or 0) or (2 if torch.device(device).type == "cuda" else 1)
-    lanes = [(model, vae, None)]
-    if n_lanes > 1 and torch.device(device).type == "cuda":
-        from .test_flow_latent import make_lanes
-
-        lanes = make_lanes(model, vae, device, n_lanes)
+    lanes = lanes_for(args, model, vae, device)
     # The host's share (device-to-host copy, JPEG encoding on rank 0) is taken OUTSIDE the lane's stream context, on a copy stream of its own, and for the batch
     # submitted `lanes` iterations ago: inside the context the copy queued on the lane stream behind the batch just enqueued, the host could not launch the next
-    # batch before that one had finished, and with world > 1 every rank waited for rank 0 at the next all-gather (round-5 advisor finding).
-    depth = len(lanes) if lanes[0][2] is not None else 1
+    # batch before that one had finished, and with world > 1 every rank waited for rank 0 at the next all-gather (round-5 advisor finding).  This is
+    # batch_pipeline.run_in_flight's order with the gather in between: the pending queue and its events are GatherPipeline's.
+    depth = len(lanes)
     pipe = GatherPipeline(world, device, depth=depth)
     copy_stream = torch.cuda.Stream(device) if lanes[0][2] is not None else None
 
@@ -175,9 +172,7 @@ def run(args, model, vae, generator, rank, world, device, to_uint8, save=None, l
         drain(prev, i - depth)
     for i in range(max(0, iters - depth), iters):
         drain(pipe.flush(), i)
-    if lanes[0][2] is not None:
-        for _, _, st in lanes:
-            torch.cuda.current_stream(device).wait_stream(st)
+    join_lanes(lanes, device)
     return {"total": total, "iters": iters, "written": written, "gather_seconds": pipe.gather_seconds, "lanes": len(lanes)}
 
 
@@ -207,7 +202,7 @@ def main(argv=None, hooks=None):
     if device.type == "cuda":
         torch.cuda.manual_seed_all(args.seed)
     generator = get_generator(args.generator, args.n_sample, args.seed)
-    save_dir = args.save_dir or "./generated_samples/{}/exp{}_ep{}_m{}".format(args.dataset, args.exp, args.epoch_id, args.method)
+    save_dir = default_save_dir(args)
     save = hooks.get("save") or (lambda block, start: save_images_uint8(block, save_dir, start))
     res = run(args, model, vae, generator, rank, world, device, hooks.get("to_uint8", images_to_uint8), save, extractor=hooks.get("extractor"))
     dist.barrier()
